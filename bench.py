@@ -18,6 +18,15 @@ Gaussian set, renders its own camera, and the 59-float/Gaussian gradient is
 summed across ranks with one RCCL all-reduce per step (weak scaling).
 
 Prints ONE JSON line on rank 0 (see the keys at the bottom).
+
+A plain run does only what the headline figure needs: set-up, warm-up, the --steps timed steps, the line.
+--full adds everything else the line used to carry -- the VALU / copy calibration of the box, the per-kernel
+table and roofline (extra untimed steps, rocprofv3 counter passes), the K steps again with the unchanged models'
+host read-backs, the CPU oracle baselines and the parity of this run's results against it, and the config-3 /
+config-5 training record (`--train-iters`, a few minutes).
+--dump-outputs DIR writes what the last timed step handed its caller as DIR/<name>.npy (float32): the images, the
+projection's per-Gaussian outputs and the parameters' gradients; per-Gaussian arrays as a fixed, seeded sample of
+rows (`outputs_of_step`), so that two builds can be compared output for output on identical inputs.
 """
 import argparse
 import json
@@ -64,16 +73,17 @@ KERNELS = (
 
 class KernelTimers:
     """HIP-event brackets around every native call.  The native calls enqueue
-    on torch's current stream, which is where these events are recorded."""
+    on torch's current stream, which is where these events are recorded.
+    `install=False` (a plain run: no per-kernel table) leaves the native calls unwrapped."""
 
-    def __init__(self):
+    def __init__(self, install=True):
         import rasterizer.cuda as C
 
         self.C = C
         self.pairs = {k: [] for _, k in KERNELS}
         self.enabled = False
         self._orig = {}
-        for attr, key in KERNELS:
+        for attr, key in (KERNELS if install else ()):
             fn = getattr(C, attr)
             self._orig[attr] = fn
             setattr(C, attr, self._wrap(fn, key))
@@ -202,6 +212,49 @@ def calibration(dev, repeats=5):
 
 def _rnd(v, k):
     return None if v is None else round(v, k)
+
+
+DUMP_GAUSSIANS = 1 << 16  # per-Gaussian arrays: a fixed, seeded sample of this many rows (all rows below it)
+DUMP_PIXELS = 1 << 21     # images: every pixel up to this many (1920x1080 included), a fixed, seeded sample beyond
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def outputs_of_step(out, params, pixels):
+    """What one step of the timed path handed its caller, on the host as float32: the images (`rgb`, `alpha`, and
+    `depth` with --render-depth), the projection's per-Gaussian outputs and the parameters' gradients (`grad_<name>`).
+    The row samples depend only on N and the image size, so that two runs with the same arguments hold the same
+    elements (1 M Gaussians at 1080p: 33 MB of images + 18 MB of per-Gaussian rows)."""
+    dev = params["means3d"].device
+
+    def sample(total, limit, seed):
+        if total <= limit:
+            return None
+        return torch.from_numpy(np.sort(np.random.default_rng(seed).choice(total, size=limit, replace=False))).to(dev)
+
+    g_idx = sample(params["means3d"].shape[0], DUMP_GAUSSIANS, 0)
+    p_idx = sample(pixels, DUMP_PIXELS, 1)
+
+    def host(t, idx, image=False):
+        t = t.detach()
+        if image and idx is not None:
+            t = t.reshape(pixels, -1)  # one row per pixel
+        if idx is not None:
+            t = t.index_select(0, idx)
+        return t.float().cpu().numpy()
+
+    res = {k: host(out[k], p_idx, image=True) for k in ("rgb", "alpha", "depth") if out.get(k) is not None}
+    res.update({k: host(out[k], g_idx) for k in ("xys", "depths", "radii", "conics", "num_tiles_hit", "rgbs")
+                if out.get(k) is not None})
+    res.update({f"grad_{k}": host(p.grad, g_idx) for k, p in params.items() if p.grad is not None})
+    total = sum(a.nbytes for a in res.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes"
+    return res
+
+
+def write_outputs(directory, arrays):
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, f"{k}.npy"), a)
 
 
 def parity_vs_oracle(gpu, ref):
@@ -608,7 +661,7 @@ def trained_raster(args, ply, env):
     # (the CPU oracle runs on this model too -- a few seconds on the host's cores: `parity_vs_oracle` of the one
     #  realistic list distribution the line has, with the job order, tail splitting and the measured split ratio
     #  active; VERDICT r5 item 2.  The one-thread baseline is skipped.)
-    cmd = [sys.executable, os.path.abspath(__file__), "--scene", f"ply:{ply}", "--steps", "50", "--warmup", "10",
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--scene", f"ply:{ply}", "--steps", "50", "--warmup", "10",
            "--train-iters", "0", "--no-cpu-one-thread", "--no-synced-regions"] + small + (["--no-pmc"] if args.no_pmc else [])
     try:
         out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=420)
@@ -750,6 +803,12 @@ def main():
     # --scale-hi 0.05` runs the denser variant (numbers for both in DESIGN.md).
     ap.add_argument("--scale-lo", type=float, default=0.0025)
     ap.add_argument("--scale-hi", type=float, default=0.025)
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: calibration, per-kernel table and roofline (counter "
+                         "passes), the regions with the caller's read-backs, CPU baselines and oracle parity, the "
+                         "training record; the --no-* options and --event-every / --train-iters select within it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cpu-one-thread", action="store_true",
                     help="skip the one-thread CPU baseline on the 60 k-Gaussian subset (10-30 s); the all-threads baseline "
@@ -793,7 +852,7 @@ def main():
     ap.add_argument("--ply-views", type=int, default=48)
     ap.add_argument("--caller-syncs", default="off", choices=["off", "on", "camera"],
                     help="run the MAIN timed region with the unchanged models' host read-backs in the caller (profiling "
-                         "runs; the default line reports all three modes anyway)")
+                         "runs; a --full line reports all three modes anyway)")
     ap.add_argument("--force-exchange", action="store_true",
                     help="with --gpus 1: create the process group anyway (one rank) and run the gradient exchange "
                          "through it -- every collective of the N > 1 path goes through the backend as an identity "
@@ -865,7 +924,9 @@ def main():
     from harness.parallel import GradientExchange
     from harness.pipeline import CameraTensors, render_view
 
-    timers = KernelTimers()
+    # per-kernel HIP events are a --full figure: a plain run leaves the native calls unwrapped
+    event_every = args.event_every if args.full else 0
+    timers = KernelTimers(install=args.full)
     if args.deterministic:
         from rasterizer import rasterize as _Rd
 
@@ -988,14 +1049,16 @@ def main():
 
     from rasterizer.cuda._backend import lib as _native
 
-    staged = torch.zeros(2, dtype=torch.int64, device=dev)
-    torch.cuda.synchronize()
-    _native().gsr_debug_count_staged(ctypes.c_void_p(staged.data_ptr()))
-    step()
-    torch.cuda.synchronize()
-    _native().gsr_debug_count_staged(None)
-    raster_launches = 2 if (args.render_depth and not args.fused_depth) else 1
-    staged_fwd, staged_bwd = (int(v) // raster_launches for v in staged.tolist())
+    staged_fwd = staged_bwd = None
+    if args.full:  # (for the roofline only)
+        staged = torch.zeros(2, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize()
+        _native().gsr_debug_count_staged(ctypes.c_void_p(staged.data_ptr()))
+        step()
+        torch.cuda.synchronize()
+        _native().gsr_debug_count_staged(None)
+        raster_launches = 2 if (args.render_depth and not args.fused_depth) else 1
+        staged_fwd, staged_bwd = (int(v) // raster_launches for v in staged.tolist())
 
     # A full pass of Python's cyclic collector over the ~170 k objects torch leaves tracked takes ~30 ms: inside a
     # 100-ms timed region that is 0.3 ms per step of pure artefact (tools/exp/gc_frames.py: it decided whether the
@@ -1006,7 +1069,7 @@ def main():
     gc.collect()
     # (one bracketed step now: the per-kernel HIP events are created on first use, and the first timed step is a
     #  bracketed one -- with 20 timed steps that one-off showed as a 1.8-ms first step)
-    timers.enabled = args.event_every > 0
+    timers.enabled = event_every > 0
     step()
     timers.enabled = False
     for k_ in timers.pairs:
@@ -1050,15 +1113,17 @@ def main():
     for i in range(args.steps):
         # per-kernel HIP events on every `event_every`-th timed step: a pair of event
         # records per native call costs ~4 us of GPU idle time (18 pairs: 5 % of a step)
-        timers.enabled = args.event_every > 0 and i % args.event_every == 0
+        timers.enabled = event_every > 0 and i % event_every == 0
         bracketed_steps += int(timers.enabled)
-        step()
+        out = step()
         marks[i + 1].record()
     barrier()
     elapsed = time.perf_counter() - t0
     timers.enabled = False
-    calib = calibration(dev) if rank == 0 else None
+    calib = calibration(dev) if rank == 0 and args.full else None
     step_ms = np.array([marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)])
+    # what the last timed step handed its caller (before the untimed --full steps below overwrite the gradients)
+    dumped = outputs_of_step(out, params, W * H) if args.dump_outputs and rank == 0 else None
 
     # The product path builds a view's tile lists on a side stream, next to the caller's own work, and composites in
     # the same native call where it can: HIP events around "one stage" do not isolate anything there.  The per-stage
@@ -1066,7 +1131,7 @@ def main():
     # (GSR_SPECULATE=0, `one_call` = 0: the same kernels, the same inputs); the compositing backward -- the
     # dominant kernel of `roofline` -- is bracketed inside the timed region as well, and that is the figure used.
     pairs_timed, iso_steps = timers.pairs, 0
-    if args.event_every > 0:  # (every rank: a step carries the gradient exchange's collectives)
+    if event_every > 0:  # (every rank: a step carries the gradient exchange's collectives)
         from rasterizer import rasterize as _Riso
 
         from rasterizer.cuda import _tuning as _Tune
@@ -1112,7 +1177,7 @@ def main():
     # `gs-train` gets with the models as they are.
     synced = {}
     for mode, key in ((True, "caller_syncs"), ("camera", "caller_and_camera_syncs")):
-        if args.no_synced_regions:
+        if args.no_synced_regions or not args.full:
             synced[key] = (None, None)
             continue
         for _ in range(min(3, args.warmup)):
@@ -1130,7 +1195,7 @@ def main():
             el = float(tt.item())
         synced[key] = (1e3 * el / args.steps, world * pixels / (el / args.steps) / 1e6)
     gpu_results = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not dp:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not dp:
         # one more (untimed) step whose results go to the host: what `parity_vs_oracle` checks
         for p in plist:
             p.grad = None
@@ -1151,8 +1216,69 @@ def main():
         dist.destroy_process_group()
 
     if rank == 0:
-        kern_ms = timers.summary_ms()
+        if dumped is not None:
+            write_outputs(args.dump_outputs, dumped)
         tiles = ((W + 15) // 16) * ((H + 15) // 16)
+        res_name = "1080p" if (W, H) == (1920, 1080) else ("4K" if (W, H) == (3840, 2160) else f"{W}x{H}")
+        n_name = f"{N // 1_000_000}M" if N % 1_000_000 == 0 else (f"{N // 1000}k" if N % 1000 == 0 else str(N))
+        line = {
+            "metric": f"raster fwd+bwd Mpix/s @{res_name} ({n_name} Gaussians, SH{deg})"
+                      + ("; train iters/s in `train`" if args.full and args.train_iters > 0 else ""),
+            "value": round(value, 2),
+            "unit": "Mpix/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 4),
+            "ms_per_step_median": round(float(np.median(step_ms)), 4),
+            "ms_per_step_p10_p90": [round(float(np.percentile(step_ms, 10)), 4),
+                                    round(float(np.percentile(step_ms, 90)), 4)],
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "config": {
+                "workload": (f"{N} Gaussians of a TRAINED model ({os.path.basename(args.scene[4:])}; view {args.ply_view} of "
+                             f"the training orbit), " if args.scene.startswith("ply:") else
+                             (f"{N} Gaussians of the held-out family '{args.scene}' (harness.scene.make_heldout_scene), "
+                              if args.scene in S.HELDOUT_KINDS else
+                              f"{N} random Gaussians (SURVEY 8d, seed 42, scales log-U[{args.scale_lo},{args.scale_hi}]), ")) +
+                            f"SH degree {deg}, {W}x{H}, block 16, fwd+bwd through the rasterizer autograd API"
+                            + ((" + depth image from the same compositing pass (gs_fused)" if args.fused_depth
+                               else " + differentiable depth pass") if args.render_depth else "")
+                            + (", deterministic backward" if args.deterministic else ""),
+                "intersections_per_gaussian": round(num_intersects / N, 2),
+                "gaussians": N, "visible": n_visible, "intersections": num_intersects,
+                "list_entries": list_entries,
+                "mean_gaussians_per_tile": round(num_intersects / tiles, 1),
+                "tile_list_length": tile_hist, "scene": args.scene, "two_round_lists": two_round,
+                "cpu_bind": cpu_bind,
+                # (inside `config` so that the driver's `parsed` keeps them)
+                "timing": {"ms_per_step_median": round(float(np.median(step_ms)), 4),
+                           "ms_per_step_p10_p90": [round(float(np.percentile(step_ms, 10)), 4),
+                                                   round(float(np.percentile(step_ms, 90)), 4)],
+                           "fixed_warmup_steps": fixed_warmup_steps, "fixed_warmup_s": round(fixed_warmup_s, 3),
+                           "ms_per_step_each": ([round(float(v), 4) for v in step_ms] if args.steps <= 40 else None),
+                           "what": f"--warmup steps, then {FIXED_WARMUP_SECONDS} s of the same workload untimed, then "
+                                   "exactly --steps timed steps (per-step figures: HIP events between steps)"},
+                "parallelism": (f"dp{world} (per-view; "
+                                + ("geometry gradients all-reduced (one flat message), SH gradient formed on every rank "
+                                   "from the all-gathered 12-byte colour cotangents (gsr_sh_backward_views), both started "
+                                   "from autograd hooks; " if sh_views else
+                                   "per-parameter all-reduce started from autograd hooks, overlapping "
+                                   "the backward; active SH bands only; ")
+                                + ("averaged in the collective, RCCL)" if args.backend == "nccl" else
+                                   f"{args.backend}: ranks share GPUs, not a measurement configuration)"))
+                               if world > 1 else "single",
+            },
+            "allreduce_bytes": allreduce_bytes,
+        }
+        if not args.full:
+            print(json.dumps(line), flush=True)
+            return
+
+        kern_ms = timers.summary_ms()
         K = S.num_sh_bases(deg)
         # per-kernel bytes for what one launch processes (the lists as built: `list_entries`);
         # the end-to-end figure prices the job as SURVEY 8(d) defines it (the reference's lists)
@@ -1186,8 +1312,8 @@ def main():
         # counter passes over a short run of this same command (skipped with --no-pmc / N > 1)
         stage_traffic = None
         if world == 1 and not args.no_pmc:
-            sub = [a for a in sys.argv[1:] if a not in ("--no-cpu-baseline",)]
-            for flag in ("--steps", "--warmup", "--event-every", "--gpus", "--train-iters"):
+            sub = [a for a in sys.argv[1:] if a not in ("--no-cpu-baseline",) and not a.startswith("--dump-outputs=")]
+            for flag in ("--steps", "--warmup", "--event-every", "--gpus", "--train-iters", "--dump-outputs"):
                 while flag in sub:
                     i = sub.index(flag)
                     del sub[i:i + 2]
@@ -1271,20 +1397,9 @@ def main():
             if not args.no_cpu_one_thread:
                 cpu1 = cpu_baseline_one_thread(sc, cam, bg_np, v_img_np, v_alpha_np, deg)
                 cpu1["value"] = round(cpu1["value"], 4)
-        res_name = "1080p" if (W, H) == (1920, 1080) else ("4K" if (W, H) == (3840, 2160) else f"{W}x{H}")
-        n_name = f"{N // 1_000_000}M" if N % 1_000_000 == 0 else (f"{N // 1000}k" if N % 1000 == 0 else str(N))
-
-        line = {
-            "metric": f"raster fwd+bwd Mpix/s @{res_name} ({n_name} Gaussians, SH{deg})"
-                      + ("; train iters/s in `train`" if args.train_iters > 0 else ""),
-            "value": round(value, 2),
+        line.update({
             "value_normalised": (round(value * CALIBRATION_REFERENCE_VALU_TOPS / calib["valu_Tops"], 2)
                                  if calib and calib.get("valu_Tops") else None),
-            "unit": "Mpix/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
             # the same steps with the unchanged models' host read-backs in the caller (see `synced` above)
             "value_with_caller_syncs": _rnd(synced["caller_syncs"][1], 2),
             "ms_per_step_with_caller_syncs": _rnd(synced["caller_syncs"][0], 4),
@@ -1296,51 +1411,6 @@ def main():
                                   "(vanilla_gs.py:784,811) block the host twice per view; caller_and_camera_syncs: plus "
                                   "the eight intrinsics read-backs ahead of the projection (:736-740,772-773), the first "
                                   "of which drains the stream; `value` = no read-backs"),
-            "ms_per_step_median": round(float(np.median(step_ms)), 4),
-            "ms_per_step_p10_p90": [round(float(np.percentile(step_ms, 10)), 4),
-                                    round(float(np.percentile(step_ms, 90)), 4)],
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {
-                "workload": (f"{N} Gaussians of a TRAINED model ({os.path.basename(args.scene[4:])}; view {args.ply_view} of "
-                             f"the training orbit), " if args.scene.startswith("ply:") else
-                             (f"{N} Gaussians of the held-out family '{args.scene}' (harness.scene.make_heldout_scene), "
-                              if args.scene in S.HELDOUT_KINDS else
-                              f"{N} random Gaussians (SURVEY 8d, seed 42, scales log-U[{args.scale_lo},{args.scale_hi}]), ")) +
-                            f"SH degree {deg}, {W}x{H}, block 16, fwd+bwd through the rasterizer autograd API"
-                            + ((" + depth image from the same compositing pass (gs_fused)" if args.fused_depth
-                               else " + differentiable depth pass") if args.render_depth else "")
-                            + (", deterministic backward" if args.deterministic else ""),
-                "intersections_per_gaussian": round(num_intersects / N, 2),
-                "gaussians": N, "visible": n_visible, "intersections": num_intersects,
-                "list_entries": list_entries,
-                "mean_gaussians_per_tile": round(num_intersects / tiles, 1),
-                "tile_list_length": tile_hist, "scene": args.scene, "two_round_lists": two_round,
-                "cpu_bind": cpu_bind,
-                # (inside `config` so that the driver's `parsed` keeps them)
-                "timing": {"ms_per_step_median": round(float(np.median(step_ms)), 4),
-                           "ms_per_step_p10_p90": [round(float(np.percentile(step_ms, 10)), 4),
-                                                   round(float(np.percentile(step_ms, 90)), 4)],
-                           "fixed_warmup_steps": fixed_warmup_steps, "fixed_warmup_s": round(fixed_warmup_s, 3),
-                           "ms_per_step_each": ([round(float(v), 4) for v in step_ms] if args.steps <= 40 else None),
-                           "what": f"--warmup steps, then {FIXED_WARMUP_SECONDS} s of the same workload untimed, then "
-                                   "exactly --steps timed steps (per-step figures: HIP events between steps)"},
-                "calibration": calib,
-                "value_normalised": (round(value * CALIBRATION_REFERENCE_VALU_TOPS / calib["valu_Tops"], 2)
-                                     if calib and calib.get("valu_Tops") else None),
-                "parallelism": (f"dp{world} (per-view; "
-                                + ("geometry gradients all-reduced (one flat message), SH gradient formed on every rank "
-                                   "from the all-gathered 12-byte colour cotangents (gsr_sh_backward_views), both started "
-                                   "from autograd hooks; " if sh_views else
-                                   "per-parameter all-reduce started from autograd hooks, overlapping "
-                                   "the backward; active SH bands only; ")
-                                + ("averaged in the collective, RCCL)" if args.backend == "nccl" else
-                                   f"{args.backend}: ranks share GPUs, not a measurement configuration)"))
-                               if world > 1 else "single",
-            },
             "roofline": roofline,
             "cpu_baseline": cpu,
             "parity_vs_oracle": parity,
@@ -1361,8 +1431,12 @@ def main():
             "allreduce_ms": (round(float(np.mean([a.elapsed_time(b) for a, b in comm_events])), 4)
                              if comm_events else None),
             "allreduce_ms_note": "exposed part: from the end of the queued backward to the last collective" if comm_events else None,
-            "allreduce_bytes": allreduce_bytes,
-        }
+        })
+        line["config"].update({
+            "calibration": calib,
+            "value_normalised": (round(value * CALIBRATION_REFERENCE_VALU_TOPS / calib["valu_Tops"], 2)
+                                 if calib and calib.get("valu_Tops") else None),
+        })
         # the second half of BASELINE's metric: config 3 (N = 1) / config 4 (N > 1) training, timed inside
         # this run (a fresh process: its failure cannot cost the line above)
         line["train"] = train_record(args, world) if args.train_iters > 0 else None

@@ -23,7 +23,7 @@ def _run(extra):
 
 
 def test_single_gpu_line_has_the_contract_fields():
-    d = _run([])
+    d = _run(["--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -51,6 +51,33 @@ def test_single_gpu_line_has_the_contract_fields():
     assert c["kind"] in ("port", "reference") and c["value"] > 0 and c["cores"] >= 1
 
 
+def test_plain_line_is_the_headline_alone_and_dumps_the_last_step(tmp_path):
+    """A plain run: the headline fields, none of what --full adds, and with --dump-outputs the arrays of its last
+    timed step as float32 .npy files (60 000 Gaussians: every row; 640 x 360: every pixel)."""
+    import numpy as np
+
+    d = _run(["--dump-outputs", str(tmp_path)])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert k in d, k
+    assert d["steps"] == 4 and d["warmup"] == 2 and d["unit"] == "Mpix/s" and d["higher_is_better"] is True
+    assert abs(d["value"] - 640 * 360 / d["ms_per_step"] / 1e3) < 0.01 * d["value"]
+    for k in ("roofline", "cpu_baseline", "parity_vs_oracle", "kernels", "train", "value_with_caller_syncs"):
+        assert k not in d, k
+    assert "calibration" not in d["config"] and "train" not in d["metric"]
+    shapes = {"rgb": (360, 640, 3), "alpha": (360, 640, 1), "xys": (60000, 2), "radii": (60000,),
+              "grad_means3d": (60000, 3), "grad_scales": (60000, 3), "grad_quats": (60000, 4),
+              "grad_opacities": (60000, 1), "grad_sh_coeffs": (60000, 16, 3)}
+    files = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(shapes) <= set(files), sorted(files)
+    for k, a in files.items():
+        assert a.dtype == np.float32, k
+        assert k not in ("rgb", "alpha") and not k.startswith("grad_") or np.isfinite(a).all(), k
+    for k, s in shapes.items():
+        assert files[k].shape == s, (k, files[k].shape)
+    assert sum(a.nbytes for a in files.values()) <= 64_000_000
+    assert (files["radii"] > 0).any() and np.abs(files["grad_means3d"]).max() > 0
+
+
 def test_plain_invocation_with_two_gpus_spawns_its_ranks():
     d = _run(["--gpus", "2", "--backend", "gloo", "--no-cpu-baseline"])
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["value"] > 0
@@ -72,7 +99,7 @@ def test_eight_ranks_as_the_driver_will_launch_them():
     base = ["--gaussians", "12000", "--width", "320", "--height", "180", "--steps", "2", "--warmup", "1", "--no-pmc"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + base +
-                         ["--gpus", "8", "--backend", "gloo", "--train-small", "--train-iters", "12", "--no-cogs",
+                         ["--full", "--gpus", "8", "--backend", "gloo", "--train-small", "--train-iters", "12", "--no-cogs",
                           "--no-cpu-baseline", "--train-timeout", "1200"], capture_output=True, text=True, timeout=1400, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
@@ -117,7 +144,7 @@ def test_the_training_record_rides_in_the_same_line_at_one_and_two_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     for extra in ([], ["--gpus", "2", "--backend", "gloo"]):
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + base + extra +
-                             ["--train-small", "--train-iters", "160", "--no-cpu-baseline"], capture_output=True,
+                             ["--full", "--train-small", "--train-iters", "160", "--no-cpu-baseline"], capture_output=True,
                              text=True, timeout=900, env=env, cwd=ROOT)
         assert out.returncode == 0, out.stderr[-3000:]
         lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]

@@ -166,7 +166,7 @@ def test_bench_with_one_gpu_on_the_rccl_backend_and_the_exchange_forced():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--backend", "nccl",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--backend", "nccl",
                           "--force-exchange", "--gaussians", "200000", "--steps", "5", "--warmup", "3",
                           "--no-cpu-baseline", "--no-pmc", "--train-iters", "0", "--no-synced-regions"],
                          capture_output=True, text=True, timeout=800, env=env, cwd=ROOT)

@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 cd "$ROOT"
 run() {  # name, flags...
   local name=$1; shift
-  timeout 600 python bench.py "$@" > "$OUT/bench_${TAG}_${name}.json" 2> "$OUT/bench_${TAG}_${name}.err"
+  timeout 600 python bench.py --full "$@" > "$OUT/bench_${TAG}_${name}.json" 2> "$OUT/bench_${TAG}_${name}.err"
   python - "$OUT/bench_${TAG}_${name}.json" "$name" <<'PY'
 import json, sys
 try:

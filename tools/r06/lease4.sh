@@ -23,7 +23,7 @@ for l in open("$out/runs.jsonl"):
     print(r["tag"], r["iters_per_s"], "render p50", r.get("render",{}).get("p50"), "bwd", r.get("backward",{}).get("p50"), "round trip us before", rt[0], "after", rt[1], "cpu", r.get("cpu_start_end"))
 PY
 timeout 1500 python tools/r06/regret.py $out/regret.txt > $out/regret_stdout.txt 2>&1; tail -20 $out/regret.txt
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_form.json 2> $out/bench_driver_form.err; python - <<PY
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_form.json 2> $out/bench_driver_form.err; python - <<PY
 import json
 d=json.loads([l for l in open("$out/bench_driver_form.json") if l.startswith("{")][-1])
 print("value", d["value"], "ms", d["ms_per_step"], "roofline", {k:v for k,v in d["roofline"].items() if not isinstance(v,(dict,list))})

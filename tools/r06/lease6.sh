@@ -27,13 +27,13 @@ for t,rs in by.items():
     print("%-16s it/s %-44s render p50 %s" % (t, " ".join("%.0f"%r["iters_per_s"] for r in rs), " ".join("%.3f"%r["render"]["p50"] for r in rs)))
 PY
 for v in 1 0; do
-  GSR_TUNE="{\"speculate_thread\": $v}" python bench.py --steps 100 --warmup 20 --train-iters 0 --no-cpu-baseline --no-pmc 2>/dev/null | python -c "
+  GSR_TUNE="{\"speculate_thread\": $v}" python bench.py --full --steps 100 --warmup 20 --train-iters 0 --no-cpu-baseline --no-pmc 2>/dev/null | python -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 print('bench default 1M 1080p, speculate_thread=$v: ms', d['ms_per_step'], 'with caller syncs', d['ms_per_step_with_caller_syncs'], 'with camera syncs too', d['ms_per_step_with_caller_and_camera_syncs'])" | tee -a $out/thread_ab.txt
 done
 bash tools/collect_profiles.sh r06 > $out/collect_profiles.log 2>&1; tail -2 $out/collect_profiles.log
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_form.json 2> $out/bench_driver_form.err; python - <<PY
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_form.json 2> $out/bench_driver_form.err; python - <<PY
 import json
 d=json.loads([l for l in open("$out/bench_driver_form.json") if l.startswith("{")][-1])
 print("value", d["value"], "ms", d["ms_per_step"], "roofline", {k:v for k,v in d["roofline"].items() if not isinstance(v,(dict,list,str))})

@@ -3,7 +3,7 @@
 # and the trained model's parity figures in a driver-form line.
 out=$PWD/gpurun_out/lease9; mkdir -p $out
 timeout 900 python -m pytest tests/test_gpu_heldout.py tests/test_gpu_bench.py -q --durations=6 2>&1 | tail -25 > $out/tests.txt; tail -6 $out/tests.txt
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cogs > $out/bench.json 2> $out/bench.err; python - <<PY
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cogs > $out/bench.json 2> $out/bench.err; python - <<PY
 import json
 d=json.loads([l for l in open("$out/bench.json") if l.startswith("{")][-1])
 print("value", d["value"], "ms", d["ms_per_step"])
