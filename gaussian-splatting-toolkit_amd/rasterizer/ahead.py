@@ -68,6 +68,14 @@ def _speculation_mode() -> str:
     return _spec_knobs["mode"]
 
 
+@_C._tuning.on_change
+def _refresh_spec_floor():
+    # `speculate_min` is a row of the table: `set_overrides` must reach it.  (The mode comes from the environment and
+    # may have been set in place by a caller: it stays.)
+    if _spec_knobs:
+        _spec_knobs["min_points"] = int(_C._tuning.get("speculate_min"))
+
+
 def _note_opacity_recipe(device, opacity) -> None:
     """Remember how the caller formed `opacity` -- for the NEXT view's lists (see above)."""
     fn = opacity.grad_fn

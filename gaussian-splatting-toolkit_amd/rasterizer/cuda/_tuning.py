@@ -11,7 +11,8 @@ A/B scripts and tests override rows without touching the code:
     GSR_TUNE='{"deep_factor": 1.5, "depth_segments_fwd": 8}' python bench.py ...      # one JSON object, read once
     rasterizer.cuda._tuning.set_overrides({"deep_factor": 1.5})                       # in-process (clears the caches)
 
-An unknown key raises: a typo must not run the default silently.
+An unknown key raises: a typo must not run the default silently.  So does a retired variable (``GSR_`` + a row's name in
+capitals, e.g. ``GSR_NO_SPECULATION``) still set in the environment: it has been ignored since round 5.
 
 Each row: ``name: (default, "what it decides; where it was measured")``.  The rows are FITTED constants: the scenes they
 were fitted on are named in the record; ``profiles/r06_regret_*.txt`` holds the default rule against a grid search on
@@ -54,7 +55,7 @@ TABLE = {
     "depth_segments_fwd": (16, "cap on the FORWARD's runs (0 = none).  8 until the end of r05 while the forward walked "
                                "every list twice; one walk since r06 (profiles/r06_forward_one_walk.txt)"),
     # ---- two-round lists for deep scenes
-    "two_round": ("auto", "auto | 0 | force: lists of the nearest Gaussians first, the rest only for unfinished tiles "
+    "two_round": ("auto", "auto | 0 | 1 (force): lists of the nearest Gaussians first, the rest only for unfinished tiles "
                           "(config 5: 3.26 -> 2.77 ms; profiles/r03_*)"),
     "two_round_depth": (1500.0, "candidate scenes: at least this many list entries per tile ..."),
     "two_round_len": (500.0, "... round 1 aims at this many entries per tile ..."),
@@ -72,9 +73,20 @@ _over = None
 _listeners = []
 
 
+def _retired_variables():
+    """The rows are named after the environment variables they replaced; one still set would be silently ignored."""
+    for key in TABLE:
+        var = "GSR_" + key.upper()
+        if var in os.environ:
+            raise ValueError(f"{var} is no longer read: the tuning table replaced it; use "
+                             f"GSR_TUNE='{{\"{key}\": {json.dumps(os.environ[var])}}}' "
+                             f"(or rasterizer.cuda._tuning.set_overrides) instead")
+
+
 def _load():
     global _over
     if _over is None:
+        _retired_variables()
         raw = os.environ.get("GSR_TUNE", "").strip()
         over = json.loads(raw) if raw else {}
         if not isinstance(over, dict):
@@ -99,6 +111,7 @@ def set_overrides(over=None):
     """Replace the overrides (None / {}: the table's defaults plus nothing -- GSR_TUNE is NOT re-read) and drop every
     cache derived from the table."""
     global _over
+    _retired_variables()  # (also when no look-up ran before)
     over = dict(over or {})
     _check(over)
     _over = over

@@ -43,9 +43,11 @@ _tls = threading.local()
 #   list_builds_ahead                   lists built ahead of time on the side stream (`speculate_lists`)
 #   ahead_hits / ahead_misses           ... and whether the rasterize call that followed could use them
 #   ahead_orders_used                   only the depth order of the side stream was used
+#   list_builds_two_round               lists built in two rounds (`_build_two_round`, deep scenes)
 #   ahead_recipes_off                   devices on which the recipe detection switched itself off (rasterizer/ahead.py)
 counters = {"list_rebuilds": 0, "list_builds_exact": 0, "list_builds_device_sized": 0, "list_builds_ahead": 0,
-            "ahead_hits": 0, "ahead_misses": 0, "ahead_orders_used": 0, "ahead_recipes_off": 0}
+            "ahead_hits": 0, "ahead_misses": 0, "ahead_orders_used": 0, "ahead_recipes_off": 0,
+            "list_builds_two_round": 0}
 
 
 def _cache_snapshot():
@@ -272,6 +274,7 @@ def _build_two_round(xys, depths, radii, conics, num_tiles_hit, opacity, tile_bo
         flags = torch.zeros((tile_bounds[0] * tile_bounds[1],), dtype=torch.int32, device=dev)
     p1, p2, p4 = (_PendingCount(dev) for _ in range(3))
     counters["list_builds_device_sized"] += 1
+    counters["list_builds_two_round"] += 1
     bins1 = _C.tile_lists_subrange(order[:n1], cap1, records, tile_bounds, ids[:cap1], p1.buf)
     round1(ids, bins1, flags)
     with torch.cuda.device(dev):

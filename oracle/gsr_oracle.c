@@ -782,6 +782,103 @@ GSR_API void gsr_oracle_rasterize_backward(
   free(absacc);
 }
 
+/* The same backward in double precision ON THE fp32 DECISIONS: which (pixel, Gaussian) pairs contribute -- sigma < 0,
+ * alpha < 1/255 evaluated in fp32 exactly as above, and the forward's final_Ts / final_idx -- is the fp32 oracle's;
+ * every value (sigma, exp, alpha, the transmittance walked back from final_Ts, the running colour, each per-pixel term
+ * and the per-Gaussian sums) is computed in double.  A high-precision reference for the compositing backward: where
+ * the fp32 terms cancel (thin splats whose v_conic sums terms of both signs over hundreds of pixels) it tells the
+ * rounding of an fp32 implementation from an error in it.  Outputs are double, [N,2] [N,3] [N,C] [N]. */
+GSR_API void gsr_oracle_rasterize_backward_fp64(
+    int img_h, int img_w, int bw, int channels, int num_points,
+    const int *gaussian_ids_sorted, const int *tile_bins, const float *xys,
+    const float *conics, const float *colors, const float *opacities,
+    const float *background, const float *final_Ts, const int *final_idx,
+    const float *v_output, const float *v_output_alpha, double *v_xy,
+    double *v_conic, double *v_colors, double *v_opacity) {
+  const int tiles_x = (img_w + bw - 1) / bw;
+  const int stride = 6 + channels;
+  int nthreads = 1;
+#ifdef _OPENMP
+  nthreads = omp_get_max_threads();
+#endif
+  while (nthreads > 1 && (double)nthreads * num_points * stride * 8.0 > 6e9) nthreads /= 2;
+  double *accs = (double *)calloc((size_t)nthreads * num_points * stride, sizeof(double));
+
+#pragma omp parallel num_threads(nthreads)
+  {
+    int tid = 0;
+#ifdef _OPENMP
+    tid = omp_get_thread_num();
+#endif
+    double *A = accs + (size_t)tid * num_points * stride;
+    double *buf = (double *)malloc(sizeof(double) * (size_t)channels);
+#pragma omp for schedule(dynamic, 4)
+    for (int i = 0; i < img_h; ++i) {
+      for (int j = 0; j < img_w; ++j) {
+        int tile = (i / bw) * tiles_x + (j / bw);
+        int lo = tile_bins[2 * tile];
+        size_t pid = (size_t)i * img_w + j;
+        const double T_final = final_Ts[pid];
+        double T = T_final;
+        int bin_final = final_idx[pid];
+        const float *vout = v_output + pid * channels;
+        const double vout_alpha = v_output_alpha[pid];
+        for (int c = 0; c < channels; ++c) buf[c] = 0.0;
+        int hi = tile_bins[2 * tile + 1];
+        int start = bin_final < hi - 1 ? bin_final : hi - 1;
+        for (int idx = start; idx >= lo; --idx) {
+          int g = gaussian_ids_sorted[idx];
+          /* the decision, in fp32 as the backward above takes it */
+          float dxf = xys[2 * g] - (float)j, dyf = xys[2 * g + 1] - (float)i;
+          float af = conics[3 * g], bf = conics[3 * g + 1], cf = conics[3 * g + 2];
+          float sigmaf = 0.5f * (af * dxf * dxf + cf * dyf * dyf) + bf * dxf * dyf;
+          float alphaf = fminf_(0.99f, opacities[g] * expf(-sigmaf));
+          if (sigmaf < 0.f || alphaf < 1.f / 255.f) continue;
+          /* the values, in double */
+          const double dx = (double)xys[2 * g] - j, dy = (double)xys[2 * g + 1] - i;
+          const double a = af, b = bf, cc = cf, opac = opacities[g];
+          const double sigma = 0.5 * (a * dx * dx + cc * dy * dy) + b * dx * dy;
+          const double vis = exp(-sigma);
+          const double alpha = opac * vis < 0.99 ? opac * vis : 0.99;
+          const double ra = 1.0 / (1.0 - alpha);
+          T *= ra;
+          const double fac = alpha * T;
+          double v_alpha = 0.0;
+          double *Ag = A + (size_t)g * stride;
+          const float *rgb = colors + (size_t)channels * g;
+          for (int c = 0; c < channels; ++c) {
+            Ag[6 + c] += fac * vout[c];
+            v_alpha += (rgb[c] * T - buf[c] * ra) * vout[c];
+          }
+          v_alpha += T_final * ra * vout_alpha;
+          for (int c = 0; c < channels; ++c) v_alpha += -T_final * ra * background[c] * vout[c];
+          for (int c = 0; c < channels; ++c) buf[c] += rgb[c] * fac;
+          const double v_sigma = -opac * vis * v_alpha;
+          Ag[2] += 0.5 * v_sigma * dx * dx;
+          Ag[3] += v_sigma * dx * dy;
+          Ag[4] += 0.5 * v_sigma * dy * dy;
+          Ag[0] += v_sigma * (a * dx + b * dy);
+          Ag[1] += v_sigma * (b * dx + cc * dy);
+          Ag[5] += vis * v_alpha;
+        }
+      }
+    }
+    free(buf);
+  }
+#pragma omp parallel for schedule(static)
+  for (int g = 0; g < num_points; ++g) {
+    for (int k = 0; k < stride; ++k) {
+      double sk = 0.0;
+      for (int t = 0; t < nthreads; ++t) sk += accs[((size_t)t * num_points + g) * stride + k];
+      if (k < 2) v_xy[2 * g + k] = sk;
+      else if (k < 5) v_conic[3 * g + (k - 2)] = sk;
+      else if (k == 5) v_opacity[g] = sk;
+      else v_colors[(size_t)channels * g + (k - 6)] = sk;
+    }
+  }
+  free(accs);
+}
+
 /* bindings.cu:19-56 : standalone conic + radius from cov2d */
 GSR_API void gsr_oracle_cov2d_bounds(int n, const float *cov2d, float *conics,
                                      float *radii) {

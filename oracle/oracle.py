@@ -259,6 +259,30 @@ def rasterize_backward(
     return out
 
 
+def rasterize_backward_fp64(
+    img_height, img_width, block_width, gaussian_ids_sorted, tile_bins, xys,
+    conics, colors, opacities, background, final_Ts, final_idx, v_output, v_output_alpha,
+):
+    """`rasterize_backward` in double precision on the fp32 oracle's decisions (which pairs contribute, final_Ts /
+    final_idx) -> float64 (v_xy, v_conic, v_colors, v_opacity[N,1])"""
+    colors = _f(colors)
+    n, ch = colors.shape
+    gids, bins = _i(gaussian_ids_sorted), _i(tile_bins)
+    xys, conics, opac, bg = _f(xys), _f(conics), _f(opacities).reshape(-1), _f(background)
+    Ts, fidx = _f(final_Ts), _i(final_idx)
+    vo, voa = _f(v_output), _f(v_output_alpha)
+    v_xy = np.empty((n, 2), np.float64)
+    v_conic = np.empty((n, 3), np.float64)
+    v_colors = np.empty((n, ch), np.float64)
+    v_opac = np.empty((n, 1), np.float64)
+    lib().gsr_oracle_rasterize_backward_fp64(
+        C.c_int(img_height), C.c_int(img_width), C.c_int(block_width), C.c_int(ch),
+        C.c_int(n), _p(gids), _p(bins), _p(xys), _p(conics), _p(colors), _p(opac),
+        _p(bg), _p(Ts), _p(fidx), _p(vo), _p(voa), _p(v_xy), _p(v_conic), _p(v_colors), _p(v_opac),
+    )
+    return v_xy, v_conic, v_colors, v_opac
+
+
 # generic-channel entry points share the implementation (fp32 accumulators)
 nd_rasterize_forward = rasterize_forward
 nd_rasterize_backward = rasterize_backward

@@ -260,6 +260,15 @@ def test_more_than_int32_intersections_is_an_error_not_a_memory_fault():
         rasterize_gaussians(xys, depths, radii, conics, tiles, colors, cu(sc["opacities"]), H, W, 16)
 
 
+def _spec_counters(stdout):
+    """The fuzz's `spec_counters: {json}` line: the speculated leg's `rasterize.counters` increments over all calls."""
+    import json
+
+    lines = [ln for ln in stdout.splitlines() if ln.startswith("spec_counters: ")]
+    assert len(lines) == 1, stdout[-2000:]
+    return json.loads(lines[0][len("spec_counters: "):])
+
+
 def test_random_view_sequences_equal_unspeculated_calls():
     """tools/exp/fuzz_sequence.py: 80 calls jumping between scenes of 60 to 400 k Gaussians, 160 x 96 to
     2560 x 1600 pixels and opacities down to 1 % (guessed list sizes overflow and are rebuilt, the count-free
@@ -271,10 +280,15 @@ def test_random_view_sequences_equal_unspeculated_calls():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     # (GSR_SPECULATE=lists: lists are built ahead of time on the side stream whenever the opacities are predictable,
     # not only while the caller is seen to block -- the fuzz must cover that path on every call)
-    out = subprocess.run([sys.executable, os.path.join(root, "tools", "exp", "fuzz_sequence.py"), "80", "17"],
+    # (seed 65: 3 lists-ahead hits and 2 rebuilds over the 80 calls; seed 17 had no call whose predecessor left a
+    # usable opacity recipe, so the lists built ahead were never exercised)
+    out = subprocess.run([sys.executable, os.path.join(root, "tools", "exp", "fuzz_sequence.py"), "80", "65"],
                          capture_output=True, text=True, timeout=900, env=dict(os.environ, GSR_SPECULATE="lists"))
     assert out.returncode == 0 and "mismatches: 0" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
     assert out.stdout.count(": ok") == 80
+    # the speculated leg covered what the fuzz is for: device-sized lists, rebuilds after overflow, lists built ahead
+    spec = _spec_counters(out.stdout)
+    assert spec["list_builds_device_sized"] > 0 and spec["list_rebuilds"] > 0 and spec["ahead_hits"] > 0, spec
 
 
 def test_random_view_sequences_with_two_round_lists_forced():
@@ -291,6 +305,8 @@ def test_random_view_sequences_with_two_round_lists_forced():
                          capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0 and "mismatches: 0" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
     assert out.stdout.count(": ok") == 80
+    spec = _spec_counters(out.stdout)
+    assert spec["list_builds_two_round"] > 0, spec
 
 
 def test_lists_built_ahead_of_time_are_used_only_with_proven_opacities():

@@ -33,15 +33,18 @@ def test_held_out_families_against_the_oracle(family, W, H, n):
     # (no floor on the share of decision-stable Gaussians: it is a property of the scene -- needles touch hundreds of
     #  pixels each -- and is printed; the bars are the oracle's on whatever is stable, and the global ones)
     # The bars every scene is held to: image / alpha 1e-4 on stable pixels, every gradient tensor max |err| <= 1e-3 max |ref|
-    # and L2-relative <= 1e-4, projection bit-identical.  The two ELEMENTWISE extras of config 2 are scene-dependent and
-    # were measured on the first GPU run of these families (profiles/r06_gpu_suite.txt): `floaters` -- near-camera splats
-    # whose footprint is 1e5 pixels, summed in fp32 atomics against the oracle's doubles -- has decision-stable Gaussians
-    # at 2.1e-3 elementwise in the projection's scale gradient (bar here 5e-3); `needles` has 1.8e-4 / 4.9e-4 of the xys
-    # elements of decision-UNSTABLE Gaussians outside the tight bound (bar here 1e-3).  For needles nearly every Gaussian is
-    # decision-unstable (3.5 % of the PIXELS have a threshold within 1e-5: a needle's long edge grazes hundreds of pixel
-    # centres at alpha ~ 1/255; 0.3 % of the visible Gaussians are stable) and the footprint model behind the per-element
-    # cap -- the share of a splat's weight its peak pixel carries, from det(conic) -- does not describe a 1:40 footprint:
-    # the cap is printed, not asserted, there.
+    # and L2-relative <= 1e-4, projection bit-identical.  The per-family values below fail config 2's defaults end to end
+    # (measured on the MI355X): floaters 480x270 -- a decision-stable scale element at 2.08e-3 (floaters 960x540 passes);
+    # needles -- 14 / 78 xys and 8 / 40 opacity elements beyond the tight bound (480x270 / 960x540) and scale / quaternion
+    # L2 1.1e-4 / 2.1e-4 and 1.0e-4 / 4.2e-4 (global_max 2e-3 and the unasserted per-element cap are kept unmeasured at
+    # the defaults).  Stage by stage (test_held_out_families_stage_by_stage) none of it is a kernel's: the projection
+    # backward is bit-identical to the oracle for the same cotangents (stage b) and exactly as far from float64 as the
+    # oracle (stage c ratio 1.0; the oracle itself is 0.21 per row off float64 in v_quat on needles at 960x540 -- a 1:40
+    # covariance's rotation is ill-conditioned in fp32); atomic and fixed-order compositing differ by <= 1.3e-6 of
+    # max |ref|; and the compositing gap to the oracle (needles v_conic 1.9e-4 L2, atomic and det alike) is decision
+    # flips at alpha = 1/255 -- with the 1.8 % / 3.5 % ambiguous pixels' cotangents zeroed both kernels pass config 2's
+    # bars, 3.4e-5 L2 from the float64 sums where the oracle is 4.0e-5.  End to end, those flips move the transmittance
+    # of every splat in front of them, and on needles they touch 98 % of the splats.
     scene_vs_oracle(sc, cam, 3, -1.0, f"heldout_{family}_{W}x{H}.json", 60.0, min_stable_pixels=0.95, within_floor=0.99,
                     stable_rel=5e-3 if family == "floaters" else 1e-3,
                     unstable_fraction=1e-3 if family == "needles" else 1e-4, worst_check=family != "needles",
@@ -51,11 +54,10 @@ def test_held_out_families_against_the_oracle(family, W, H, n):
                     global_max=2e-3 if family == "needles" else 1e-3, global_l2=1e-3 if family == "needles" else 1e-4)
 
 
-@pytest.mark.timeout(900)
-def test_a_trained_model_against_the_oracle_with_the_job_order_active(tmp_path):
-    """bench.py's `train.trained_raster.parity_vs_oracle` in small: a model trained here (coarse-to-fine schedule,
-    refinement firing), exported through gs_io.ply, read back and rendered at 1920x1080 from one of its training
-    views -- longest-job-first order, tail splitting and the measured split ratio are what the compositing runs with."""
+@pytest.fixture(scope="module")
+def trained_model(tmp_path_factory):
+    """A model trained here (coarse-to-fine schedule, refinement firing), exported through gs_io.ply and read back,
+    with the 1920x1080 camera of one of its training views -- trained ONCE for the module's tests."""
     import bench
     from gs_fused import RefineConfig
     from gs_io.ply import read_gaussian_ply
@@ -66,17 +68,177 @@ def test_a_trained_model_against_the_oracle_with_the_job_order_active(tmp_path):
     cfg.scene_objects, cfg.scene_scale, cfg.sh_degree_interval, cfg.phase_every = (12, 0.3, 0.6), (0.01, 0.03), 80, 0
     cfg.refine = RefineConfig(warmup_length=60, refine_every=40, reset_alpha_every=6, stop_screen_size_at=300)
     cfg.resolution_schedule, cfg.eval_views, cfg.log_every = 100, 1, 0
-    ply = os.path.join(tmp_path, "trained.ply")
+    ply = os.path.join(tmp_path_factory.mktemp("trained"), "trained.ply")
     cfg.export_ply = ply
     res = train(cfg, torch.device("cuda", 0), 0, 1)
-    assert res["refinements"], "the refinement never fired: not the distribution this test is about"
     raw = read_gaussian_ply(ply)
-    n = raw["means"].shape[0]
     q = raw["quats"] / np.linalg.norm(raw["quats"], axis=-1, keepdims=True)
     sc = {"means3d": raw["means"], "scales": np.exp(raw["scales"]).astype(np.float32), "quats": q.astype(np.float32),
           "opacities": (1.0 / (1.0 + np.exp(-raw["opacities"].astype(np.float64)))).astype(np.float32),
           "sh_coeffs": np.ascontiguousarray(np.concatenate([raw["features_dc"][:, None, :], raw["features_rest"]], 1))}
     cam = orbit_cameras(cfg.num_views, 1920, 1080, radius=cfg.cam_radius)[0]
-    print("trained model:", n, "Gaussians after", len(res["refinements"]), "refinements")
+    return sc, cam, res["refinements"]
+
+
+@pytest.mark.timeout(900)
+def test_a_trained_model_against_the_oracle_with_the_job_order_active(trained_model):
+    """bench.py's `train.trained_raster.parity_vs_oracle` in small: a model trained here (coarse-to-fine schedule,
+    refinement firing), exported through gs_io.ply, read back and rendered at 1920x1080 from one of its training
+    views -- longest-job-first order, tail splitting and the measured split ratio are what the compositing runs with."""
+    sc, cam, refinements = trained_model
+    assert refinements, "the refinement never fired: not the distribution this test is about"
+    n = sc["means3d"].shape[0]
+    print("trained model:", n, "Gaussians after", len(refinements), "refinements")
+    # (stable_rel 2e-3 / unstable_fraction 3e-4 kept: the model differs from run to run and one run's pass at the defaults
+    #  is not a measurement.  Stage by stage, the oracle's own decision-stable v_opacity element is 1.3e-3 - 1.5e-3 from
+    #  the float64 sums -- fp32 per-pixel terms that cancel -- and the kernels 0.6e-3 - 0.8e-3)
     scene_vs_oracle(sc, cam, 3, -1.0, "trained_small_1080p.json", 60.0, min_stable_pixels=0.95, within_floor=0.99,
                     stable_rel=2e-3, unstable_fraction=3e-4)
+
+
+# ---- the same scenes stage by stage (each stage fed the SAME inputs as the oracle's, config 2's bars, no per-family
+# constant): (a) the compositing backward, atomic and fixed-order, (b) the projection backward against the oracle,
+# (c) both against a float64 restatement of the projection (tests/test_project_fp64.py) -- a kernel worse than an fp32
+# restatement of the reference fails (c) whatever the covariances' condition.
+def _stages(sc, cam, label):
+    import rasterizer.cuda as C
+    from test_gpu_fullsize import cu, grad_close, npy, peak_pixel_share, stable_gaussians
+    from test_project_fp64 import oracle_project_vjp, project_vjp_fp64, row_err, row_max
+
+    from oracle import oracle as O
+
+    W, H, n = cam.width, cam.height, sc["means3d"].shape[0]
+    tb = ((W + 15) // 16, (H + 15) // 16, 1)
+    tiles = tb[0] * tb[1]
+    g = {k: cu(sc[k]) for k in ("means3d", "scales", "quats")}
+    vm, pm = cu(cam.viewmat[:3]), cu(cam.projmat)
+    proj = C.project_gaussians_forward(n, g["means3d"], g["scales"], 1.0, g["quats"], vm, pm, cam.fx, cam.fy, cam.cx,
+                                       cam.cy, H, W, 16, 0.01)
+    cov3d, xys, depths, radii, conics, comp, nth = proj
+    ref = O.project_gaussians_forward(n, sc["means3d"], sc["scales"], 1.0, sc["quats"], cam.viewmat[:3], cam.projmat,
+                                      cam.fx, cam.fy, cam.cx, cam.cy, H, W, 16, 0.01)
+    for mine, r, nm in zip(proj[1:], ref[1:], ("xys", "depths", "radii", "conics", "compensation", "num_tiles_hit")):
+        assert np.array_equal(npy(mine), r), f"{label}: projection {nm} not bit-identical"
+    gx, gd, gr, gc, gt = ref[1], ref[2], ref[3], ref[4], ref[6]
+
+    # ---- (a) compositing backward: the oracle's lists (equal to the GPU's), the oracle's final_Ts / final_idx
+    I, cum = O.compute_cumulative_intersects(gt)
+    _, _, _, vs, bins = O.bin_and_sort_gaussians(n, I, gx, gd, gr, cum, tb, 16)
+    order, cum_sorted = C.depth_order(depths, radii, nth)
+    ids, tile_bins = C.bin_sorted(n, I, order, cum_sorted, xys, radii, tb, 16)
+    assert np.array_equal(npy(ids), vs) and np.array_equal(npy(tile_bins), bins), f"{label}: lists differ"
+    if tiles > 1100:  # the product's dispatch at this grid: longest job first (+ the measured split threshold)
+        arg = C.deep_arg(tile_bins, I, tiles, backward=True, tile_bounds=tb)
+        assert arg & C.GSR_DEEP_ORDERED and C.depth_segments(I, tiles)[0] == 1
+    else:             # ... depth segments
+        assert C.depth_segments(I, tiles)[0] > 1
+    dirs = S.viewdirs_for(sc, cam)
+    rgbs = np.maximum(O.compute_sh_forward(n, 3, 3, dirs, sc["sh_coeffs"]) + 0.5, 0).astype(np.float32)
+    opac = sc["opacities"].reshape(n, 1).astype(np.float32)
+    bg = np.array(S.BACKGROUND, np.float32)
+    v_img, v_alpha = S.make_cotangents(cam)
+    _, Ts, fidx, amb = O.rasterize_forward(tb, (16, 16, 1), (W, H, 1), vs, bins, gx, gc, rgbs, opac, bg, ambig_eps=1e-5)
+    # Decision-ambiguous pixels get zero cotangents (a pixel with zero cotangents adds nothing to any gradient).  Such a
+    # pixel holds a (pixel, splat) pair whose alpha is within 1e-5 of 1/255 (or sigma of 0, T of the 1e-4 stop): a
+    # kernel's exp may legitimately decide it the other way, and the flip moves the transmittance -- so the gradient --
+    # of every splat in front of it in that pixel.  On needles 3.5 % of the pixels are such, and they touch 98 % of the
+    # splats.  Sigma is bit-identical to the oracle's (same expression and order), so on the other pixels every
+    # decision is the oracle's, and what remains between the kernel and the oracle is arithmetic.
+    keep = ~amb
+    v_img, v_alpha = v_img * keep[..., None], v_alpha * keep
+    vxy, vconic, vcol, vop, axy, aconic, acol, aop, amb_g = O.rasterize_backward(
+        H, W, 16, vs, bins, gx, gc, rgbs, opac, bg, Ts, fidx, v_img, v_alpha, with_abs_sums=True, ambig_eps=1e-5)
+    stable = stable_gaussians(amb, amb_g, gx, gr, W, H)
+    share = peak_pixel_share(gc)
+    ins = (xys, conics, cu(rgbs), cu(opac), cu(bg), cu(Ts), cu(fidx), cu(v_img), cu(v_alpha))
+    atomic = C.rasterize_backward(H, W, 16, ids, tile_bins, *ins)
+    # fixed order: the per-(tile, entry) partials summed per Gaussian in list order (host-built inverse map)
+    counts = np.bincount(vs, minlength=n)
+    det = C.rasterize_backward_det(H, W, ids, tile_bins, *ins, cu(np.arange(n, dtype=np.int32)),
+                                   cu(np.cumsum(counts).astype(np.int32)), cu(np.argsort(vs, kind="stable").astype(np.int32)))
+    torch.cuda.synchronize()
+    # float64 on the same decisions (oracle/gsr_oracle.c): how far each fp32 implementation is from the exact sums
+    f64 = O.rasterize_backward_fp64(H, W, 16, vs, bins, gx, gc, rgbs, opac, bg, Ts, fidx, v_img, v_alpha)
+    print(f"{label}: {n} Gaussians, {int((gr > 0).sum())} visible, {I} list entries, {tiles} tiles, "
+          f"{float(amb.mean()):.4f} of the pixels ambiguous (cotangents zeroed), "
+          f"decision-stable {float(stable[gr > 0].mean()):.4f} of the visible")
+    failed = []  # (every stage runs and prints before anything is asserted: the decomposition is the point)
+
+    def check(fn, *args, **kw):
+        try:
+            fn(*args, **kw)
+        except AssertionError as e:
+            failed.append(str(e).splitlines()[0])
+            print("FAILED:", failed[-1])
+
+    for k, (nm, r, a) in enumerate(zip(("v_xy", "v_conic", "v_colors", "v_opacity"), (vxy, vconic, vcol, vop),
+                                       (axy, aconic, acol, aop))):
+        at, de = npy(atomic[k]).reshape(r.shape), npy(det[k]).reshape(r.shape)
+        order_share = np.abs(at - de).max() / max(np.abs(r).max(), 1e-30)
+        order_l2 = np.linalg.norm(at - de) / max(np.linalg.norm(r), 1e-30)
+        l2 = lambda x: np.linalg.norm(x - f64[k]) / max(np.linalg.norm(f64[k]), 1e-300)  # noqa: E731
+        print(f"{label} (a) {nm}: atomic - det max |diff| / max |ref| = {order_share:.3e}, L2 {order_l2:.3e} "
+              f"(summation order); L2 from fp64: oracle {l2(r):.3e}, atomic {l2(at):.3e}, det {l2(de):.3e}")
+        # Config 2's bars against the oracle.  Its 1e-3 elementwise bar on decision-stable Gaussians, however, is what an
+        # fp32 evaluation of the per-pixel terms costs by itself where they cancel: the oracle (fp32 terms, double sums)
+        # is 1.2e-3 from the float64 sums on a stable v_xy element of `room` and 1.3e-3 on the trained model's v_opacity.
+        # So a stable element is held to 1e-3 of the float64 value OR twice the oracle's own distance from it, whichever
+        # is larger: no constant per scene, and a kernel worse than an fp32 restatement of the reference fails.
+        ref64 = f64[k].reshape(r.shape)
+        floor = np.maximum(np.abs(ref64[stable]), 1e-4 * np.abs(ref64).max())
+        own = np.abs(r - ref64)[stable]
+        for tag, x in (("atomic", at), ("det", de)):
+            e = np.abs(x - ref64)[stable]
+            worst = float((e / (1e-3 * floor + 2 * own)).max()) if e.size else 0.0
+            print(f"{label} (a) {tag} {nm}: stable elements from fp64 {float((e / floor).max()) if e.size else 0.0:.3e} "
+                  f"(oracle {float((own / floor).max()) if e.size else 0.0:.3e}), {worst:.3f} of the bar")
+            if worst > 1.0:
+                failed.append(f"{label} (a) {tag} {nm}: a decision-stable element is {worst:.2f}x the bar")
+            check(grad_close, x, r, a, name=f"{label} (a) {tag} {nm}", peak_share=share)
+
+    # ---- (b) projection backward, the same cotangents: (a)'s atomic v_xy / v_conic, then a compensation cotangent
+    rng = np.random.default_rng(0)
+    z = np.zeros(n, np.float32)
+    cots = {"v_xy/v_conic": (npy(atomic[0]), z, npy(atomic[1]), z),
+            "v_compensation": (np.zeros((n, 2), np.float32), z, np.zeros((n, 3), np.float32),
+                               rng.standard_normal(n).astype(np.float32))}
+    for what, cot in cots.items():
+        hip = C.project_gaussians_backward(n, g["means3d"], g["scales"], 1.0, g["quats"], vm, pm, cam.fx, cam.fy, cam.cx,
+                                           cam.cy, H, W, cov3d, radii, conics, comp, *(cu(c) for c in cot))[2:]
+        hip = [npy(t) for t in hip]
+        orc = oracle_project_vjp(sc, cam, npy(cov3d), gr, gc, npy(comp), *cot)
+        for o, r, nm in zip(hip, orc, ("v_mean3d", "v_scale", "v_quat")):
+            rowmax = np.abs(r).max(axis=-1, keepdims=True)
+            e = np.abs(o - r) / np.maximum(rowmax, 1e-6 * np.abs(r).max())
+            print(f"{label} (b) {what} {nm}: HIP vs oracle per row {e.max():.3e}")
+            if not e.max() < 1e-3:
+                failed.append(f"{label} (b) {what} {nm}: {e.max():.3e}")
+        # ---- (c) the float64 restatement: per row, HIP no further from it than twice the oracle (+ 1e-6 of the row)
+        f64 = project_vjp_fp64(sc["means3d"], sc["scales"], 1.0, sc["quats"], cam.viewmat[:3], cam.projmat, cam.fx,
+                               cam.fy, cam.cx, cam.cy, H, W, npy(comp), *cot)
+        rows = (gr > 0) & f64[3]
+        for h, o, f, nm in zip(hip, orc, f64[:3], ("v_mean3d", "v_scale", "v_quat")):
+            eh, eo, fm = row_err(h[rows], f[rows]), row_err(o[rows], f[rows]), row_max(f[rows])
+            fm_ = np.maximum(fm, 1e-30)
+            print(f"{label} (c) {what} {nm}: vs fp64 per row, HIP max {float((eh / fm_).max()):.3e}, oracle max "
+                  f"{float((eo / fm_).max()):.3e}; {int(rows.sum())} rows, {int(((gr > 0) & ~f64[3]).sum())} visible "
+                  f"outside the guard band left out")
+            over = eh > 2 * eo + 1e-6 * fm
+            if over.any():
+                failed.append(f"{label} (c) {what} {nm}: {int(over.sum())} rows further from fp64 than the oracle "
+                              f"allows, worst {float(((eh - 2 * eo) / fm_).max()):.3e} of the row")
+    assert not failed, "\n".join(failed)
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize("W,H,n", [(480, 270, 40_000), (960, 540, 80_000)])
+@pytest.mark.parametrize("family", S.HELDOUT_KINDS)
+def test_held_out_families_stage_by_stage(family, W, H, n):
+    cam = S.make_camera(W, H)
+    _stages(S.make_heldout_scene(family, n, cam, sh_degree=3), cam, f"{family} {W}x{H}")
+
+
+@pytest.mark.timeout(600)
+def test_a_trained_model_stage_by_stage(trained_model):
+    sc, cam, _ = trained_model
+    _stages(sc, cam, "trained 1920x1080")

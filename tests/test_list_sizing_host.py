@@ -211,3 +211,46 @@ def test_the_tuning_table_rejects_unknown_rows_and_reads_gsr_tune_once(monkeypat
         T.set_overrides(saved)
     for name, (default, record) in T.TABLE.items():
         assert isinstance(record, str) and len(record) > 20, name  # every row says where its value comes from
+
+
+def test_a_retired_tuning_variable_in_the_environment_raises():
+    """The table's rows carry the names of the environment variables they replaced (round 5); such a variable still set
+    was silently ignored -- the list fuzz's unspeculated leg compared the speculated path with itself that way.  Now
+    the first look-up raises and names the GSR_TUNE row.  (A child process: the variable is never set in this one.)"""
+    import os
+    import subprocess
+    import sys
+
+    import rasterizer.cuda._tuning as T
+
+    child = ("import importlib.util, sys\n"
+             "spec = importlib.util.spec_from_file_location('_tuning', sys.argv[1])\n"
+             "t = importlib.util.module_from_spec(spec); spec.loader.exec_module(t)\n"
+             "try:\n"
+             "    t.get('no_speculation')\n"
+             "except ValueError as e:\n"
+             "    print('raised:', e); sys.exit(0)\n"
+             "print('no error'); sys.exit(3)\n")
+    env = {k: v for k, v in os.environ.items() if not k.startswith("GSR_")}
+    out = subprocess.run([sys.executable, "-c", child, T.__file__], capture_output=True, text=True, timeout=120,
+                         env=dict(env, GSR_NO_SPECULATION="1"))
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "GSR_NO_SPECULATION" in out.stdout and '"no_speculation"' in out.stdout and "GSR_TUNE" in out.stdout
+    clean = subprocess.run([sys.executable, "-c", child, T.__file__], capture_output=True, text=True, timeout=120,
+                           env=env)
+    assert clean.returncode == 3, clean.stdout + clean.stderr  # (and nothing raises without it)
+
+
+def test_set_overrides_reaches_the_speculation_floor(tune):
+    """`speculate_min` is cached with the speculation mode (rasterizer/ahead.py); `set_overrides` must reach it --
+    and leave a mode a caller set in place (bench.py's isolation steps) as it is."""
+    R._speculation_mode()
+    saved = R._spec_knobs["mode"]
+    try:
+        R._spec_knobs["mode"] = "0"
+        tune(speculate_min=12345)
+        assert R._speculation_mode() == "0" and R._spec_knobs["min_points"] == 12345
+        tune()
+        assert R._speculation_mode() == "0" and R._spec_knobs["min_points"] == 65536
+    finally:
+        R._spec_knobs["mode"] = saved

@@ -2,7 +2,12 @@
 sequence of views over scenes of different sizes, resolutions and opacities (the number of Gaussians and list
 entries jumps up and down, so guesses overflow and are rebuilt) must give, call by call, exactly the images
 and (up to atomic summation order) the gradients of the same calls made without speculation and without cache.
+The plain leg runs under the tuning table's `no_speculation` = 1 and `two_round` = "0" (on top of whatever GSR_TUNE
+set); the speculated leg under the overrides as found.  Every call checks from `rasterize.counters` that the plain leg
+built exact lists only (a leg that quietly took the other path counts as a mismatch), and the speculated leg's totals
+are printed at the end (`spec_counters: {json}`) so that a caller can assert what it covered.
 python tools/exp/fuzz_sequence.py [calls] [seed]"""
+import json
 import os
 import sys
 
@@ -14,8 +19,11 @@ from harness import scene as S
 from harness.pipeline import CameraTensors
 from rasterizer import project_gaussians, rasterize_gaussians
 from rasterizer import rasterize as R
+from rasterizer.cuda import _tuning
 
 DEV = torch.device("cuda:0")
+# what the plain leg must never do (`list_builds_exact` it must do once per rasterize call)
+SPECULATIVE = ("list_builds_device_sized", "list_builds_ahead", "ahead_hits", "ahead_orders_used", "list_builds_two_round")
 
 
 def main():
@@ -59,7 +67,6 @@ def main():
         cam = S.make_camera(cam0.width, cam0.height, yaw=yaw)
         ct = CameraTensors.from_numpy(cam, DEV)
         n = max(1, int(sc["means3d"].shape[0] * frac))
-        os.environ["GSR_NO_SPECULATION"] = "0" if speculate else "1"
         if not speculate:
             R._bin_cache["key"] = None
         means = sc["means3d"][:n].clone().requires_grad_(True)
@@ -91,8 +98,19 @@ def main():
             loss = loss + depth_img.sum() * 0.1
             depth_img = depth_img.detach()
         grads = torch.autograd.grad(loss, (means, wrt, colors))
-        return rgb.detach(), None if alpha is None else alpha.detach(), grads, depth_img
+        return rgb.detach(), None if alpha is None else alpha.detach(), grads, depth_img, 2 if second else 1
 
+    def leg(overrides, *args):
+        """-> (run's results, the counters' increments over it)"""
+        _tuning.set_overrides(overrides)
+        before = dict(R.counters)
+        out = run(*args)
+        torch.cuda.synchronize()
+        return out, {k: R.counters[k] - before.get(k, 0) for k in R.counters}
+
+    base = _tuning.overrides()  # (GSR_TUNE's rows included)
+    plain = dict(base, no_speculation=1, two_round="0")
+    spec_total = {}
     for k in range(calls):
         idx = int(rng.integers(len(scenes)))
         frac = float(rng.choice([1.0, 1.0, 0.5, 0.1, 0.02]))
@@ -104,9 +122,19 @@ def main():
         if rng.integers(4) == 0 and k > 0:
             idx, frac, ofac = last  # the same scene again: the recipe AND the count hint of the previous call fit
         last = (idx, frac, ofac)
-        a = run(idx, frac, ofac, yaw, want_alpha, second, True, omode)
-        b = run(idx, frac, ofac, yaw, want_alpha, second, False, omode)
-        ok = torch.equal(a[0], b[0]) and (a[1] is None or torch.equal(a[1], b[1]))
+        try:
+            a, ca = leg(base, idx, frac, ofac, yaw, want_alpha, second, True, omode)
+            b, cb = leg(plain, idx, frac, ofac, yaw, want_alpha, second, False, omode)
+        finally:
+            _tuning.set_overrides(base)
+        for name, v in ca.items():
+            spec_total[name] = spec_total.get(name, 0) + v
+        wrong = {name: cb[name] for name in SPECULATIVE if cb.get(name, 0)}
+        if cb["list_builds_exact"] < b[4]:
+            wrong["list_builds_exact"] = cb["list_builds_exact"]
+        if wrong:
+            print(f"call {k}: the plain leg did not build exact lists only ({b[4]} rasterize calls): {wrong}", flush=True)
+        ok = not wrong and torch.equal(a[0], b[0]) and (a[1] is None or torch.equal(a[1], b[1]))
         ok = ok and (a[3] is None or torch.equal(a[3], b[3]))
         for ga, gb in zip(a[2], b[2]):
             ok = ok and float((ga - gb).abs().max()) <= 1e-5 * float(gb.abs().max()) + 1e-12
@@ -114,8 +142,8 @@ def main():
         print(f"call {k}: scene {idx} ({int(spec[0] * frac)} Gaussians, {spec[1]}x{spec[2]}) opacity x{ofac} yaw {yaw} "
               f"alpha={want_alpha} second={second} opacity={omode}: {'ok' if ok else 'MISMATCH'}", flush=True)
         bad += 0 if ok else 1
-    os.environ["GSR_NO_SPECULATION"] = "0"
     print("lists:", dict(R.counters))
+    print("spec_counters:", json.dumps(spec_total, sort_keys=True))
     print("mismatches:", bad)
     sys.exit(1 if bad else 0)
 
