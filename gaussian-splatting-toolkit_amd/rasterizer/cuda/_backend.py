@@ -84,6 +84,16 @@ SYMBOLS = (
     "gsr_rasterize_backward_det",
     "gsr_tile_jobs_ints",
     "gsr_tile_jobs_build",
+    "gsr_tsdf_touch",
+    "gsr_tsdf_allocate_workspace_bytes",
+    "gsr_tsdf_allocate",
+    "gsr_tsdf_integrate",
+    "gsr_tsdf_extract_points_workspace_bytes",
+    "gsr_tsdf_extract_points_count",
+    "gsr_tsdf_extract_points_emit",
+    "gsr_tsdf_extract_mesh_workspace_bytes",
+    "gsr_tsdf_extract_mesh_count",
+    "gsr_tsdf_extract_mesh_emit",
     "gsr_debug_count_staged",
     "gsr_debug_wave_trace",
     "gsr_calibrate_valu",
@@ -123,6 +133,9 @@ def _load():
     lib.gsr_rasterize_forward_seg_workspace_bytes.restype = C.c_size_t
     lib.gsr_rasterize_backward_seg_workspace_bytes.restype = C.c_size_t
     lib.gsr_rasterize_backward_det_workspace_bytes.restype = C.c_size_t
+    lib.gsr_tsdf_allocate_workspace_bytes.restype = C.c_size_t
+    lib.gsr_tsdf_extract_points_workspace_bytes.restype = C.c_size_t
+    lib.gsr_tsdf_extract_mesh_workspace_bytes.restype = C.c_size_t
     return lib
 
 

@@ -884,6 +884,86 @@ int gsr_rasterize_backward_det(
     void *workspace, size_t workspace_bytes, float *v_xy, float *v_conic,
     float *v_colors, float *v_extra, float *v_opacity, gsr_stream_t stream);
 
+/* ---- TSDF fusion: point cloud and mesh from rendered depth ------
+ * A bounded, block-sparse truncated-signed-distance volume.  Geometry: `origin[3]`, voxel
+ * length, `sdf_trunc`, blocks (Bx, By, Bz) of 8x8x8 voxels, a pool of `capacity` blocks.
+ * All buffers are the caller's (nothing is allocated here):
+ *   table  int32 [Bz,By,Bx]      pool slot of a block, -1 = not allocated
+ *   tsdf   float [capacity,512]  voxel (lx,ly,lz) of a block at (lz*8 + ly)*8 + lx
+ *   weight float [capacity,512]
+ *   color  float [capacity,512,3]
+ *   flags  uint8 [Bz*By*Bx]      blocks touched by the view in flight; zero between views
+ *   list   int32 [Bz*By*Bx]      this view's touched, allocated blocks, ascending; bit 30
+ *                                set: the slot was handed out by this view (pool rows unset)
+ *   state  int32 [8]             0 allocated blocks, 1 length of `list`, 2 overflow flag,
+ *                                3 largest would-be block count, 4 scratch, 5 points of the
+ *                                last count, 6 vertices, 7 triangles of the last count
+ * Voxel (ix,iy,iz) has its centre at origin[a] + ((float)i_a + 0.5f) * voxel_length.  The
+ * camera: world->camera `viewmat` and its inverse `cam2world` (row-major, 12 floats each,
+ * passed by value in the kernel arguments), pixel (i,j) looks along ((j + 0.5 - cx) / fx,
+ * (i + 0.5 - cy) / fy, 1).  A pixel is usable when 0 < depth <= depth_trunc and `valid`
+ * (uint8 [H,W] or NULL) is non-zero.  Per view: touch, allocate, integrate, in this order on
+ * one stream; nothing is read back. */
+typedef struct gsr_tsdf_volume {
+  float origin[3];
+  float voxel_length;
+  float sdf_trunc;
+  int blocks[3]; /* Bx, By, Bz */
+  int capacity;
+  int32_t *table;
+  float *tsdf;
+  float *weight;
+  float *color;
+  int32_t *state;
+} gsr_tsdf_volume;
+
+typedef struct gsr_tsdf_view {
+  unsigned height, width;
+  float fx, fy, cx, cy;
+  float depth_trunc;
+  float viewmat[12];   /* rows 0..2 of world->camera */
+  float cam2world[12]; /* rows 0..2 of its inverse */
+  const float *depth;  /* [H,W] z-depth */
+  const float *color;  /* [H,W,3] */
+  const uint8_t *valid; /* [H,W] or NULL */
+} gsr_tsdf_view;
+
+/* flags every block within sdf_trunc (per axis) of a usable pixel's world point */
+int gsr_tsdf_touch(const gsr_tsdf_volume *vol, const gsr_tsdf_view *view,
+                   uint8_t *flags, gsr_stream_t stream);
+/* hands pool slots to the flagged blocks without one in ascending block index (a scan, so
+ * the numbering is reproducible), writes `list` and state[0..3], and clears `flags`.
+ * Blocks beyond `capacity` stay -1, set state[2] and are left out of `list`. */
+size_t gsr_tsdf_allocate_workspace_bytes(int num_blocks);
+int gsr_tsdf_allocate(const gsr_tsdf_volume *vol, uint8_t *flags, int32_t *list,
+                      void *workspace, size_t workspace_bytes, gsr_stream_t stream);
+/* running weighted mean of the truncated signed distance and the colour over every voxel
+ * of the blocks in `list` (their number is read on the device from state[1]) */
+int gsr_tsdf_integrate(const gsr_tsdf_volume *vol, const gsr_tsdf_view *view,
+                       const int32_t *list, gsr_stream_t stream);
+/* Point cloud: one point per sign change between a voxel and its +x / +y / +z neighbour,
+ * both observed and |tsdf| < 0.98; rows ordered by (block, voxel, axis).  _count leaves the
+ * number of points in state[5] and per-block offsets in the workspace; _emit (same
+ * workspace, untouched in between) writes `num_points` rows (what the caller read back). */
+size_t gsr_tsdf_extract_points_workspace_bytes(int num_blocks);
+int gsr_tsdf_extract_points_count(const gsr_tsdf_volume *vol, void *workspace,
+                                  size_t workspace_bytes, gsr_stream_t stream);
+int gsr_tsdf_extract_points_emit(const gsr_tsdf_volume *vol, const void *workspace,
+                                 size_t workspace_bytes, int num_points, float *points,
+                                 float *colors, float *normals, int32_t *axis,
+                                 gsr_stream_t stream);
+/* Surface-nets mesh: one vertex per cell whose eight corners are observed with
+ * |tsdf| < 0.98 and mixed signs, one quad (two triangles, normals towards positive tsdf)
+ * per sign-changing grid edge whose four cells are active.  _count leaves the numbers of
+ * vertices and triangles in state[6], state[7]. */
+size_t gsr_tsdf_extract_mesh_workspace_bytes(int num_blocks, int capacity);
+int gsr_tsdf_extract_mesh_count(const gsr_tsdf_volume *vol, void *workspace,
+                                size_t workspace_bytes, gsr_stream_t stream);
+int gsr_tsdf_extract_mesh_emit(const gsr_tsdf_volume *vol, void *workspace,
+                               size_t workspace_bytes, int num_vertices, int num_triangles,
+                               float *vertices, float *vertex_colors, int32_t *triangles,
+                               gsr_stream_t stream);
+
 /* ---- measurement hook ---------------------------------------------------------
  * counters: two device uint64 (or NULL = off, the default).  While set, the 16x16
  * compositing kernels add the number of list entries they stage to counters[0]
