@@ -15,6 +15,7 @@ Orders that the rules leave to the implementation and that both sides follow:
     otherwise;
   * a blended normal is ``(g0*r1 + g1*r0)/(r0 + r1)`` divided by ``sqrt((nx*nx + ny*ny) + nz*nz)`` (zero if that is 0).
 """
+import functools
 import math
 
 import numpy as np
@@ -472,3 +473,322 @@ def dense_view_sdf(volume_args, depth, color, fx, fy, cx, cy, viewmat, valid=Non
     every = np.arange(int(np.prod(vol.blocks)))
     vol.flagged_blocks = lambda *a, **k: every
     return vol.integrate(depth, color, fx, fy, cx, cy, viewmat, valid=valid, depth_trunc=depth_trunc)["sdf"]
+
+
+# ---- noise scene: per-pixel random depth over a volume of more than 2048 blocks ---------------------------------------
+# Nothing here is a surface: every pixel is a depth point of its own, so nearly every block of the volume is opened by
+# nearly every view (lists longer than the 2048 workgroups of the looping kernels), and the fused values have no
+# smoothness for an error to hide in -- a voxel that takes the wrong pixel takes an unrelated depth and colour.
+NOISE_L = 1.0 / 64
+NOISE_W, NOISE_H = 317, 203
+NOISE_DEPTH_TRUNC = 3.0
+NOISE_BLOCKS = (16, 12, 16)
+NOISE_ORIGIN = (-1.0, -0.75, -1.0)
+NOISE_OVERFLOW_CAPACITY = 2500
+
+
+def noise_volume_args(capacity=3072):
+    L = NOISE_L
+    return dict(voxel_length=L, sdf_trunc=4 * L, origin=NOISE_ORIGIN, blocks=NOISE_BLOCKS, capacity=capacity)
+
+
+def noise_intrinsics():
+    fx = float(np.float32(0.5 * NOISE_W / math.tan(math.radians(100.0) / 2)))
+    return fx, float(np.float32(1.07 * fx)), NOISE_W / 2.0 + 0.37, NOISE_H / 2.0 - 0.21
+
+
+def noise_cameras():
+    """One camera inside the volume, three near its corners, one outside it (its frustum clips the volume)."""
+    return [look_at((-0.93, -0.68, -0.9), (0.35, 0.2, 0.3)),
+            look_at((0.92, 0.66, -0.88), (-0.3, -0.25, 0.35)),
+            look_at((0.1, -0.05, 0.2), (0.6, 0.3, -0.5)),
+            look_at((-0.9, 0.68, 0.93), (0.3, -0.2, -0.35)),
+            look_at((1.6, -1.2, 1.45), (0.1, 0.0, 0.05))]
+
+
+def noise_view(k, poison=False):
+    """-> depth [H,W] f32 uniform in [0.15, 3.2] with 5 % zeros, color [H,W,3] f32 uniform, valid [H,W] u8 (90 % set).
+    `poison`: a fixed 1 % of the pixels hold NaN, +inf, -1 and 1.5 * depth_trunc in turn; their `valid` stays 1."""
+    rng = np.random.default_rng(4100 + k)
+    depth = rng.uniform(0.15, 3.2, (NOISE_H, NOISE_W)).astype(np.float32)
+    depth[rng.random((NOISE_H, NOISE_W)) < 0.05] = 0.0
+    color = rng.random((NOISE_H, NOISE_W, 3)).astype(np.float32)
+    valid = (rng.random((NOISE_H, NOISE_W)) < 0.9).astype(np.uint8)
+    bad = rng.permutation(NOISE_H * NOISE_W)[:NOISE_H * NOISE_W // 100]
+    if poison:
+        values = np.array([np.nan, np.inf, -1.0, NOISE_DEPTH_TRUNC * 1.5], np.float32)
+        depth.reshape(-1)[bad] = values[np.arange(len(bad)) % 4]
+    valid.reshape(-1)[bad] = 1
+    return depth, color, valid
+
+
+def sphere_views(n_views=None):
+    """The scenes as lists of views: dicts of the keyword arguments of `integrate`."""
+    fx, fy, cx, cy = sphere_intrinsics()
+    out = []
+    for V in sphere_cameras()[:n_views]:
+        d, c, m = sphere_view(V)
+        out.append(dict(depth=d, color=c, fx=fx, fy=fy, cx=cx, cy=cy, viewmat=V, valid=m, depth_trunc=10.0))
+    return out
+
+
+def room_views():
+    fx, fy, cx, cy = room_intrinsics()
+    out = []
+    for V in room_cameras():
+        d, c = room_view(V)
+        out.append(dict(depth=d, color=c, fx=fx, fy=fy, cx=cx, cy=cy, viewmat=V, valid=None,
+                        depth_trunc=ROOM_DEPTH_TRUNC))
+    return out
+
+
+def noise_views(poison=False, masked=False):
+    fx, fy, cx, cy = noise_intrinsics()
+    out = []
+    for k, V in enumerate(noise_cameras()):
+        d, c, m = noise_view(k, poison)
+        out.append(dict(depth=d, color=c, fx=fx, fy=fy, cx=cx, cy=cy, viewmat=V, valid=m if masked else None,
+                        depth_trunc=NOISE_DEPTH_TRUNC))
+    return out
+
+
+def fuse_views(vol, views):
+    """Integrate `views` (dicts as above) into a RefVolume, or a wrapper with the same `integrate`, in order."""
+    return [vol.integrate(v["depth"], v["color"], v["fx"], v["fy"], v["cx"], v["cy"], v["viewmat"], valid=v["valid"],
+                          depth_trunc=v["depth_trunc"]) for v in views]
+
+
+def blocked(a, blocks):
+    """dense [Bz*8, By*8, Bx*8(, C)] -> [num_blocks, 512(, C)] in the pool's block and voxel order."""
+    Bx, By, Bz = blocks
+    tail = a.shape[3:]
+    a = a.reshape((Bz, 8, By, 8, Bx, 8) + tail)
+    a = a.transpose((0, 2, 4, 1, 3, 5) + tuple(range(6, 6 + len(tail))))
+    return np.ascontiguousarray(a).reshape((Bx * By * Bz, 512) + tail)
+
+
+def dense_fusion_f64(volume_args, views, lists=None):
+    """The fusion rule in plain float64 over EVERY voxel of the volume: no blocks, no touch step, no slot table.
+
+    The parameters are the float32 numbers the kernels receive (voxel length, truncation, origin, intrinsics, the
+    world->camera matrix), widened; every operation on them is float64.  -> dict of tsdf [num_blocks,512], weight,
+    color [num_blocks,512,3] and
+      unstable [num_blocks,512]: true where, in any view, a float32 evaluation may decide otherwise than this one -- a
+        projected coordinate within AMBIG_PIXEL of an integer (voxels in front of the camera), the fetched depth within
+        AMBIG_VALUE of depth_trunc, or the sdf within AMBIG_VALUE of -sdf_trunc;
+      band [num_blocks,512] int64: bit k set where view k updates the voxel with sdf < sdf_trunc -- what the touch step
+        of view k has to cover (an update with sdf >= sdf_trunc is free space: it stores 1, and only blocks that a
+        depth point opened receive it).
+
+    A block-sparse volume applies a view to the blocks that view opened, this function to every voxel: the two agree
+    where every block is opened by every view that sees it (the noise scene).  For a scene of surfaces, `lists[k]`
+    (linear block indices) confines view k to those blocks; `band` does not depend on it, and says whether the lists
+    hold what they must."""
+    w32 = lambda x: float(np.float32(x))  # noqa: E731
+    L, trunc = w32(volume_args["voxel_length"]), w32(volume_args["sdf_trunc"])
+    origin = np.asarray(volume_args["origin"], np.float32).astype(np.float64)
+    Bx, By, Bz = (int(b) for b in volume_args["blocks"])
+    X = origin[0] + (np.arange(Bx * 8) + 0.5) * L
+    Y = origin[1] + (np.arange(By * 8) + 0.5) * L
+    Z = origin[2] + (np.arange(Bz * 8) + 0.5) * L
+    pz, py, px = np.meshgrid(Z, Y, X, indexing="ij")
+    shape = px.shape
+    tsdf = np.zeros(shape)
+    weight = np.zeros(shape)
+    color = np.zeros(shape + (3,))
+    unstable = np.zeros(shape, bool)
+    band = np.zeros(shape, np.int64)
+    for k, view in enumerate(views):
+        depth = np.asarray(view["depth"], np.float32).astype(np.float64)
+        image = np.asarray(view["color"], np.float32).astype(np.float64)
+        H, W = depth.shape
+        fx, fy, cx, cy = (w32(view[k]) for k in ("fx", "fy", "cx", "cy"))
+        dt = w32(view["depth_trunc"])
+        M = np.asarray(view["viewmat"], np.float32).astype(np.float64)
+        xc = M[0, 0] * px + M[0, 1] * py + M[0, 2] * pz + M[0, 3]
+        yc = M[1, 0] * px + M[1, 1] * py + M[1, 2] * pz + M[1, 3]
+        zc = M[2, 0] * px + M[2, 1] * py + M[2, 2] * pz + M[2, 3]
+        front = zc > 0
+        zs = np.where(front, zc, 1.0)
+        u = fx * xc / zs + cx
+        v = fy * yc / zs + cy
+        unstable |= front & ((np.abs(u - np.rint(u)) < AMBIG_PIXEL) | (np.abs(v - np.rint(v)) < AMBIG_PIXEL))
+        ju, iv = np.floor(u), np.floor(v)
+        inside = front & (ju >= 0) & (ju < W) & (iv >= 0) & (iv < H)
+        j = np.where(inside, ju, 0).astype(np.int64)
+        i = np.where(inside, iv, 0).astype(np.int64)
+        d = depth[i, j]
+        finite = np.isfinite(d)
+        dz = np.where(finite, d, 0.0)  # (a NaN or inf pixel is unusable; kept out of the arithmetic below)
+        unstable |= inside & finite & (np.abs(dz - dt) < AMBIG_VALUE)
+        usable = inside & finite & (dz > 0) & (dz <= dt)
+        if view["valid"] is not None:
+            usable &= np.asarray(view["valid"])[i, j] != 0
+        xn = (j + 0.5 - cx) / fx
+        yn = (i + 0.5 - cy) / fy
+        sdf = (dz - zc) * np.sqrt(1.0 + xn * xn + yn * yn)
+        unstable |= usable & (np.abs(sdf + trunc) < AMBIG_VALUE)
+        upd = usable & (sdf > -trunc)
+        band |= (upd & (sdf < trunc)).astype(np.int64) << k
+        if lists is not None:
+            member = np.zeros(Bx * By * Bz, bool)
+            member[np.asarray(lists[k], np.int64)] = True
+            upd &= member.reshape(Bz, By, Bx).repeat(8, 0).repeat(8, 1).repeat(8, 2)
+        f = np.minimum(1.0, sdf / trunc)
+        w1 = weight + 1.0
+        tsdf = np.where(upd, (tsdf * weight + f) / w1, tsdf)
+        color = np.where(upd[..., None], (color * weight[..., None] + image[i, j]) / w1[..., None], color)
+        weight = np.where(upd, w1, weight)
+    blocks = (Bx, By, Bz)
+    return {"tsdf": blocked(tsdf, blocks), "weight": blocked(weight, blocks), "color": blocked(color, blocks),
+            "unstable": blocked(unstable, blocks), "band": blocked(band, blocks)}
+
+
+def pool_by_block(vol_table, pool):
+    """pool rows [capacity, 512(,C)] -> [num_blocks, 512(,C)] through the slot table (zeros where there is no slot)."""
+    table = np.asarray(vol_table).reshape(-1)
+    out = np.zeros((len(table),) + pool.shape[1:], pool.dtype)
+    held = table >= 0
+    out[held] = pool[table[held]]
+    return out
+
+
+def f64_distance(table, tsdf, weight, color, dense, what=""):
+    """A fused float32 volume (table and pool arrays) against `dense` = dense_fusion_f64(...).  -> dict: stable (mask
+    [num_blocks,512]), unstable_share, uncovered (stable voxels float64 updated that lie in no allocated block),
+    weight_mismatches, d_tsdf / d_color (largest distances), all over stable voxels."""
+    t64, w64, c64, unstable = (dense[k] for k in ("tsdf", "weight", "color", "unstable"))
+    stable = ~unstable
+    t, w, c = (pool_by_block(table, a) for a in (tsdf, weight, color))
+    held = (np.asarray(table).reshape(-1) >= 0)[:, None]
+    rep = {"stable": stable, "unstable_share": float(unstable.mean()),
+           "uncovered": int((stable & (w64 > 0) & ~held).sum()),
+           "weight_mismatches": int((w.astype(np.float64) != w64)[stable].sum()),
+           "d_tsdf": float(np.abs(t - t64)[stable].max()), "d_color": float(np.abs(c - c64)[stable].max())}
+    if what:
+        print(f"{what}: {int(stable.sum())} stable voxels ({rep['unstable_share']:.3%} unstable), "
+              f"{int((w64 > 0)[stable].sum())} updated in float64, {rep['uncovered']} of them in no allocated block, "
+              f"{rep['weight_mismatches']} weights differ, max |tsdf - f64| {rep['d_tsdf']:.3e}, "
+              f"max |colour - f64| {rep['d_color']:.3e}")
+    return rep
+
+
+# ---- random volumes for the extraction ---------------------------------------------------------------------------------
+RANDOM_SHAPES = [(2100, 1, 1), (1, 1, 2100), (13, 17, 11), (1, 1, 1)]
+RANDOM_KINDS = ["smooth", "noise"]
+RANDOM_L = 1.0 / 64
+SMOOTH_WAVES, SMOOTH_WAVELENGTHS = 3, (16.0, 40.0)
+PLANTED = (np.float32(0.0), np.float32(-0.0), QUALIFY, -QUALIFY, np.nextafter(QUALIFY, F(0)))
+
+
+def random_fill(blocks):
+    """Share of allocated blocks per shape: the oracle stays within a few seconds on each."""
+    return 1.0 if int(np.prod(blocks)) == 1 else 0.8
+
+
+def random_volume_state(blocks, capacity=None, fill=0.8, seed=0, kind="noise", plant=0.002):
+    """A `state_dict` that no fusion produced.  A random `fill` share of the blocks holds a slot, the slot numbers are a
+    random permutation (slot order unrelated to block order), `capacity` None leaves three spare slots.  tsdf:
+    "smooth" = 0.6 times a sum of three random sinusoids over the voxel position (wavelengths of 16 to 40 voxels),
+    clipped to [-1, 1]; "noise" = clip(0.6 N(0,1), -1, 1) per voxel.  Then weight = 0 on a random 10 % of the voxels
+    (weights are 1..6 elsewhere), and each of the values of PLANTED on a random `plant` share of them.
+
+    Surface nets lists a directed edge twice wherever a cell face has the signs of a checkerboard (the four grid edges
+    of that face all cross, and each of their quads joins the same two cells), so a mesh is consistently oriented in
+    the sense of `mesh_report` only if the field has no such face.  The smooth kind is meant to have none: its
+    wavelengths are long, and the planted values that count as positive (0.0, -0.0, just below 0.98) go only where the
+    field is not negative, so that no planted voxel flips a sign next to the surface (the noise kind plants them
+    everywhere).  Whether a given seed gives such a field is pinned on the oracle (test_tsdf_host.py)."""
+    rng = np.random.default_rng(seed)
+    Bx, By, Bz = (int(b) for b in blocks)
+    nb = Bx * By * Bz
+    n = max(1, min(nb, int(round(fill * nb))))
+    capacity = n + 3 if capacity is None else int(capacity)
+    assert capacity >= n
+    held = np.sort(rng.permutation(nb)[:n])
+    table = np.full(nb, -1, np.int32)
+    table[held] = rng.permutation(n).astype(np.int32)
+    L = np.float32(RANDOM_L)
+    origin = np.array([-0.3, 0.2, 0.1], np.float32)
+    v = np.arange(512)
+    g = np.stack([(held % Bx)[:, None] * 8 + (v & 7)[None], ((held // Bx) % By)[:, None] * 8 + ((v >> 3) & 7)[None],
+                  (held // (Bx * By))[:, None] * 8 + (v >> 6)[None]], -1).astype(np.float64)  # [n,512,3]
+    if kind == "smooth":
+        f = np.zeros((n, 512))
+        for _ in range(SMOOTH_WAVES):
+            k = rng.standard_normal(3)
+            k *= 2 * math.pi / (rng.uniform(*SMOOTH_WAVELENGTHS) * np.linalg.norm(k))
+            f += np.sin(g @ k + rng.uniform(0, 2 * math.pi))
+        f = np.clip(0.6 * f, -1.0, 1.0)
+    elif kind == "noise":
+        f = np.clip(0.6 * rng.standard_normal((n, 512)), -1.0, 1.0)
+    else:
+        raise ValueError(kind)
+    f = f.astype(np.float32)
+    w = rng.integers(1, 7, (n, 512)).astype(np.float32)
+    w[rng.random((n, 512)) < 0.1] = 0.0
+    where = rng.random((n, 512))
+    for k, value in enumerate(PLANTED):
+        here = (where >= k * plant) & (where < (k + 1) * plant)
+        if kind == "smooth" and abs(value) < QUALIFY:
+            here &= f >= 0
+        f[here] = value
+    col = rng.random((n, 512, 3)).astype(np.float32)
+    tsdf = np.zeros((capacity, 512), np.float32)
+    weight = np.zeros((capacity, 512), np.float32)
+    color = np.zeros((capacity, 512, 3), np.float32)
+    tsdf[table[held]], weight[table[held]], color[table[held]] = f, w, col
+    return {"voxel_length": float(L), "sdf_trunc": float(4 * L), "origin": origin, "blocks": (Bx, By, Bz),
+            "capacity": capacity, "table": table.reshape(Bz, By, Bx), "tsdf": tsdf, "weight": weight, "color": color,
+            "num_allocated": n, "overflow": False, "needed": n}
+
+
+def ref_from_state(sd):
+    """A RefVolume holding the state `sd` (its arrays are copied)."""
+    vol = RefVolume(sd["voxel_length"], sd["sdf_trunc"], sd["origin"], sd["blocks"], sd["capacity"])
+    vol.table = np.array(sd["table"], np.int32)
+    vol.tsdf, vol.weight, vol.color = (np.array(sd[k], np.float32) for k in ("tsdf", "weight", "color"))
+    vol.num_allocated, vol.overflow, vol.needed = int(sd["num_allocated"]), bool(sd["overflow"]), int(sd["needed"])
+    return vol
+
+
+def band_uncovered(dense, lists):
+    """Per view: stable voxels that the view updates with sdf < sdf_trunc (float64) in a block missing from the
+    view's list."""
+    out = []
+    for k, blocks in enumerate(lists):
+        need = ((dense["band"] >> k) & 1).astype(bool) & ~dense["unstable"]
+        need[np.asarray(blocks, np.int64)] = False
+        out.append(int(need.sum()))
+    return out
+
+
+# ---- cases shared by the CPU and the GPU tests --------------------------------------------------------------------------
+def f64_case(scene):
+    """-> volume args, views, and `lists(infos)`: what dense_fusion_f64 takes as `lists` for this scene -- None on the
+    noise scene (the plain rule), the oracle's per-view blocks on the scenes of surfaces."""
+    if scene == "noise":
+        return noise_volume_args(), noise_views(), lambda infos: None
+    args, views = (sphere_volume_args(), sphere_views()) if scene == "sphere" else (room_volume_args(), room_views())
+    return args, views, lambda infos: [i["blocks"] for i in infos]
+
+
+@functools.lru_cache(maxsize=None)
+def fused_oracle(scene, capacity=None, poison=False, masked=False):
+    """-> (RefVolume, infos) of a whole scene, computed once per process; callers leave it unchanged."""
+    if scene == "noise":
+        args, views = noise_volume_args(), noise_views(poison, masked)
+    else:
+        args, views, _ = f64_case(scene)
+    if capacity is not None:
+        args = {**args, "capacity": capacity}
+    vol = RefVolume(**args)
+    return vol, fuse_views(vol, views)
+
+
+RANDOM_SEED = 8  # (with it the smooth fields have no ambiguous face: test_oracle_extraction_of_random_volumes)
+
+
+@functools.lru_cache(maxsize=None)
+def random_state(blocks, kind):
+    return random_volume_state(blocks, fill=random_fill(blocks), seed=RANDOM_SEED, kind=kind)
