@@ -205,7 +205,7 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(
   if (RGBD) v_extra[g] = acc[9];
 }
 
-// ---- depth segments -------------------------------------------------------------------
+// ---- depth segments (docs/history/DESIGN_r01-r05.md 4.16) -------------------------------------------------------------------
 // A deep tile's walk is a serial chain; on a grid that cannot fill the chip (480 x 270 is 510 tiles) the kernel lasts as
 // long as its deepest tile.  The backward's per-pixel state is two scalars (T, K) and a run of list entries maps it
 // affinely:  T_out = T_in R,  K_out = K_in - T_in S  with R the product of the run's `ra` and S the sum of
@@ -819,6 +819,92 @@ int zero_grads(int n, unsigned channels, float *v_xy, float *v_conic, float *v_c
   return GSR_OK;
 }
 
+// (the tile16 kernels' accumulators: v_xy | v_conic | v_colors [n,3] | v_opacity and, with the fourth channel, v_extra)
+int zero_accumulators(int n, bool rgbd, float *v_xy, float *v_conic, float *v_colors, float *v_opacity, float *v_extra,
+                      hipStream_t s) {
+  if (int rc = zero_grads(n, 3, v_xy, v_conic, v_colors, v_opacity, s)) return rc;
+  return rgbd ? gsr_zero_async(v_extra, sizeof(float) * (size_t)n, s) : GSR_OK;
+}
+
+// ---- the one launch site of raster_bwd_tile16_kernel ---------------------------------------------------------------
+// What a launch takes; gsr_rasterize_backward{_ex,_rgbd,_seg,_two,_det} fill it and call launch_tile16_backward.
+struct Bwd16 {
+  unsigned img_h, img_w;
+  int num_points;
+  const int32_t *ids, *tile_bins;
+  const float *xys, *conics, *colors, *opacities, *background, *final_Ts;
+  const int32_t *final_idx;
+  const float *v_output, *v_output_alpha;  // (v_output_alpha may be null: no cotangent)
+  float *v_xy, *v_conic, *v_colors, *v_opacity;
+  int deep_arg;               // deep_tile_threshold as the caller gave it (threshold | order flags)
+  bool accumulators_zeroed;   // false: the launch is preceded by zero_accumulators
+  bool static_order = false;  // true: the static block order whatever the flags say (two-round lists, _det)
+  const float *extra = nullptr;  // the fourth channel: with it go v_output_extra and v_extra
+  float extra_background = 0.f;
+  const float *v_output_extra = nullptr;
+  float *v_extra = nullptr;
+  const int32_t *tile_bins2 = nullptr;  // two-round lists: the second ranges, relative to idx_base2
+  int idx_base2 = 0;
+  float *partials = nullptr;  // _det: one row per list entry instead of atomics, and the rows' written flags
+  unsigned char *pflags = nullptr;
+  int segments = 0, segment_min_entries = 0;  // depth segments: >= 2 runs, with the workspace of
+  void *workspace = nullptr;                  // gsr_rasterize_backward_seg_workspace_bytes
+};
+
+template <bool RGBD>
+void launch_tile16_backward(const Bwd16 &a, const int tiles_x, const int tiles_y, const int deep, hipStream_t s) {
+  const int num_tiles = tiles_x * tiles_y, img_w = (int)a.img_w, img_h = (int)a.img_h;
+  const unsigned base = gsr_xcd_grid(tiles_x, tiles_y);
+  const int2 *bins = reinterpret_cast<const int2 *>(a.tile_bins), *bins2 = reinterpret_cast<const int2 *>(a.tile_bins2);
+  const float2 *xys = reinterpret_cast<const float2 *>(a.xys);
+  const float bg_extra = RGBD ? a.extra_background : 0.f;
+  const float *v_output_extra = RGBD ? a.v_output_extra : nullptr;
+  float *v_extra = RGBD ? a.v_extra : nullptr;
+  if (a.segments < 2) {
+    hipLaunchKernelGGL((raster_bwd_tile16_kernel<4, RGBD, false>), dim3(deep ? 4 * base : base), dim3(64), 0, s, tiles_x,
+                       num_tiles, img_w, img_h, a.ids, bins, xys, a.conics, a.colors, a.opacities, a.background,
+                       a.final_Ts, a.final_idx, a.v_output, a.v_output_alpha, a.v_xy, a.v_conic, a.v_colors, a.v_opacity,
+                       a.extra, bg_extra, v_output_extra, v_extra, deep, base, a.partials, a.pflags, bins2, a.idx_base2);
+    return;
+  }
+  // (R, S) of the runs behind each run per pixel, their prefixes, then one wave per (tile, sub-tile, run)
+  const int segments = a.segments, threshold = gsr_deep_threshold(a.deep_arg);
+  const int seg_min = a.segment_min_entries > threshold ? a.segment_min_entries : threshold;
+  float2 *state = static_cast<float2 *>(a.workspace);
+  hipLaunchKernelGGL(raster_bwd_segstate_kernel<RGBD>, dim3((unsigned)(segments - 1) * 4u * base), dim3(64), 0, s, tiles_x,
+                     num_tiles, img_w, img_h, a.ids, bins, xys, a.conics, a.colors, a.opacities, a.final_Ts, a.final_idx,
+                     a.v_output, a.extra, v_output_extra, deep, base, segments, seg_min, state);
+  hipLaunchKernelGGL(raster_bwd_segprefix_kernel, dim3((unsigned)(((size_t)a.img_h * a.img_w + 255) / 256)), dim3(256), 0,
+                     s, tiles_x, img_w, img_h, bins, threshold, segments, seg_min, state);
+  hipLaunchKernelGGL((raster_bwd_tile16_kernel<4, RGBD, true>), dim3((unsigned)segments * 4u * base), dim3(64), 0, s,
+                     tiles_x, num_tiles, img_w, img_h, a.ids, bins, xys, a.conics, a.colors, a.opacities, a.background,
+                     a.final_Ts, a.final_idx, a.v_output, a.v_output_alpha, a.v_xy, a.v_conic, a.v_colors, a.v_opacity,
+                     a.extra, bg_extra, v_output_extra, v_extra, deep, base, a.partials, a.pflags, bins2, a.idx_base2,
+                     segments, seg_min, (const float2 *)state);
+}
+
+// Checks what every 16-px entry requires, clears the accumulators unless the caller has, builds the job order where the
+// deep argument asks for one and launches; `who` is the entry's name in the messages.  No points: nothing is launched.
+int launch_tile16_backward(const char *who, const Bwd16 &a, hipStream_t s) {
+  GSR_REQUIRE(a.img_h > 0 && a.img_w > 0, "%s: empty image", who);
+  GSR_REQUIRE(a.num_points >= 0, "%s: num_points < 0", who);
+  if (a.num_points == 0) return GSR_OK;
+  const bool rgbd = a.extra != nullptr;
+  GSR_REQUIRE(a.ids && a.tile_bins && a.xys && a.conics && a.colors && a.opacities && a.background && a.final_Ts &&
+                  a.final_idx && a.v_output && a.v_xy && a.v_conic && a.v_colors && a.v_opacity &&
+                  (!rgbd || (a.v_output_extra && a.v_extra)),
+              "%s: null pointer", who);
+  if (!a.accumulators_zeroed)  // (else: cleared by the forward launch's zero_ptr, untouched since)
+    if (int rc = zero_accumulators(a.num_points, rgbd, a.v_xy, a.v_conic, a.v_colors, a.v_opacity, a.v_extra, s)) return rc;
+  const int tiles_x = (int)gsr_cdiv(a.img_w, 16), tiles_y = (int)gsr_cdiv(a.img_h, 16);
+  const int deep = a.static_order ? gsr_deep_threshold(a.deep_arg)
+                                  : gsr_prepare_jobs(a.deep_arg, tiles_x, tiles_y, a.tile_bins, s);
+  if (rgbd) launch_tile16_backward<true>(a, tiles_x, tiles_y, deep, s);
+  else launch_tile16_backward<false>(a, tiles_x, tiles_y, deep, s);
+  GSR_CHECK_LAUNCH(who);
+  return GSR_OK;
+}
+
 }  // namespace
 
 GSR_EXPORT int gsr_rasterize_backward_nd(
@@ -868,30 +954,10 @@ GSR_EXPORT int gsr_rasterize_backward_ex(
                                      gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities,
                                      background, final_Ts, final_idx, v_output, v_output_alpha, v_xy,
                                      v_conic, v_colors, v_opacity, stream);
-  GSR_REQUIRE(img_height > 0 && img_width > 0, "rasterize_backward: empty image");
-  GSR_REQUIRE(num_points >= 0, "rasterize_backward: num_points < 0");
-  if (num_points == 0) return GSR_OK;
-  GSR_REQUIRE(gaussian_ids_sorted && tile_bins && xys && conics && colors && opacities &&
-                  background && final_Ts && final_idx && v_output && v_xy &&
-                  v_conic && v_colors && v_opacity,
-              "rasterize_backward: null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  if (!accumulators_zeroed) {  // (else: cleared by gsr_rasterize_forward_ex's zero_ptr, untouched since)
-    int rc = zero_grads(num_points, 3, v_xy, v_conic, v_colors, v_opacity, s);
-    if (rc != GSR_OK) return rc;
-  }
-  const int tiles_x = (int)gsr_cdiv(img_width, 16), tiles_y = (int)gsr_cdiv(img_height, 16);
-  const int num_tiles = tiles_x * tiles_y;
-  const unsigned base = gsr_xcd_grid(tiles_x, num_tiles / tiles_x);
-  const int deep = gsr_prepare_jobs(deep_tile_threshold, tiles_x, tiles_y, tile_bins, s);
-  hipLaunchKernelGGL((raster_bwd_tile16_kernel<4, false>), dim3(deep ? 4 * base : base), dim3(64), 0, s, tiles_x,
-                     num_tiles, (int)img_width, (int)img_height, gaussian_ids_sorted,
-                     reinterpret_cast<const int2 *>(tile_bins), reinterpret_cast<const float2 *>(xys), conics, colors,
-                     opacities, background, final_Ts, final_idx, v_output, v_output_alpha, v_xy, v_conic, v_colors,
-                     v_opacity, (const float *)nullptr, 0.f, (const float *)nullptr, (float *)nullptr, deep, base,
-                     (float *)nullptr, (unsigned char *)nullptr, (const int2 *)nullptr, 0);
-  GSR_CHECK_LAUNCH("rasterize_backward(tile16)");
-  return GSR_OK;
+  const Bwd16 a = {img_height, img_width, num_points, gaussian_ids_sorted, tile_bins, xys, conics, colors,
+                   opacities, background, final_Ts, final_idx, v_output, v_output_alpha, v_xy, v_conic,
+                   v_colors, v_opacity, deep_tile_threshold, accumulators_zeroed != 0};
+  return launch_tile16_backward("rasterize_backward", a, (hipStream_t)stream);
 }
 
 GSR_EXPORT int gsr_rasterize_backward_rgbd(
@@ -901,31 +967,12 @@ GSR_EXPORT int gsr_rasterize_backward_rgbd(
     const int32_t *final_idx, const float *v_output, const float *v_output_extra, const float *v_output_alpha,
     float *v_xy, float *v_conic, float *v_colors, float *v_extra, float *v_opacity, int deep_tile_threshold,
     int accumulators_zeroed, gsr_stream_t stream) {
-  GSR_REQUIRE(img_height > 0 && img_width > 0, "rasterize_backward_rgbd: empty image");
-  GSR_REQUIRE(num_points >= 0, "rasterize_backward_rgbd: num_points < 0");
-  if (num_points == 0) return GSR_OK;
-  GSR_REQUIRE(gaussian_ids_sorted && tile_bins && xys && conics && colors && extra && opacities && background &&
-                  final_Ts && final_idx && v_output && v_output_extra && v_xy && v_conic && v_colors && v_extra &&
-                  v_opacity,
-              "rasterize_backward_rgbd: null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  if (!accumulators_zeroed) {  // (else: cleared by gsr_rasterize_forward_rgbd's zero_ptr)
-    int rc = zero_grads(num_points, 3, v_xy, v_conic, v_colors, v_opacity, s);
-    if (rc != GSR_OK) return rc;
-    if (int zrc = gsr_zero_async(v_extra, sizeof(float) * (size_t)num_points, s)) return zrc;
-  }
-  const int tiles_x = (int)gsr_cdiv(img_width, 16), tiles_y = (int)gsr_cdiv(img_height, 16);
-  const int num_tiles = tiles_x * tiles_y;
-  const unsigned base = gsr_xcd_grid(tiles_x, num_tiles / tiles_x);
-  const int deep = gsr_prepare_jobs(deep_tile_threshold, tiles_x, tiles_y, tile_bins, s);
-  hipLaunchKernelGGL((raster_bwd_tile16_kernel<4, true>), dim3(deep ? 4 * base : base), dim3(64),
-                     0, s, tiles_x, num_tiles, (int)img_width, (int)img_height, gaussian_ids_sorted,
-                     reinterpret_cast<const int2 *>(tile_bins), reinterpret_cast<const float2 *>(xys), conics,
-                     colors, opacities, background, final_Ts, final_idx, v_output, v_output_alpha, v_xy, v_conic,
-                     v_colors, v_opacity, extra, extra_background, v_output_extra, v_extra, deep, base, (float *)nullptr,
-                     (unsigned char *)nullptr, (const int2 *)nullptr, 0);
-  GSR_CHECK_LAUNCH("rasterize_backward_rgbd");
-  return GSR_OK;
+  GSR_REQUIRE(extra || num_points <= 0, "rasterize_backward_rgbd: null pointer");
+  Bwd16 a = {img_height, img_width, num_points, gaussian_ids_sorted, tile_bins, xys, conics, colors,
+             opacities, background, final_Ts, final_idx, v_output, v_output_alpha, v_xy, v_conic,
+             v_colors, v_opacity, deep_tile_threshold, accumulators_zeroed != 0};
+  a.extra = extra, a.extra_background = extra_background, a.v_output_extra = v_output_extra, a.v_extra = v_extra;
+  return launch_tile16_backward("rasterize_backward_rgbd", a, (hipStream_t)stream);
 }
 
 // ---- depth segments: deep tiles' lists cut into `segments` pieces walked by their own waves -------------------
@@ -942,66 +989,19 @@ GSR_EXPORT int gsr_rasterize_backward_seg(
     float *v_xy, float *v_conic, float *v_colors, float *v_extra, float *v_opacity, int deep_tile_threshold,
     int accumulators_zeroed, int segments, int segment_min_entries, void *workspace, size_t workspace_bytes,
     gsr_stream_t stream) {
-  const bool rgbd = extra != nullptr;
-  if (segments < 2 || deep_tile_threshold <= 0) {
-    if (rgbd)
-      return gsr_rasterize_backward_rgbd(img_height, img_width, num_points, gaussian_ids_sorted, tile_bins, xys, conics,
-                                         colors, extra, opacities, background, extra_background, final_Ts, final_idx,
-                                         v_output, v_output_extra, v_output_alpha, v_xy, v_conic, v_colors, v_extra,
-                                         v_opacity, deep_tile_threshold, accumulators_zeroed, stream);
-    return gsr_rasterize_backward_ex(img_height, img_width, 16, num_points, gaussian_ids_sorted, tile_bins, xys, conics,
-                                     colors, opacities, background, final_Ts, final_idx, v_output, v_output_alpha, v_xy,
-                                     v_conic, v_colors, v_opacity, deep_tile_threshold, accumulators_zeroed, stream);
+  Bwd16 a = {img_height, img_width, num_points, gaussian_ids_sorted, tile_bins, xys, conics, colors,
+             opacities, background, final_Ts, final_idx, v_output, v_output_alpha, v_xy, v_conic,
+             v_colors, v_opacity, deep_tile_threshold, accumulators_zeroed != 0};
+  a.extra = extra, a.extra_background = extra_background, a.v_output_extra = v_output_extra, a.v_extra = v_extra;
+  if (segments >= 2 && deep_tile_threshold > 0) {  // (else nothing to cut: the walk of _ex / _rgbd)
+    GSR_REQUIRE(segments <= 16, "rasterize_backward_seg: at most 16 segments");
+    GSR_REQUIRE(num_points <= 0 || (workspace && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0 &&
+                                    workspace_bytes >=
+                                        gsr_rasterize_backward_seg_workspace_bytes(img_height, img_width, segments)),
+                "rasterize_backward_seg: workspace too small or not 8-byte aligned");
+    a.segments = segments, a.segment_min_entries = segment_min_entries, a.workspace = workspace;
   }
-  GSR_REQUIRE(img_height > 0 && img_width > 0, "rasterize_backward_seg: empty image");
-  GSR_REQUIRE(num_points >= 0, "rasterize_backward_seg: num_points < 0");
-  GSR_REQUIRE(segments <= 16, "rasterize_backward_seg: at most 16 segments");
-  if (num_points == 0) return GSR_OK;
-  GSR_REQUIRE(gaussian_ids_sorted && tile_bins && xys && conics && colors && opacities && background && final_Ts &&
-                  final_idx && v_output && v_xy && v_conic && v_colors && v_opacity &&
-                  (!rgbd || (v_output_extra && v_extra)),
-              "rasterize_backward_seg: null pointer");
-  GSR_REQUIRE(workspace && workspace_bytes >= gsr_rasterize_backward_seg_workspace_bytes(img_height, img_width, segments) &&
-                  (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
-              "rasterize_backward_seg: workspace too small or not 8-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  if (!accumulators_zeroed) {
-    int rc = zero_grads(num_points, 3, v_xy, v_conic, v_colors, v_opacity, s);
-    if (rc != GSR_OK) return rc;
-    if (rgbd)
-      if (int zrc = gsr_zero_async(v_extra, sizeof(float) * (size_t)num_points, s)) return zrc;
-  }
-  const int tiles_x = (int)gsr_cdiv(img_width, 16), tiles_y = (int)gsr_cdiv(img_height, 16);
-  const int num_tiles = tiles_x * tiles_y;
-  const unsigned base = gsr_xcd_grid(tiles_x, tiles_y);
-  const int deep_arg = gsr_prepare_jobs(deep_tile_threshold, tiles_x, tiles_y, tile_bins, s);  // (threshold | order flag)
-  deep_tile_threshold = gsr_deep_threshold(deep_tile_threshold);
-  const int seg_min = segment_min_entries > deep_tile_threshold ? segment_min_entries : deep_tile_threshold;
-  float2 *state = static_cast<float2 *>(workspace);
-#define GSR_LAUNCH_BWD_SEG(RGBD_)                                                                                      \
-  hipLaunchKernelGGL(raster_bwd_segstate_kernel<RGBD_>, dim3((unsigned)(segments - 1) * 4u * base), dim3(64), 0, s,    \
-                     tiles_x, num_tiles, (int)img_width, (int)img_height, gaussian_ids_sorted,                         \
-                     reinterpret_cast<const int2 *>(tile_bins), reinterpret_cast<const float2 *>(xys), conics, colors,  \
-                     opacities, final_Ts, final_idx, v_output, extra, v_output_extra, deep_arg, base,                  \
-                     segments, seg_min, state);                                                                        \
-  hipLaunchKernelGGL(raster_bwd_segprefix_kernel, dim3((unsigned)(((size_t)img_height * img_width + 255) / 256)),     \
-                     dim3(256), 0, s, tiles_x, (int)img_width, (int)img_height,                                        \
-                     reinterpret_cast<const int2 *>(tile_bins), deep_tile_threshold, segments, seg_min, state);        \
-  hipLaunchKernelGGL((raster_bwd_tile16_kernel<4, RGBD_, true>), dim3((unsigned)segments * 4u * base), dim3(64), 0, s, \
-                     tiles_x, num_tiles, (int)img_width, (int)img_height, gaussian_ids_sorted,                         \
-                     reinterpret_cast<const int2 *>(tile_bins), reinterpret_cast<const float2 *>(xys), conics, colors,  \
-                     opacities, background, final_Ts, final_idx, v_output, v_output_alpha, v_xy, v_conic, v_colors,    \
-                     v_opacity, extra, extra_background, v_output_extra, v_extra, deep_arg, base,                      \
-                     (float *)nullptr, (unsigned char *)nullptr, (const int2 *)nullptr, 0, segments, seg_min,          \
-                     (const float2 *)state)
-  if (rgbd) {
-    GSR_LAUNCH_BWD_SEG(true);
-  } else {
-    GSR_LAUNCH_BWD_SEG(false);
-  }
-#undef GSR_LAUNCH_BWD_SEG
-  GSR_CHECK_LAUNCH("rasterize_backward_seg");
-  return GSR_OK;
+  return launch_tile16_backward("rasterize_backward_seg", a, (hipStream_t)stream);
 }
 
 // ---- two-round lists: a tile's list = its range in tile_bins, then its range in tile_bins2 (+ idx_base2) ----
@@ -1012,42 +1012,15 @@ GSR_EXPORT int gsr_rasterize_backward_two(
     const float *final_Ts, const int32_t *final_idx, const float *v_output, const float *v_output_extra,
     const float *v_output_alpha, float *v_xy, float *v_conic, float *v_colors, float *v_extra, float *v_opacity,
     int deep_tile_threshold, int accumulators_zeroed, gsr_stream_t stream) {
-  GSR_REQUIRE(img_height > 0 && img_width > 0, "rasterize_backward_two: empty image");
-  GSR_REQUIRE(num_points >= 0 && idx_base2 >= 0, "rasterize_backward_two: negative size");
-  if (num_points == 0) return GSR_OK;
-  const bool rgbd = extra != nullptr;
-  GSR_REQUIRE(gaussian_ids_sorted && tile_bins && tile_bins2 && xys && conics && colors && opacities && background &&
-                  final_Ts && final_idx && v_output && v_xy && v_conic && v_colors && v_opacity &&
-                  (!rgbd || (v_output_extra && v_extra)),
-              "rasterize_backward_two: null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  if (!accumulators_zeroed) {
-    int rc = zero_grads(num_points, 3, v_xy, v_conic, v_colors, v_opacity, s);
-    if (rc != GSR_OK) return rc;
-    if (rgbd)
-      if (int zrc = gsr_zero_async(v_extra, sizeof(float) * (size_t)num_points, s)) return zrc;
-  }
-  const int tiles_x = (int)gsr_cdiv(img_width, 16), tiles_y = (int)gsr_cdiv(img_height, 16);
-  const int num_tiles = tiles_x * tiles_y;
-  const unsigned base = gsr_xcd_grid(tiles_x, tiles_y);
-  const int deep = gsr_deep_threshold(deep_tile_threshold);  // (two-round lists: the static block order)
-  const dim3 grd(deep ? 4 * base : base), blk(64);
-  if (rgbd)
-    hipLaunchKernelGGL((raster_bwd_tile16_kernel<4, true>), grd, blk, 0, s, tiles_x, num_tiles, (int)img_width,
-                       (int)img_height, gaussian_ids_sorted, reinterpret_cast<const int2 *>(tile_bins),
-                       reinterpret_cast<const float2 *>(xys), conics, colors, opacities, background, final_Ts, final_idx,
-                       v_output, v_output_alpha, v_xy, v_conic, v_colors, v_opacity, extra, extra_background,
-                       v_output_extra, v_extra, deep, base, (float *)nullptr, (unsigned char *)nullptr,
-                       reinterpret_cast<const int2 *>(tile_bins2), idx_base2);
-  else
-    hipLaunchKernelGGL((raster_bwd_tile16_kernel<4, false>), grd, blk, 0, s, tiles_x, num_tiles, (int)img_width,
-                       (int)img_height, gaussian_ids_sorted, reinterpret_cast<const int2 *>(tile_bins),
-                       reinterpret_cast<const float2 *>(xys), conics, colors, opacities, background, final_Ts, final_idx,
-                       v_output, v_output_alpha, v_xy, v_conic, v_colors, v_opacity, (const float *)nullptr, 0.f,
-                       (const float *)nullptr, (float *)nullptr, deep, base, (float *)nullptr, (unsigned char *)nullptr,
-                       reinterpret_cast<const int2 *>(tile_bins2), idx_base2);
-  GSR_CHECK_LAUNCH("rasterize_backward_two");
-  return GSR_OK;
+  GSR_REQUIRE(idx_base2 >= 0, "rasterize_backward_two: negative size");
+  GSR_REQUIRE(tile_bins2 || num_points <= 0, "rasterize_backward_two: null pointer");
+  Bwd16 a = {img_height, img_width, num_points, gaussian_ids_sorted, tile_bins, xys, conics, colors,
+             opacities, background, final_Ts, final_idx, v_output, v_output_alpha, v_xy, v_conic,
+             v_colors, v_opacity, deep_tile_threshold, accumulators_zeroed != 0};
+  a.static_order = true;  // (two-round lists: no job order behind either tile_bins)
+  a.extra = extra, a.extra_background = extra_background, a.v_output_extra = v_output_extra, a.v_extra = v_extra;
+  a.tile_bins2 = tile_bins2, a.idx_base2 = idx_base2;
+  return launch_tile16_backward("rasterize_backward_two", a, (hipStream_t)stream);
 }
 
 // ---- deterministic backward ----------------------------------------------------------
@@ -1068,43 +1041,35 @@ GSR_EXPORT int gsr_rasterize_backward_det(
   GSR_REQUIRE(img_height > 0 && img_width > 0, "rasterize_backward_det: empty image");
   GSR_REQUIRE(num_points >= 0 && list_capacity >= 0, "rasterize_backward_det: negative size");
   if (num_points == 0) return GSR_OK;
-  const bool rgbd = extra != nullptr;
   GSR_REQUIRE(gaussian_ids_sorted && tile_bins && xys && conics && colors && opacities && background && final_Ts &&
                   final_idx && v_output && order && cum_sorted && slot_of_entry && v_xy && v_conic && v_colors &&
-                  v_opacity && (!rgbd || (v_output_extra && v_extra)),
+                  v_opacity && (!extra || (v_output_extra && v_extra)),
               "rasterize_backward_det: null pointer");
   GSR_REQUIRE(num_bands >= 1, "rasterize_backward_det: num_bands < 1");
   GSR_REQUIRE(workspace && workspace_bytes >= gsr_rasterize_backward_det_workspace_bytes(list_capacity) &&
                   (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
               "rasterize_backward_det: workspace too small or not 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
-  float *partials = static_cast<float *>(workspace);
-  unsigned char *pflags = reinterpret_cast<unsigned char *>(workspace) +
-                          (((size_t)list_capacity * kPartialStride * sizeof(float) + 255) & ~(size_t)255);
-  if (int zrc = gsr_zero_async(pflags, ((size_t)list_capacity + 3) & ~(size_t)3, s)) return zrc;
-  const int tiles_x = (int)gsr_cdiv(img_width, 16), tiles_y = (int)gsr_cdiv(img_height, 16);
-  const int num_tiles = tiles_x * tiles_y;
-  const unsigned base = gsr_xcd_grid(tiles_x, num_tiles / tiles_x);
-  // (one wave per tile: a split tile would need one partial row per sub-tile wave)
-  if (rgbd) {
-    hipLaunchKernelGGL((raster_bwd_tile16_kernel<4, true>), dim3(base), dim3(64), 0, s, tiles_x, num_tiles,
-                       (int)img_width, (int)img_height, gaussian_ids_sorted, reinterpret_cast<const int2 *>(tile_bins),
-                       reinterpret_cast<const float2 *>(xys), conics, colors, opacities, background, final_Ts, final_idx,
-                       v_output, v_output_alpha, v_xy, v_conic, v_colors, v_opacity, extra, extra_background,
-                       v_output_extra, v_extra, 0, base, partials, pflags, (const int2 *)nullptr, 0);
+  // the walk writes rows of partials instead of adding to the gradients, which reduce_partials_kernel then WRITES: no
+  // clearing; one wave per tile (deep argument 0): a split tile would need one partial row per sub-tile wave
+  Bwd16 a = {img_height, img_width, num_points, gaussian_ids_sorted, tile_bins, xys, conics, colors,
+             opacities, background, final_Ts, final_idx, v_output, v_output_alpha, v_xy, v_conic,
+             v_colors, v_opacity, 0, true};
+  a.static_order = true;
+  a.extra = extra, a.extra_background = extra_background, a.v_output_extra = v_output_extra, a.v_extra = v_extra;
+  a.partials = static_cast<float *>(workspace);
+  a.pflags = reinterpret_cast<unsigned char *>(workspace) +
+             (((size_t)list_capacity * kPartialStride * sizeof(float) + 255) & ~(size_t)255);
+  if (int zrc = gsr_zero_async(a.pflags, ((size_t)list_capacity + 3) & ~(size_t)3, s)) return zrc;
+  if (int rc = launch_tile16_backward("rasterize_backward_det", a, s)) return rc;
+  if (extra)
     hipLaunchKernelGGL(reduce_partials_kernel<true>, dim3(gsr_cdiv(num_points, 256)), dim3(256), 0, s, num_points,
-                       num_bands, list_capacity, order, cum_sorted, slot_of_entry, (const float *)partials,
-                       (const unsigned char *)pflags, v_xy, v_conic, v_colors, v_opacity, v_extra);
-  } else {
-    hipLaunchKernelGGL((raster_bwd_tile16_kernel<4, false>), dim3(base), dim3(64), 0, s, tiles_x, num_tiles,
-                       (int)img_width, (int)img_height, gaussian_ids_sorted, reinterpret_cast<const int2 *>(tile_bins),
-                       reinterpret_cast<const float2 *>(xys), conics, colors, opacities, background, final_Ts, final_idx,
-                       v_output, v_output_alpha, v_xy, v_conic, v_colors, v_opacity, (const float *)nullptr, 0.f,
-                       (const float *)nullptr, (float *)nullptr, 0, base, partials, pflags, (const int2 *)nullptr, 0);
+                       num_bands, list_capacity, order, cum_sorted, slot_of_entry, (const float *)a.partials,
+                       (const unsigned char *)a.pflags, v_xy, v_conic, v_colors, v_opacity, v_extra);
+  else
     hipLaunchKernelGGL(reduce_partials_kernel<false>, dim3(gsr_cdiv(num_points, 256)), dim3(256), 0, s, num_points,
-                       num_bands, list_capacity, order, cum_sorted, slot_of_entry, (const float *)partials,
-                       (const unsigned char *)pflags, v_xy, v_conic, v_colors, v_opacity, (float *)nullptr);
-  }
+                       num_bands, list_capacity, order, cum_sorted, slot_of_entry, (const float *)a.partials,
+                       (const unsigned char *)a.pflags, v_xy, v_conic, v_colors, v_opacity, (float *)nullptr);
   GSR_CHECK_LAUNCH("rasterize_backward_det");
   return GSR_OK;
 }

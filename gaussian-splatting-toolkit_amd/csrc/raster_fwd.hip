@@ -48,7 +48,7 @@ __device__ gsr::WaveTrace g_fwd_trace = {nullptr, 0u};
 // RGBD: a fourth channel (one scalar per Gaussian, e.g. its depth) is composited in the
 // same pass into its own [H,W] image over background `bg_extra` (the
 // models run a second full pass for the depth image, vanilla_gs.py:840-855).
-// ---- depth segments (one walk since round 6) ------------------------------------------------------
+// ---- depth segments (docs/history/DESIGN_r01-r05.md 4.16; one walk since round 6) ------------------------------------------------------
 // On a tile grid that cannot fill the chip the kernel lasts as long as its deepest tile's serial walk.  The list of a
 // tile that is split over four waves is therefore also cut into up to `seg_count` runs, and compositing is ASSOCIATIVE in
 // (C, T): a run walked from T = 1 yields its colour sums C_k and its transmittance product P_k, and the pixel is
@@ -749,6 +749,92 @@ int check_common(const char *who, int tiles_x, int tiles_y, unsigned bw, unsigne
   return GSR_OK;
 }
 
+// ---- the one launch site of raster_fwd_tile16_kernel ---------------------------------------------------------------
+// What a launch takes; gsr_rasterize_forward{,_ex,_rgbd,_seg,_round} fill it and call launch_tile16_forward.
+struct Fwd16 {
+  int tiles_x, tiles_y;
+  unsigned img_w, img_h;
+  const int32_t *ids, *tile_bins;
+  const float *xys, *conics, *colors, *opacities, *background;
+  float *out_img, *final_Ts;
+  int32_t *final_idx;
+  int deep_arg;               // deep_tile_threshold as the caller gave it (threshold | order flags)
+  bool static_order = false;  // true: the static block order whatever the flags say (the two-round lists)
+  const float *extra = nullptr;  // the fourth channel: with it goes out_extra
+  float extra_background = 0.f;
+  float *out_extra = nullptr, *out_alpha = nullptr;
+  void *zero_ptr = nullptr;  // cleared by the launch
+  size_t zero_bytes = 0;
+  int round = 0;  // two-round compositing: 1 | 2 with tile_flags and idx_base
+  int32_t *tile_flags = nullptr;
+  int idx_base = 0;
+  int segments = 0, segment_min_entries = 0;  // depth segments: >= 2 runs, with the workspace of
+  void *workspace = nullptr;                  // gsr_rasterize_forward_seg_workspace_bytes
+};
+
+template <bool RGBD>
+void launch_tile16_forward(const Fwd16 &a, const int deep, const unsigned base, hipStream_t s) {
+  const int num_tiles = a.tiles_x * a.tiles_y, img_w = (int)a.img_w, img_h = (int)a.img_h;
+  const int2 *bins = reinterpret_cast<const int2 *>(a.tile_bins);
+  const float2 *xys = reinterpret_cast<const float2 *>(a.xys);
+  const float bg_extra = RGBD ? a.extra_background : 0.f;
+  unsigned *zero_ptr = static_cast<unsigned *>(a.zero_ptr);
+  const unsigned zero_words = (unsigned)(a.zero_bytes >> 2);
+  if (a.segments < 2) {
+    hipLaunchKernelGGL((raster_fwd_tile16_kernel<RGBD, false>), dim3(deep ? 4 * base : base), dim3(64), 0, s, a.tiles_x,
+                       num_tiles, img_w, img_h, a.ids, bins, xys, a.conics, a.colors, a.opacities, a.background,
+                       a.out_img, a.final_Ts, a.final_idx, a.extra, bg_extra, a.out_extra, deep, base, a.out_alpha,
+                       zero_ptr, zero_words, a.round, a.tile_flags, a.idx_base);
+    return;
+  }
+  // every run walked once, the prefixes resolved per pixel, the crossing runs re-walked (header of this file)
+  const int segments = a.segments, threshold = gsr_deep_threshold(a.deep_arg);
+  const int seg_min = a.segment_min_entries > threshold ? a.segment_min_entries : threshold;
+  const size_t px = (size_t)a.img_h * a.img_w;
+  char *ws = static_cast<char *>(a.workspace);
+  float4 *raw = reinterpret_cast<float4 *>(ws);
+  int *lastp = reinterpret_cast<int *>(ws + (size_t)segments * px * 16);
+  float *extrap = reinterpret_cast<float *>(lastp + (size_t)segments * px);  // (written and read with `extra` only)
+  int *kstarp = reinterpret_cast<int *>(extrap + (size_t)segments * px);
+  int *flagsp = kstarp + px;
+  float *marksp = reinterpret_cast<float *>(flagsp + 4 * (size_t)num_tiles);
+  hipLaunchKernelGGL(seg_marks_clear_kernel, dim3((unsigned)((64 * (size_t)num_tiles + 255) / 256)), dim3(256), 0, s, marksp,
+                     64u * (unsigned)num_tiles);
+  hipLaunchKernelGGL((raster_fwd_tile16_kernel<RGBD, true>), dim3((unsigned)segments * 4u * base), dim3(64), 0, s,
+                     a.tiles_x, num_tiles, img_w, img_h, a.ids, bins, xys, a.conics, a.colors, a.opacities, a.background,
+                     a.out_img, a.final_Ts, a.final_idx, a.extra, bg_extra, a.out_extra, deep, base, a.out_alpha, zero_ptr,
+                     zero_words, a.round, a.tile_flags, a.idx_base, segments, seg_min, raw, lastp, extrap, marksp);
+  hipLaunchKernelGGL(raster_fwd_segresolve_kernel<RGBD>, dim3(4u * base), dim3(64), 0, s, a.tiles_x, num_tiles, img_w,
+                     img_h, bins, a.background, a.out_img, a.final_Ts, a.final_idx, bg_extra, a.out_extra, deep, base,
+                     a.out_alpha, segments, seg_min, raw, lastp, extrap, kstarp, flagsp);
+  hipLaunchKernelGGL(raster_fwd_segrewalk_kernel<RGBD>, dim3((unsigned)segments * 4u * base), dim3(64), 0, s, a.tiles_x,
+                     num_tiles, img_w, img_h, a.ids, bins, xys, a.conics, a.colors, a.opacities, a.background, a.out_img,
+                     a.final_Ts, a.final_idx, a.extra, bg_extra, a.out_extra, deep, base, a.out_alpha, segments, seg_min,
+                     (const float4 *)raw, (const int *)lastp, (const float *)extrap, (const int *)kstarp,
+                     (const int *)flagsp);
+}
+
+// Checks what every 16-px entry requires, builds the job order where the deep argument asks for one and launches; `who`
+// is the entry's name in the messages.
+int launch_tile16_forward(const char *who, const Fwd16 &a, hipStream_t s) {
+  int rc = check_common(who, a.tiles_x, a.tiles_y, 16, a.img_w, a.img_h, 3);
+  if (rc != GSR_OK) return rc;
+  GSR_REQUIRE(a.ids && a.tile_bins && a.xys && a.conics && a.colors && a.opacities && a.background && a.out_img &&
+                  a.final_Ts && a.final_idx,
+              "%s: null pointer", who);
+  GSR_REQUIRE((a.extra == nullptr) == (a.out_extra == nullptr), "%s: extra and out_extra go together", who);
+  GSR_REQUIRE(a.zero_ptr == nullptr || ((a.zero_bytes & 3) == 0 && (reinterpret_cast<uintptr_t>(a.zero_ptr) & 3) == 0 &&
+                                        a.zero_bytes < ((size_t)1 << 34)),
+              "%s: zero_ptr / zero_bytes must be multiples of 4 (and below 16 GB)", who);
+  const unsigned base = gsr_xcd_grid(a.tiles_x, a.tiles_y);
+  const int deep = a.static_order ? gsr_deep_threshold(a.deep_arg)
+                                  : gsr_prepare_jobs(a.deep_arg, a.tiles_x, a.tiles_y, a.tile_bins, s);
+  if (a.extra) launch_tile16_forward<true>(a, deep, base, s);
+  else launch_tile16_forward<false>(a, deep, base, s);
+  GSR_CHECK_LAUNCH(who);
+  return GSR_OK;
+}
+
 }  // namespace
 
 GSR_EXPORT int gsr_rasterize_forward_nd(int tiles_x, int tiles_y, unsigned block_width,
@@ -790,31 +876,17 @@ GSR_EXPORT int gsr_rasterize_forward_ex(int tiles_x, int tiles_y, unsigned block
                                         float *out_img, float *final_Ts, int32_t *final_idx,
                                         int deep_tile_threshold, float *out_alpha, void *zero_ptr,
                                         size_t zero_bytes, gsr_stream_t stream) {
-  int rc = check_common("rasterize_forward", tiles_x, tiles_y, block_width, img_width, img_height, 3);
-  if (rc != GSR_OK) return rc;
-  GSR_REQUIRE(gaussian_ids_sorted && tile_bins && xys && conics && colors && opacities &&
-                  background && out_img && final_Ts && final_idx,
-              "rasterize_forward: null pointer");
-  GSR_REQUIRE((out_alpha == nullptr && zero_ptr == nullptr) || block_width == 16,
-              "rasterize_forward_ex: out_alpha / zero_ptr need block_width 16");
-  GSR_REQUIRE(zero_ptr == nullptr || ((zero_bytes & 3) == 0 && (reinterpret_cast<uintptr_t>(zero_ptr) & 3) == 0 &&
-                                      zero_bytes < ((size_t)1 << 34)),
-              "rasterize_forward_ex: zero_ptr / zero_bytes must be multiples of 4 (and below 16 GB)");
-  if (block_width != 16)
-    return launch_generic(tiles_x, tiles_y, block_width, img_width, img_height, 3,
-                          gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities,
-                          background, out_img, final_Ts, final_idx, (hipStream_t)stream);
-  const int num_tiles = tiles_x * tiles_y;
-  const unsigned base = gsr_xcd_grid(tiles_x, num_tiles / tiles_x);
-  const int deep = gsr_prepare_jobs(deep_tile_threshold, tiles_x, tiles_y, tile_bins, (hipStream_t)stream);
-  hipLaunchKernelGGL(raster_fwd_tile16_kernel<false>, dim3(deep ? 4 * base : base), dim3(64), 0,
-                     (hipStream_t)stream, tiles_x, num_tiles, (int)img_width, (int)img_height, gaussian_ids_sorted,
-                     reinterpret_cast<const int2 *>(tile_bins),
-                     reinterpret_cast<const float2 *>(xys), conics, colors, opacities, background,
-                     out_img, final_Ts, final_idx, (const float *)nullptr, 0.f, (float *)nullptr, deep, base,
-                     out_alpha, static_cast<unsigned *>(zero_ptr), (unsigned)(zero_bytes >> 2), 0, (int *)nullptr, 0);
-  GSR_CHECK_LAUNCH("rasterize_forward(tile16)");
-  return GSR_OK;
+  if (block_width != 16) {
+    GSR_REQUIRE(out_alpha == nullptr && zero_ptr == nullptr,
+                "rasterize_forward_ex: out_alpha / zero_ptr need block_width 16");
+    return gsr_rasterize_forward_nd(tiles_x, tiles_y, block_width, img_width, img_height, 3, gaussian_ids_sorted,
+                                    tile_bins, xys, conics, colors, opacities, background, out_img, final_Ts, final_idx,
+                                    stream);
+  }
+  Fwd16 a = {tiles_x, tiles_y, img_width, img_height, gaussian_ids_sorted, tile_bins, xys, conics, colors,
+             opacities, background, out_img, final_Ts, final_idx, deep_tile_threshold};
+  a.out_alpha = out_alpha, a.zero_ptr = zero_ptr, a.zero_bytes = zero_bytes;
+  return launch_tile16_forward("rasterize_forward", a, (hipStream_t)stream);
 }
 
 GSR_EXPORT size_t gsr_rasterize_forward_seg_workspace_bytes(unsigned img_height, unsigned img_width, int segments) {
@@ -834,70 +906,21 @@ GSR_EXPORT int gsr_rasterize_forward_seg(int tiles_x, int tiles_y, unsigned img_
                                          int32_t *final_idx, int deep_tile_threshold, float *out_alpha, void *zero_ptr,
                                          size_t zero_bytes, int segments, int segment_min_entries, void *workspace,
                                          size_t workspace_bytes, gsr_stream_t stream) {
-  if (segments < 2 || deep_tile_threshold <= 0) {
-    if (extra)
-      return gsr_rasterize_forward_rgbd(tiles_x, tiles_y, img_width, img_height, gaussian_ids_sorted, tile_bins, xys,
-                                        conics, colors, extra, opacities, background, extra_background, out_img,
-                                        out_extra, final_Ts, final_idx, deep_tile_threshold, out_alpha, zero_ptr,
-                                        zero_bytes, stream);
-    return gsr_rasterize_forward_ex(tiles_x, tiles_y, 16, img_width, img_height, gaussian_ids_sorted, tile_bins, xys,
-                                    conics, colors, opacities, background, out_img, final_Ts, final_idx,
-                                    deep_tile_threshold, out_alpha, zero_ptr, zero_bytes, stream);
+  Fwd16 a = {tiles_x, tiles_y, img_width, img_height, gaussian_ids_sorted, tile_bins, xys, conics, colors,
+             opacities, background, out_img, final_Ts, final_idx, deep_tile_threshold};
+  a.extra = extra, a.extra_background = extra_background, a.out_alpha = out_alpha;
+  a.zero_ptr = zero_ptr, a.zero_bytes = zero_bytes;
+  if (segments < 2 || deep_tile_threshold <= 0) {  // nothing to cut: the walk of _ex / _rgbd
+    a.out_extra = extra ? out_extra : nullptr;     // (_ex has no such argument: ignored without `extra`)
+    return launch_tile16_forward("rasterize_forward_seg", a, (hipStream_t)stream);
   }
-  int rc = check_common("rasterize_forward_seg", tiles_x, tiles_y, 16, img_width, img_height, 3);
-  if (rc != GSR_OK) return rc;
-  GSR_REQUIRE(gaussian_ids_sorted && tile_bins && xys && conics && colors && opacities && background && out_img &&
-                  final_Ts && final_idx,
-              "rasterize_forward_seg: null pointer");
-  GSR_REQUIRE((extra == nullptr) == (out_extra == nullptr), "rasterize_forward_seg: extra and out_extra go together");
   GSR_REQUIRE(segments <= 16, "rasterize_forward_seg: at most 16 segments");
-  GSR_REQUIRE(zero_ptr == nullptr || ((zero_bytes & 3) == 0 && (reinterpret_cast<uintptr_t>(zero_ptr) & 3) == 0 &&
-                                      zero_bytes < ((size_t)1 << 34)),
-              "rasterize_forward_seg: zero_ptr / zero_bytes must be multiples of 4 (and below 16 GB)");
   GSR_REQUIRE(workspace && workspace_bytes >= gsr_rasterize_forward_seg_workspace_bytes(img_height, img_width, segments) &&
                   (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
               "rasterize_forward_seg: workspace too small or not 16-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  const int num_tiles = tiles_x * tiles_y;
-  const unsigned base = gsr_xcd_grid(tiles_x, tiles_y);
-  const size_t px = (size_t)img_height * img_width;
-  const int deep_arg = gsr_prepare_jobs(deep_tile_threshold, tiles_x, tiles_y, tile_bins, s);  // (threshold | order flag)
-  deep_tile_threshold = gsr_deep_threshold(deep_tile_threshold);
-  const int seg_min = segment_min_entries > deep_tile_threshold ? segment_min_entries : deep_tile_threshold;
-  char *ws = static_cast<char *>(workspace);
-  float4 *raw = reinterpret_cast<float4 *>(ws);
-  int *lastp = reinterpret_cast<int *>(ws + (size_t)segments * px * 16);
-  float *extrap = reinterpret_cast<float *>(lastp + (size_t)segments * px);  // (written and read with `extra` only)
-  int *kstarp = reinterpret_cast<int *>(extrap + (size_t)segments * px);
-  int *flagsp = kstarp + px;
-  float *marksp = reinterpret_cast<float *>(flagsp + 4 * (size_t)num_tiles);
-  hipLaunchKernelGGL(seg_marks_clear_kernel, dim3((unsigned)((64 * (size_t)num_tiles + 255) / 256)), dim3(256), 0, s, marksp,
-                     64u * (unsigned)num_tiles);
-#define GSR_LAUNCH_FWD_SEG(RGBD_)                                                                                       \
-  hipLaunchKernelGGL((raster_fwd_tile16_kernel<RGBD_, true>), dim3((unsigned)segments * 4u * base), dim3(64), 0, s,      \
-                     tiles_x, num_tiles, (int)img_width, (int)img_height, gaussian_ids_sorted,                          \
-                     reinterpret_cast<const int2 *>(tile_bins), reinterpret_cast<const float2 *>(xys), conics, colors,   \
-                     opacities, background, out_img, final_Ts, final_idx, extra, extra_background, out_extra,           \
-                     deep_arg, base, out_alpha, static_cast<unsigned *>(zero_ptr),                                       \
-                     (unsigned)(zero_bytes >> 2), 0, (int *)nullptr, 0, segments, seg_min, raw, lastp, extrap, marksp);  \
-  hipLaunchKernelGGL(raster_fwd_segresolve_kernel<RGBD_>, dim3(4u * base), dim3(64), 0, s, tiles_x, num_tiles,          \
-                     (int)img_width, (int)img_height, reinterpret_cast<const int2 *>(tile_bins), background, out_img,    \
-                     final_Ts, final_idx, extra_background, out_extra, deep_arg, base, out_alpha, segments, seg_min,    \
-                     raw, lastp, extrap, kstarp, flagsp);                                                                \
-  hipLaunchKernelGGL(raster_fwd_segrewalk_kernel<RGBD_>, dim3((unsigned)segments * 4u * base), dim3(64), 0, s,          \
-                     tiles_x, num_tiles, (int)img_width, (int)img_height, gaussian_ids_sorted,                          \
-                     reinterpret_cast<const int2 *>(tile_bins), reinterpret_cast<const float2 *>(xys), conics, colors,   \
-                     opacities, background, out_img, final_Ts, final_idx, extra, extra_background, out_extra, deep_arg, \
-                     base, out_alpha, segments, seg_min, (const float4 *)raw, (const int *)lastp,                       \
-                     (const float *)extrap, (const int *)kstarp, (const int *)flagsp)
-  if (extra) {
-    GSR_LAUNCH_FWD_SEG(true);
-  } else {
-    GSR_LAUNCH_FWD_SEG(false);
-  }
-#undef GSR_LAUNCH_FWD_SEG
-  GSR_CHECK_LAUNCH("rasterize_forward_seg");
-  return GSR_OK;
+  a.out_extra = out_extra;
+  a.segments = segments, a.segment_min_entries = segment_min_entries, a.workspace = workspace;
+  return launch_tile16_forward("rasterize_forward_seg", a, (hipStream_t)stream);
 }
 
 GSR_EXPORT int gsr_rasterize_forward_scan(int tiles_x, int tiles_y, unsigned img_width, unsigned img_height,
@@ -928,25 +951,12 @@ GSR_EXPORT int gsr_rasterize_forward_rgbd(int tiles_x, int tiles_y, unsigned img
                                           float *out_extra, float *final_Ts, int32_t *final_idx,
                                           int deep_tile_threshold, float *out_alpha, void *zero_ptr,
                                           size_t zero_bytes, gsr_stream_t stream) {
-  int rc = check_common("rasterize_forward_rgbd", tiles_x, tiles_y, 16, img_width, img_height, 3);
-  if (rc != GSR_OK) return rc;
-  GSR_REQUIRE(gaussian_ids_sorted && tile_bins && xys && conics && colors && extra && opacities && background &&
-                  out_img && out_extra && final_Ts && final_idx,
-              "rasterize_forward_rgbd: null pointer");
-  GSR_REQUIRE(zero_ptr == nullptr || ((zero_bytes & 3) == 0 && (reinterpret_cast<uintptr_t>(zero_ptr) & 3) == 0 &&
-                                      zero_bytes < ((size_t)1 << 34)),
-              "rasterize_forward_rgbd: zero_ptr / zero_bytes must be multiples of 4 (and below 16 GB)");
-  const int num_tiles = tiles_x * tiles_y;
-  const unsigned base = gsr_xcd_grid(tiles_x, num_tiles / tiles_x);
-  const int deep = gsr_prepare_jobs(deep_tile_threshold, tiles_x, tiles_y, tile_bins, (hipStream_t)stream);
-  hipLaunchKernelGGL(raster_fwd_tile16_kernel<true>, dim3(deep ? 4 * base : base), dim3(64), 0,
-                     (hipStream_t)stream, tiles_x, num_tiles, (int)img_width, (int)img_height, gaussian_ids_sorted,
-                     reinterpret_cast<const int2 *>(tile_bins),
-                     reinterpret_cast<const float2 *>(xys), conics, colors, opacities, background,
-                     out_img, final_Ts, final_idx, extra, extra_background, out_extra, deep, base,
-                     out_alpha, static_cast<unsigned *>(zero_ptr), (unsigned)(zero_bytes >> 2), 0, (int *)nullptr, 0);
-  GSR_CHECK_LAUNCH("rasterize_forward_rgbd");
-  return GSR_OK;
+  GSR_REQUIRE(extra, "rasterize_forward_rgbd: null pointer");
+  Fwd16 a = {tiles_x, tiles_y, img_width, img_height, gaussian_ids_sorted, tile_bins, xys, conics, colors,
+             opacities, background, out_img, final_Ts, final_idx, deep_tile_threshold};
+  a.extra = extra, a.extra_background = extra_background, a.out_extra = out_extra, a.out_alpha = out_alpha;
+  a.zero_ptr = zero_ptr, a.zero_bytes = zero_bytes;
+  return launch_tile16_forward("rasterize_forward_rgbd", a, (hipStream_t)stream);
 }
 
 GSR_EXPORT int gsr_rasterize_forward_round(int round, int tiles_x, int tiles_y, unsigned img_width,
@@ -957,36 +967,16 @@ GSR_EXPORT int gsr_rasterize_forward_round(int round, int tiles_x, int tiles_y, 
                                            float *out_img, float *out_extra, float *final_Ts, int32_t *final_idx,
                                            int32_t *tile_flags, int deep_tile_threshold, float *out_alpha,
                                            void *zero_ptr, size_t zero_bytes, gsr_stream_t stream) {
-  int rc = check_common("rasterize_forward_round", tiles_x, tiles_y, 16, img_width, img_height, 3);
-  if (rc != GSR_OK) return rc;
   GSR_REQUIRE(round == 1 || round == 2, "rasterize_forward_round: round must be 1 or 2");
-  GSR_REQUIRE(gaussian_ids_sorted && tile_bins && xys && conics && colors && opacities && background && out_img &&
-                  final_Ts && final_idx,
-              "rasterize_forward_round: null pointer");
-  GSR_REQUIRE((extra == nullptr) == (out_extra == nullptr), "rasterize_forward_round: extra and out_extra go together");
   GSR_REQUIRE(tile_flags != nullptr, "rasterize_forward_round: tile_flags is required");
   GSR_REQUIRE(idx_base >= 0, "rasterize_forward_round: idx_base < 0");
-  GSR_REQUIRE(zero_ptr == nullptr || ((zero_bytes & 3) == 0 && (reinterpret_cast<uintptr_t>(zero_ptr) & 3) == 0 &&
-                                      zero_bytes < ((size_t)1 << 34)),
-              "rasterize_forward_round: zero_ptr / zero_bytes must be multiples of 4 (and below 16 GB)");
-  const int num_tiles = tiles_x * tiles_y;
-  const unsigned base = gsr_xcd_grid(tiles_x, tiles_y);
-  const int deep = gsr_deep_threshold(deep_tile_threshold);  // (two-round lists: the static block order)
-  const dim3 grd(deep ? 4 * base : base), blk(64);
-  if (extra)
-    hipLaunchKernelGGL(raster_fwd_tile16_kernel<true>, grd, blk, 0, (hipStream_t)stream, tiles_x, num_tiles,
-                       (int)img_width, (int)img_height, gaussian_ids_sorted, reinterpret_cast<const int2 *>(tile_bins),
-                       reinterpret_cast<const float2 *>(xys), conics, colors, opacities, background, out_img, final_Ts,
-                       final_idx, extra, extra_background, out_extra, deep, base, out_alpha,
-                       static_cast<unsigned *>(zero_ptr), (unsigned)(zero_bytes >> 2), round, tile_flags, idx_base);
-  else
-    hipLaunchKernelGGL(raster_fwd_tile16_kernel<false>, grd, blk, 0, (hipStream_t)stream, tiles_x, num_tiles,
-                       (int)img_width, (int)img_height, gaussian_ids_sorted, reinterpret_cast<const int2 *>(tile_bins),
-                       reinterpret_cast<const float2 *>(xys), conics, colors, opacities, background, out_img, final_Ts,
-                       final_idx, (const float *)nullptr, 0.f, (float *)nullptr, deep, base, out_alpha,
-                       static_cast<unsigned *>(zero_ptr), (unsigned)(zero_bytes >> 2), round, tile_flags, idx_base);
-  GSR_CHECK_LAUNCH("rasterize_forward_round");
-  return GSR_OK;
+  Fwd16 a = {tiles_x, tiles_y, img_width, img_height, gaussian_ids_sorted, tile_bins, xys, conics, colors,
+             opacities, background, out_img, final_Ts, final_idx, deep_tile_threshold};
+  a.static_order = true;  // (two-round lists: no job order behind either tile_bins)
+  a.extra = extra, a.extra_background = extra_background, a.out_extra = out_extra, a.out_alpha = out_alpha;
+  a.zero_ptr = zero_ptr, a.zero_bytes = zero_bytes;
+  a.round = round, a.tile_flags = tile_flags, a.idx_base = idx_base;
+  return launch_tile16_forward("rasterize_forward_round", a, (hipStream_t)stream);
 }
 
 GSR_EXPORT size_t gsr_tile_jobs_ints(int tiles_x, int tiles_y) {

@@ -512,16 +512,10 @@ def rasterize_backward_two(img_height, img_width, gaussian_ids_sorted, tile_bins
     if extra is not None:
         v_output_extra = _check(v_output_extra.contiguous(), "v_output_extra", _f32)
     n = xys.size(0)
-    k = 10 if extra is not None else 9
     dev = xys.device
     with _on(dev):
         zeroed = accumulators is not None
-        if zeroed and (accumulators.numel() != n * k or accumulators.dtype != _f32 or not accumulators.is_contiguous()):
-            raise RuntimeError("rasterize_backward_two: accumulators must be backward_accumulators(n, 3 or 4, device)")
-        flat = accumulators if zeroed else torch.empty((n * k,), dtype=_f32, device=dev)
-        v_xy, v_conic = flat[: 2 * n].view(n, 2), flat[2 * n: 5 * n].view(n, 3)
-        v_colors, v_opacity = flat[5 * n: 8 * n].view(n, 3), flat[8 * n: 9 * n].view(n, 1)
-        v_extra = flat[9 * n:] if extra is not None else None
+        v_xy, v_conic, v_colors, v_opacity, v_extra = _carve_accumulators(accumulators, n, 3, extra is not None, dev)
         nt = ((img_width + 15) // 16) * ((img_height + 15) // 16)
         _call("gsr_rasterize_backward_two", C.c_uint(img_height), C.c_uint(img_width), C.c_int(n),
               _ptr(gaussian_ids_sorted), _ptr(tile_bins), _ptr(tile_bins2), C.c_int(int(idx_base2)), _ptr(xys),
@@ -554,7 +548,7 @@ def _raster_inputs(gaussian_ids_sorted, tile_bins, xys, conics, colors, opacitie
 def depth_segments(list_entries: int, num_tiles: int):
     """-> (segments, minimum entries) for ``gsr_rasterize_forward_seg`` / ``gsr_rasterize_backward_seg``: into how many
     runs the lists of the tiles that are split over four waves are cut, each run walked by its own waves (DESIGN.md
-    4.16).  Only tile grids that cannot fill the chip gain: 16 runs (`depth_segments` in _tuning.py; 1 = off) on grids of up to
+    4.3; docs/history/DESIGN_r01-r05.md 4.16).  Only tile grids that cannot fill the chip gain: 16 runs (`depth_segments` in _tuning.py; 1 = off) on grids of up to
     `depth_segments_grid` = 1 100 tiles (the grids on which forward and backward split every tile), for lists of more
     than `depth_segments_min` = 512 entries.  Measured (tools/exp/seg_ab.py, profiles/r04_depth_segments.txt):
     300 k Gaussians of the trainer's object scene at 480 x 270, compositing backward 436 -> 263 us with 8 runs
@@ -668,7 +662,7 @@ def deep_arg(tile_bins: Optional[Tensor], list_entries: int, num_tiles: int, bac
     """The `deep_tile_threshold` argument of a compositing entry: the threshold (`deep_tile_threshold`), with
     GSR_DEEP_ORDERED set when `tile_bins` came from `alloc_tile_bins` (so the job order fits behind it), the grid
     is not a small one and `deep_order` is not 0 -- the entry then runs the launch's jobs longest first (DESIGN.md
-    section 4.18)."""
+    section 4.1; docs/history/DESIGN_r01-r05.md section 4.18)."""
     deep = deep_tile_threshold(list_entries, num_tiles, backward) if backward else deep_tile_threshold(list_entries, num_tiles)
     if deep <= 0 or tile_bins is None or tile_bounds is None or not _order_knob():
         return deep
@@ -876,26 +870,39 @@ def rasterize_gaussians_forward(xys, depths, radii, conics, colors, opacities, b
     return ids, bins, img, Ts, idx, alpha
 
 
+def _composite16_forward(tile_bounds, W: int, H: int, gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities,
+                         background, out_img, final_Ts, final_idx, dev, *, extra=None, extra_background: float = 0.0,
+                         out_extra=None, alpha=None, zero=None, deep: Optional[int] = None) -> None:
+    """The one call of ``gsr_rasterize_forward_seg`` -- the 16-px, 3-channel compositing forward, with or without the
+    ``extra`` channel, into the caller's outputs.  The entry cuts the deep lists into the runs of
+    :func:`_forward_segments` where that gives any, and is ``gsr_rasterize_forward_ex`` / ``_rgbd`` where not.
+    ``deep``: the deep argument (default: :func:`forward_orders`); ``zero``: a float32 tensor the launch clears."""
+    entries, tiles = gaussian_ids_sorted.numel(), tile_bounds[0] * tile_bounds[1]
+    if deep is None:
+        deep = forward_orders(tile_bins, entries, tiles, tile_bounds, dev)
+    segs, seg_min, seg_ws = _forward_segments(entries, tiles, H, W, dev)
+    zero_bytes = zero.numel() * 4 if zero is not None else 0
+    _call("gsr_rasterize_forward_seg", C.c_int(tile_bounds[0]), C.c_int(tile_bounds[1]), C.c_uint(W), C.c_uint(H),
+          _ptr(gaussian_ids_sorted), _ptr(tile_bins), _ptr(xys), _ptr(conics), _ptr(colors),
+          _ptr(extra) if extra is not None else None, _ptr(opacities), _ptr(background), C.c_float(extra_background),
+          _ptr(out_img), _ptr(out_extra) if out_extra is not None else None, _ptr(final_Ts), _ptr(final_idx),
+          C.c_int(deep), _ptr(alpha) if alpha is not None else None, _ptr(zero) if zero_bytes else None,
+          C.c_size_t(zero_bytes), C.c_int(segs), C.c_int(seg_min), _ptr(seg_ws) if seg_ws is not None else None,
+          C.c_size_t(seg_ws.numel() if seg_ws is not None else 0), _stream(dev))
+
+
 def composite_prepared(tile_bounds, img_width: int, img_height: int, gaussian_ids_sorted, tile_bins, xys, conics, colors,
                        opacities, background, out_img, planes, want_alpha: bool, zero=None):
-    """``gsr_rasterize_forward_ex`` into caller-owned outputs, for callers that have validated their tensors and
+    """The 16-px compositing forward into caller-owned outputs, for callers that have validated their tensors and
     allocated ``out_img`` [H,W,3] and ``planes`` [3,H,W] (final_Ts | final_idx as int32 | alpha) ahead of time: the
     shortest host path to the compositing launch (rasterize.py, "lists built ahead of time")
     -> (out_img, final_Ts, final_idx, alpha or None)."""
     dev = xys.device
     Ts, idx = planes[0], planes[1].view(_i32)
     alpha = planes[2] if want_alpha else None
-    zero_bytes = zero.numel() * 4 if zero is not None else 0
     with _on(dev):
-        tiles = tile_bounds[0] * tile_bounds[1]
-        segs, seg_min, seg_ws = _forward_segments(gaussian_ids_sorted.numel(), tiles, int(img_height), int(img_width), dev)
-        _call("gsr_rasterize_forward_seg", C.c_int(tile_bounds[0]), C.c_int(tile_bounds[1]),
-              C.c_uint(int(img_width)), C.c_uint(int(img_height)), _ptr(gaussian_ids_sorted), _ptr(tile_bins), _ptr(xys),
-              _ptr(conics), _ptr(colors), None, _ptr(opacities), _ptr(background), C.c_float(0.0), _ptr(out_img), None,
-              _ptr(Ts), _ptr(idx), C.c_int(forward_orders(tile_bins, gaussian_ids_sorted.numel(), tiles, tile_bounds, dev)),
-              _ptr(alpha) if alpha is not None else None, _ptr(zero) if zero_bytes else None, C.c_size_t(zero_bytes),
-              C.c_int(segs), C.c_int(seg_min), _ptr(seg_ws) if seg_ws is not None else None,
-              C.c_size_t(seg_ws.numel() if seg_ws is not None else 0), _stream(dev))
+        _composite16_forward(tile_bounds, int(img_width), int(img_height), gaussian_ids_sorted, tile_bins, xys, conics,
+                             colors, opacities, background, out_img, Ts, idx, dev, alpha=alpha, zero=zero)
     return out_img, Ts, idx, alpha
 
 
@@ -919,37 +926,28 @@ def _rasterize_forward(tile_bounds, block, img_size, gaussian_ids_sorted, tile_b
         out_img = torch.empty((H, W, channels), dtype=_f32, device=dev)
         final_Ts = torch.empty((H, W), dtype=_f32, device=dev)
         final_idx = torch.empty((H, W), dtype=_i32, device=dev)
-        head = (C.c_int(tile_bounds[0]), C.c_int(tile_bounds[1]), C.c_uint(block[0]), C.c_uint(W),
-                C.c_uint(H))
-        tail = (_ptr(gaussian_ids_sorted), _ptr(tile_bins), _ptr(xys), _ptr(conics), _ptr(colors),
-                _ptr(opacities), _ptr(background), _ptr(out_img), _ptr(final_Ts), _ptr(final_idx))
-        if nd:
-            _call("gsr_rasterize_forward_nd", *head, C.c_uint(channels), *tail, _stream(dev))
+        if not nd and channels != 3:
+            raise RuntimeError("rasterize_forward expects 3 channels; use nd_rasterize_forward")
+        alpha = None
+        if ex:
+            if zero is not None and _check(zero, "zero", _f32).numel() == 0:
+                zero = None
+            alpha = torch.empty((H, W), dtype=_f32, device=dev) if want_alpha else None
+        if not nd and block[0] == 16:
+            _composite16_forward(tile_bounds, W, H, gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities,
+                                 background, out_img, final_Ts, final_idx, dev, alpha=alpha, zero=zero if ex else None)
         else:
-            if channels != 3:
-                raise RuntimeError("rasterize_forward expects 3 channels; use nd_rasterize_forward")
-            deep = forward_orders(tile_bins, gaussian_ids_sorted.numel(), tile_bounds[0] * tile_bounds[1], tile_bounds, dev) \
-                if block[0] == 16 else deep_tile_threshold(gaussian_ids_sorted.numel(), tile_bounds[0] * tile_bounds[1])
-            segs, seg_min, seg_ws = _forward_segments(gaussian_ids_sorted.numel(), tile_bounds[0] * tile_bounds[1], H, W,
-                                                      dev) if block[0] == 16 else (0, 0, None)
-            if ex or segs > 1:
-                if zero is not None:
-                    _check(zero, "zero", _f32)
-                    if zero.numel() == 0:
-                        zero = None
-                alpha = torch.empty((H, W), dtype=_f32, device=dev) if want_alpha else None
-                tail_ex = (C.c_int(deep), _ptr(alpha) if alpha is not None else None,
-                           _ptr(zero) if zero is not None else None,
-                           C.c_size_t(zero.numel() * 4 if zero is not None else 0))
-                if segs > 1:
-                    _call("gsr_rasterize_forward_seg", head[0], head[1], head[3], head[4], *tail[:5], None, *tail[5:7],
-                          C.c_float(0.0), tail[7], None, *tail[8:], *tail_ex, C.c_int(segs), C.c_int(seg_min),
-                          _ptr(seg_ws), C.c_size_t(seg_ws.numel()), _stream(dev))
-                else:
-                    _call("gsr_rasterize_forward_ex", *head, *tail, *tail_ex, _stream(dev))
-                return (out_img, final_Ts, final_idx, alpha) if ex else (out_img, final_Ts, final_idx)
-            _call("gsr_rasterize_forward", *head, *tail, C.c_int(deep), _stream(dev))
-    return out_img, final_Ts, final_idx
+            if alpha is not None or (ex and zero is not None):  # (the generic kernel writes neither)
+                raise RuntimeError("rasterize_forward_ex: out_alpha / zero_ptr need block_width 16")
+            sizes = (C.c_int(tile_bounds[0]), C.c_int(tile_bounds[1]), C.c_uint(block[0]), C.c_uint(W), C.c_uint(H))
+            args = (_ptr(gaussian_ids_sorted), _ptr(tile_bins), _ptr(xys), _ptr(conics), _ptr(colors), _ptr(opacities),
+                    _ptr(background), _ptr(out_img), _ptr(final_Ts), _ptr(final_idx))
+            if nd:
+                _call("gsr_rasterize_forward_nd", *sizes, C.c_uint(channels), *args, _stream(dev))
+            else:
+                deep = deep_tile_threshold(gaussian_ids_sorted.numel(), tile_bounds[0] * tile_bounds[1])
+                _call("gsr_rasterize_forward", *sizes, *args, C.c_int(deep), _stream(dev))
+    return (out_img, final_Ts, final_idx, alpha) if ex else (out_img, final_Ts, final_idx)
 
 
 def rasterize_forward(tile_bounds, block, img_size, gaussian_ids_sorted, tile_bins, xys, conics,
@@ -1005,16 +1003,9 @@ def rasterize_forward_rgbd(tile_bounds, img_size, gaussian_ids_sorted, tile_bins
         alpha = torch.empty((H, W), dtype=_f32, device=dev) if want_alpha else None
         if zero is not None:
             _check(zero, "zero", _f32)
-        segs, seg_min, seg_ws = _forward_segments(gaussian_ids_sorted.numel(), tile_bounds[0] * tile_bounds[1], H, W, dev)
-        _call("gsr_rasterize_forward_seg", C.c_int(tile_bounds[0]), C.c_int(tile_bounds[1]), C.c_uint(W),
-              C.c_uint(H), _ptr(gaussian_ids_sorted), _ptr(tile_bins), _ptr(xys), _ptr(conics), _ptr(colors),
-              _ptr(extra), _ptr(opacities), _ptr(background), C.c_float(extra_background), _ptr(img), _ptr(ext),
-              _ptr(Ts), _ptr(idx),
-              C.c_int(forward_orders(tile_bins, gaussian_ids_sorted.numel(), tile_bounds[0] * tile_bounds[1], tile_bounds, dev)),
-              _ptr(alpha) if alpha is not None else None, _ptr(zero) if zero is not None else None,
-              C.c_size_t(zero.numel() * 4 if zero is not None else 0), C.c_int(segs), C.c_int(seg_min),
-              _ptr(seg_ws) if seg_ws is not None else None, C.c_size_t(seg_ws.numel() if seg_ws is not None else 0),
-              _stream(dev))
+        _composite16_forward(tile_bounds, W, H, gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, background,
+                             img, Ts, idx, dev, extra=extra, extra_background=extra_background, out_extra=ext, alpha=alpha,
+                             zero=zero)
     if want_alpha:
         return img, ext, Ts, idx, alpha
     return img, ext, Ts, idx
@@ -1034,26 +1025,11 @@ def rasterize_backward_rgbd(img_height, img_width, gaussian_ids_sorted, tile_bin
     n = xys.size(0)
     dev = xys.device
     with _on(dev):
-        if accumulators is not None and (accumulators.numel() != n * 10 or accumulators.dtype != _f32 or
-                                         not accumulators.is_contiguous()):
-            raise RuntimeError("rasterize_backward_rgbd: accumulators must be backward_accumulators(n, 4, device)")
-        flat = accumulators if accumulators is not None else torch.empty((n * 10,), dtype=_f32, device=dev)
-        v_xy, v_conic = flat[: 2 * n].view(n, 2), flat[2 * n: 5 * n].view(n, 3)
-        v_colors, v_opacity = flat[5 * n: 8 * n].view(n, 3), flat[8 * n: 9 * n].view(n, 1)
-        v_extra = flat[9 * n:]
-        tiles = ((img_width + 15) // 16) * ((img_height + 15) // 16)
-        segs, seg_min = depth_segments(gaussian_ids_sorted.numel(), tiles)
-        ws = torch.empty(((segs - 1) * int(img_height) * int(img_width), 2), dtype=_f32, device=dev) if segs > 1 else None
-        _call("gsr_rasterize_backward_seg", C.c_uint(img_height), C.c_uint(img_width), C.c_int(n),
-              _ptr(gaussian_ids_sorted), _ptr(tile_bins), _ptr(xys), _ptr(conics), _ptr(colors), _ptr(extra),
-              _ptr(opacities), _ptr(background), C.c_float(extra_background), _ptr(final_Ts), _ptr(final_idx),
-              _ptr(v_output), _ptr(v_output_extra),
-              _ptr(v_output_alpha) if v_output_alpha is not None else None, _ptr(v_xy), _ptr(v_conic),
-              _ptr(v_colors), _ptr(v_extra), _ptr(v_opacity),
-              C.c_int(backward_order(tile_bins, gaussian_ids_sorted.numel(), tiles,
-                                     ((int(img_width) + 15) // 16, (int(img_height) + 15) // 16))),
-              C.c_int(1 if accumulators is not None else 0), C.c_int(segs if ws is not None else 0), C.c_int(seg_min),
-              _ptr(ws) if ws is not None else None, C.c_size_t(ws.numel() * 4 if ws is not None else 0), _stream(dev))
+        v_xy, v_conic, v_colors, v_opacity, v_extra = _carve_accumulators(accumulators, n, 3, True, dev)
+        _composite16_backward(img_height, img_width, n, gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities,
+                              background, final_Ts, final_idx, v_output, v_output_alpha, v_xy, v_conic, v_colors,
+                              v_opacity, accumulators is not None, dev, extra=extra, extra_background=extra_background,
+                              v_output_extra=v_output_extra, v_extra=v_extra)
     return v_xy, v_conic, v_colors, v_extra, v_opacity
 
 
@@ -1107,6 +1083,41 @@ def backward_accumulators(n: int, channels: int, device) -> Tensor:
         return torch.empty((n * (6 + channels),), dtype=_f32, device=device)
 
 
+def _carve_accumulators(flat: Optional[Tensor], n: int, channels: int, with_extra: bool, dev):
+    """-> (v_xy [n,2], v_conic [n,3], v_colors [n,channels], v_opacity [n,1], v_extra [n] or None): views of ONE
+    allocation, back to back (the library clears them with one fill) -- of ``flat``, a :func:`backward_accumulators`
+    buffer the forward launch has already cleared, or of a new one."""
+    k = 6 + channels + (1 if with_extra else 0)
+    if flat is None:
+        flat = torch.empty((n * k,), dtype=_f32, device=dev)
+    elif flat.numel() != n * k or flat.dtype != _f32 or not flat.is_contiguous():
+        raise RuntimeError(f"accumulators must be backward_accumulators(n, {k - 6}, device)")
+    v_opacity = flat[(5 + channels) * n: (6 + channels) * n].view(n, 1)
+    return (flat[: 2 * n].view(n, 2), flat[2 * n: 5 * n].view(n, 3), flat[5 * n: (5 + channels) * n].view(n, channels),
+            v_opacity, flat[(6 + channels) * n:] if with_extra else None)
+
+
+def _composite16_backward(img_height, img_width, n: int, gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities,
+                          background, final_Ts, final_idx, v_output, v_output_alpha, v_xy, v_conic, v_colors, v_opacity,
+                          zeroed: bool, dev, *, extra=None, extra_background: float = 0.0, v_output_extra=None,
+                          v_extra=None) -> None:
+    """The one call of ``gsr_rasterize_backward_seg`` -- the 16-px, 3-channel compositing backward, with or without
+    the ``extra`` channel.  The entry cuts the deep lists into the runs of :func:`depth_segments` where that gives any,
+    and is ``gsr_rasterize_backward_ex`` / ``_rgbd`` where not.  ``zeroed``: the accumulators are cleared already."""
+    _o = lambda t: None if t is None else _ptr(t)  # noqa: E731
+    tb = ((int(img_width) + 15) // 16, (int(img_height) + 15) // 16)
+    entries, tiles = gaussian_ids_sorted.numel(), tb[0] * tb[1]
+    segs, seg_min = depth_segments(entries, tiles)
+    ws = torch.empty(((segs - 1) * int(img_height) * int(img_width), 2), dtype=_f32, device=dev) if segs > 1 else None
+    _call("gsr_rasterize_backward_seg", C.c_uint(img_height), C.c_uint(img_width), C.c_int(n),
+          _ptr(gaussian_ids_sorted), _ptr(tile_bins), _ptr(xys), _ptr(conics), _ptr(colors), _o(extra), _ptr(opacities),
+          _ptr(background), C.c_float(extra_background), _ptr(final_Ts), _ptr(final_idx), _ptr(v_output),
+          _o(v_output_extra), _o(v_output_alpha), _ptr(v_xy), _ptr(v_conic), _ptr(v_colors), _o(v_extra), _ptr(v_opacity),
+          C.c_int(backward_order(tile_bins, entries, tiles, tb)), C.c_int(1 if zeroed else 0),
+          C.c_int(segs if ws is not None else 0), C.c_int(seg_min), _o(ws),
+          C.c_size_t(ws.numel() * 4 if ws is not None else 0), _stream(dev))
+
+
 def _rasterize_backward(img_height, img_width, block_width, gaussian_ids_sorted, tile_bins, xys,
                         conics, colors, opacities, background, final_Ts, final_idx, v_output,
                         v_output_alpha, nd: bool, accumulators: Optional[Tensor] = None, trusted: bool = False):
@@ -1122,46 +1133,25 @@ def _rasterize_backward(img_height, img_width, block_width, gaussian_ids_sorted,
     n, channels = xys.size(0), colors.size(1)
     dev = xys.device
     with _on(dev):
-        # four contiguous tensors carved out of one allocation: the library
-        # zero-fills them with a single memset when they are back to back
-        zeroed = accumulators is not None and not nd and block_width == 16
-        if zeroed and (accumulators.numel() != n * (6 + channels) or accumulators.dtype != _f32 or
-                       not accumulators.is_contiguous()):
-            raise RuntimeError("rasterize_backward: accumulators must be backward_accumulators(n, channels, device)")
-        flat = accumulators if zeroed else torch.empty((n * (6 + channels),), dtype=_f32, device=dev)
-        v_xy = flat[: 2 * n].view(n, 2)
-        v_conic = flat[2 * n: 5 * n].view(n, 3)
-        v_colors = flat[5 * n: (5 + channels) * n].view(n, channels)
-        v_opacity = flat[(5 + channels) * n:].view(n, 1)
-        head = (C.c_uint(img_height), C.c_uint(img_width), C.c_uint(block_width))
-        tail = (C.c_int(n), _ptr(gaussian_ids_sorted), _ptr(tile_bins), _ptr(xys), _ptr(conics),
-                _ptr(colors), _ptr(opacities), _ptr(background), _ptr(final_Ts), _ptr(final_idx),
-                _ptr(v_output), _ptr(v_output_alpha) if v_output_alpha is not None else None, _ptr(v_xy), _ptr(v_conic), _ptr(v_colors),
-                _ptr(v_opacity))
-        if nd:
-            _call("gsr_rasterize_backward_nd", *head, C.c_uint(channels), *tail, _stream(dev))
+        tile16 = not nd and block_width == 16
+        zeroed = accumulators is not None and tile16  # (the generic kernels' entries clear for themselves)
+        v_xy, v_conic, v_colors, v_opacity, _ = _carve_accumulators(accumulators if zeroed else None, n, channels, False, dev)
+        if tile16:
+            _composite16_backward(img_height, img_width, n, gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities,
+                                  background, final_Ts, final_idx, v_output, v_output_alpha, v_xy, v_conic, v_colors,
+                                  v_opacity, zeroed, dev)
         else:
-            tiles = ((img_width + block_width - 1) // block_width) * ((img_height + block_width - 1) // block_width)
-            segs, seg_min = depth_segments(gaussian_ids_sorted.numel(), tiles) if block_width == 16 else (1, 0)
-            _tb16 = ((int(img_width) + 15) // 16, (int(img_height) + 15) // 16) if block_width == 16 else None
-            if segs > 1:
-                deep = backward_order(tile_bins, gaussian_ids_sorted.numel(), tiles,
-                                      ((int(img_width) + 15) // 16, (int(img_height) + 15) // 16))
-                ws = torch.empty(((segs - 1) * int(img_height) * int(img_width), 2), dtype=_f32, device=dev)
-                _call("gsr_rasterize_backward_seg", C.c_uint(img_height), C.c_uint(img_width), *tail[:6], None,
-                      *tail[6:8], C.c_float(0.0), *tail[8:11], None, *tail[11:15], None, tail[15], C.c_int(deep),
-                      C.c_int(1 if zeroed else 0), C.c_int(segs), C.c_int(seg_min), _ptr(ws),
-                      C.c_size_t(ws.numel() * 4), _stream(dev))
-            elif zeroed:
-                _call("gsr_rasterize_backward_ex", *head, *tail,
-                      C.c_int(backward_order(tile_bins, gaussian_ids_sorted.numel(), tiles, _tb16) if _tb16 else
-                              deep_tile_threshold(gaussian_ids_sorted.numel(), tiles, backward=True)),
-                      C.c_int(1), _stream(dev))
+            sizes = (C.c_uint(img_height), C.c_uint(img_width), C.c_uint(block_width))
+            args = (C.c_int(n), _ptr(gaussian_ids_sorted), _ptr(tile_bins), _ptr(xys), _ptr(conics), _ptr(colors),
+                    _ptr(opacities), _ptr(background), _ptr(final_Ts), _ptr(final_idx), _ptr(v_output),
+                    _ptr(v_output_alpha) if v_output_alpha is not None else None, _ptr(v_xy), _ptr(v_conic), _ptr(v_colors),
+                    _ptr(v_opacity))
+            if nd:
+                _call("gsr_rasterize_backward_nd", *sizes, C.c_uint(channels), *args, _stream(dev))
             else:
-                _call("gsr_rasterize_backward", *head, *tail,
-                      C.c_int(backward_order(tile_bins, gaussian_ids_sorted.numel(), tiles, _tb16) if _tb16 else
-                              deep_tile_threshold(gaussian_ids_sorted.numel(), tiles, backward=True)),
-                      _stream(dev))
+                tiles = ((img_width + block_width - 1) // block_width) * ((img_height + block_width - 1) // block_width)
+                _call("gsr_rasterize_backward", *sizes, *args,
+                      C.c_int(deep_tile_threshold(gaussian_ids_sorted.numel(), tiles, backward=True)), _stream(dev))
     return v_xy, v_conic, v_colors, v_opacity
 
 

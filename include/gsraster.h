@@ -359,7 +359,7 @@ int gsr_rasterize_backward_ex(unsigned img_height, unsigned img_width,
  * list twice).  For tile grids too small to fill the chip (the
  * 480 x 270 phase of the reference's coarse-to-fine schedule, vanilla_gs.py:48-53, is 510 tiles).  Results equal
  * gsr_rasterize_forward_ex's to rounding.  workspace: gsr_rasterize_forward_seg_workspace_bytes(...) bytes, 16-byte
- * aligned.  segments < 2 or deep_tile_threshold <= 0: gsr_rasterize_forward_ex. */
+ * aligned.  segments < 2 or deep_tile_threshold <= 0: the walk of gsr_rasterize_forward_ex (with `extra`: _rgbd). */
 size_t gsr_rasterize_forward_seg_workspace_bytes(unsigned img_height, unsigned img_width, int segments);
 /* extra / out_extra: NULL, or the fourth channel of gsr_rasterize_forward_rgbd ([n] / [P], over extra_background) */
 int gsr_rasterize_forward_seg(int tiles_x, int tiles_y, unsigned img_width, unsigned img_height,
@@ -379,7 +379,7 @@ int gsr_rasterize_forward_seg(int tiles_x, int tiles_y, unsigned img_width, unsi
  * independent.  For tile grids too small to fill the chip and for scenes whose deepest tiles set the kernel's
  * duration.  Results equal gsr_rasterize_backward_ex's to rounding (T reaches a run as a product of run products).
  * workspace: gsr_rasterize_backward_seg_workspace_bytes(img_height, img_width, segments) bytes, 8-byte aligned.
- * segments < 2 or deep_tile_threshold <= 0: gsr_rasterize_backward_ex. */
+ * segments < 2 or deep_tile_threshold <= 0: the walk of gsr_rasterize_backward_ex (with `extra`: _rgbd). */
 size_t gsr_rasterize_backward_seg_workspace_bytes(unsigned img_height, unsigned img_width, int segments);
 /* extra / v_output_extra / v_extra: NULL, or the fourth channel as in gsr_rasterize_backward_rgbd */
 int gsr_rasterize_backward_seg(unsigned img_height, unsigned img_width, int num_points,
@@ -558,7 +558,7 @@ int gsr_rasterize_backward_rgbd(unsigned img_height, unsigned img_width,
                                 float *v_opacity, int deep_tile_threshold,
                                 int accumulators_zeroed, gsr_stream_t stream);
 
-/* ---- two-round lists for deep scenes (block_width 16) --------------------
+/* ---- two-round lists for deep scenes (block_width 16; docs/history/DESIGN_r01-r05.md section 4.11) --------------------
  * replaces, like gsr_bin_sorted + gsr_rasterize_forward / _backward, the list construction of
  * rasterizer/utils.py:106-182 and the walks of forward.cu:278-395 / backward.cu:133-303 -- with the SAME
  * results: on a scene whose tiles saturate early (3 M Gaussians at 4K: 97.7 M list entries built, 4.1 M ever

@@ -1330,3 +1330,134 @@ def test_sh_backward_over_several_views(degree, deg_use, views):
     assert torch.equal(v_dc, joint[:, 0, :]) and torch.equal(v_rest, joint[:, 1:, :])
     if deg_use < degree:
         assert not joint[:, (deg_use + 1) ** 2:, :].any()  # bands above the warm-up degree: exact zeros
+
+
+def test_tile16_entries_route_equality():
+    """The 16-px entries of the C ABI that name the same walk reach the same kernel instantiation with the same
+    arguments (raster_fwd.hip / raster_bwd.hip: launch_tile16_forward / launch_tile16_backward): called directly
+    through the library, `gsr_rasterize_forward` = `_ex` with null extras = `_seg` with segments 0, and `_rgbd` = `_seg`
+    with `extra`, bit for bit (images, final_Ts, final_idx, extra plane, alpha, the cleared `zero` region); the
+    backwards `gsr_rasterize_backward` (clearing for itself) = `_ex` on accumulators the forward cleared = `_seg`
+    with segments 0, and the rgbd pair, to the gradient tolerance (float atomics: 1e-3 relative, DESIGN.md section 2);
+    `gsr_rasterize_backward_det` twice, bit for bit (its partial-row arguments).  Whole-tile walk (deep_tile_threshold
+    0) and split tiles (128).  72 x 40: 5 x 3 tiles, both edges partial; one tile's list beyond 512 entries, one
+    below 64."""
+    import ctypes as ct
+
+    import rasterizer.cuda as C
+    from rasterizer.cuda._backend import lib
+
+    L = lib()
+    W, H, n, bw = 72, 40, 2000, 16
+    tb = ((W + bw - 1) // bw, (H + bw - 1) // bw, 1)
+    rng = np.random.default_rng(14)
+    dense = 1700  # centres inside tile (1, 0); the rest thin over the image (the 8 x 8 corner tile sees a handful)
+    xys = np.concatenate([rng.uniform((18, 2), (30, 14), (dense, 2)), rng.uniform((0, 0), (W, H), (n - dense, 2))])
+    sigma = rng.uniform(0.8, 1.5, n)
+    conics = np.stack([1 / sigma ** 2, np.zeros(n), 1 / sigma ** 2], 1)
+    f32 = lambda a: cu(np.asarray(a, np.float32))  # noqa: E731
+    g = dict(xys=f32(xys), conics=f32(conics), radii=cu(np.ceil(3 * sigma).astype(np.int32)),
+             depths=f32(rng.uniform(1, 10, n)), opac=f32(rng.uniform(0.02, 0.3, (n, 1))),
+             colors=f32(rng.uniform(0, 1, (n, 3))), bg=cu(np.array(S.BACKGROUND, np.float32)))
+    cnt, recs = C.count_reach(g["xys"], g["radii"], g["conics"], g["opac"], tb, bands=C.tile_bands(tb))
+    order, cum = C.depth_order(g["depths"], g["radii"], cnt)
+    I = int(cum[-1].item())
+    ids, bins, slots = C.bin_sorted(n, I + 4096, order, cum, g["xys"], g["radii"], tb, bw, recs, device_sized=True,
+                                    want_slots=True)
+    lens = npy(bins[:, 1] - bins[:, 0])
+    assert lens.max() > 512 and lens.min() < 64, (lens.max(), lens.min())
+
+    p = lambda t: None if t is None else ct.c_void_p(t.data_ptr())  # noqa: E731
+    i_, u_, f_, z_ = ct.c_int, ct.c_uint, ct.c_float, ct.c_size_t
+    geo = (p(g["xys"]), p(g["conics"]), p(g["colors"]))
+    stream = ct.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def ok(rc):
+        assert rc == 0, L.gsr_last_error().decode()
+
+    def forward(entry, deep, rgbd):
+        o = dict(img=torch.empty(H, W, 3, device=DEV), T=torch.empty(H, W, device=DEV),
+                 idx=torch.empty(H, W, dtype=torch.int32, device=DEV), zero=torch.ones(10 * n, device=DEV))
+        if entry != "plain":
+            o["alpha"] = torch.empty(H, W, device=DEV)
+        if rgbd:
+            o["ext"] = torch.empty(H, W, device=DEV)
+        ex = (i_(deep), p(o.get("alpha")), p(o["zero"]), z_(4 * o["zero"].numel()))
+        lists, tail = (p(ids), p(bins)), (p(g["opac"]), p(g["bg"]))
+        outs = (p(o["T"]), p(o["idx"]))
+        if entry == "plain":
+            ok(L.gsr_rasterize_forward(i_(tb[0]), i_(tb[1]), u_(bw), u_(W), u_(H), *lists, *geo, *tail, p(o["img"]), *outs,
+                                       i_(deep), stream))
+            del o["zero"]  # (this entry clears nothing)
+        elif entry == "ex":
+            ok(L.gsr_rasterize_forward_ex(i_(tb[0]), i_(tb[1]), u_(bw), u_(W), u_(H), *lists, *geo, *tail, p(o["img"]),
+                                          *outs, *ex, stream))
+        elif entry == "rgbd":
+            ok(L.gsr_rasterize_forward_rgbd(i_(tb[0]), i_(tb[1]), u_(W), u_(H), *lists, *geo, p(g["depths"]), *tail,
+                                            f_(0.25), p(o["img"]), p(o["ext"]), *outs, *ex, stream))
+        else:
+            ok(L.gsr_rasterize_forward_seg(i_(tb[0]), i_(tb[1]), u_(W), u_(H), *lists, *geo,
+                                           p(g["depths"]) if rgbd else None, *tail, f_(0.25 if rgbd else 0.0), p(o["img"]),
+                                           p(o.get("ext")), *outs, *ex, i_(0), i_(0), None, z_(0), stream))
+        return o
+
+    v_img = torch.rand(H, W, 3, device=DEV) * 2 - 1
+    v_alpha, v_ext = torch.rand(H, W, device=DEV) * 2 - 1, torch.rand(H, W, device=DEV) * 2 - 1
+
+    def backward(entry, deep, rgbd, f, acc=None):
+        zeroed = acc is not None
+        if not zeroed:
+            acc = torch.full((10 * n,), 7.0, device=DEV)  # (the entry clears what it accumulates into)
+        v = [acc[:2 * n], acc[2 * n:5 * n], acc[5 * n:8 * n], acc[8 * n:9 * n], acc[9 * n:]]
+        head = (u_(H), u_(W))
+        a = (i_(n), p(ids), p(bins), *geo)
+        b = (p(g["opac"]), p(g["bg"]))
+        st = (p(f["T"]), p(f["idx"]), p(v_img))
+        if entry in ("plain", "ex"):
+            more = (i_(deep), stream) if entry == "plain" else (i_(deep), i_(1 if zeroed else 0), stream)
+            ok(getattr(L, "gsr_rasterize_backward" + ("" if entry == "plain" else "_ex"))(
+                *head, u_(bw), *a, *b, *st, p(v_alpha), *(p(t) for t in v[:4]), *more))
+        elif entry == "rgbd":
+            ok(L.gsr_rasterize_backward_rgbd(*head, *a, p(g["depths"]), *b, f_(0.25), *st, p(v_ext), p(v_alpha),
+                                             p(v[0]), p(v[1]), p(v[2]), p(v[4]), p(v[3]), i_(deep),
+                                             i_(1 if zeroed else 0), stream))
+        else:
+            ok(L.gsr_rasterize_backward_seg(*head, *a, p(g["depths"]) if rgbd else None, *b, f_(0.25 if rgbd else 0.0), *st,
+                                            p(v_ext) if rgbd else None, p(v_alpha), p(v[0]), p(v[1]), p(v[2]),
+                                            p(v[4]) if rgbd else None, p(v[3]), i_(deep), i_(1 if zeroed else 0), i_(0),
+                                            i_(0), None, z_(0), stream))
+        return [npy(t) for t in (v if rgbd else v[:4])]
+
+    for deep in (0, 128):
+        for rgbd, entries in ((False, ("plain", "ex", "seg")), (True, ("rgbd", "seg"))):
+            outs = [forward(e, deep, rgbd) for e in entries]
+            for e, o, prev in zip(entries[1:], outs[1:], outs):  # (plain has neither alpha nor a zero region)
+                for k in prev.keys() & o.keys():
+                    assert torch.equal(prev[k], o[k]), (deep, rgbd, e, k)
+            assert {"alpha", "zero"} <= outs[-2].keys() & outs[-1].keys() and (not rgbd or "ext" in outs[-1])
+            for o in outs:
+                assert "zero" not in o or not o["zero"].any(), (deep, rgbd)
+            f = outs[-1]
+            grads = [backward(e, deep, rgbd, f, acc=f["zero"] if e in ("ex", "rgbd") else None) for e in entries]
+            for e, gr in zip(entries[1:], grads[1:]):
+                for nm, x, y in zip(("v_xy", "v_conic", "v_colors", "v_opacity", "v_extra"), gr, grads[0]):
+                    grad_close(x, y, name=f"{nm} ({e}, deep {deep}, rgbd {rgbd})")
+            assert np.abs(grads[0][0]).max() > 0
+
+    # the deterministic variant, through its partial rows: twice the same bits, RGB and RGB + extra
+    f3, f4 = forward("ex", 0, False), forward("rgbd", 0, True)
+    nbytes = int(L.gsr_rasterize_backward_det_workspace_bytes(i_(ids.numel())))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=DEV)
+    for rgbd, f in ((False, f3), (True, f4)):
+        runs = []
+        for _ in range(2):
+            v = [torch.empty(n, k, device=DEV) for k in (2, 3, 3, 1, 1)]
+            ok(L.gsr_rasterize_backward_det(
+                u_(H), u_(W), i_(n), i_(ids.numel()), p(ids), p(bins), *geo, p(g["depths"]) if rgbd else None, p(g["opac"]),
+                p(g["bg"]), f_(0.25 if rgbd else 0.0), p(f["T"]), p(f["idx"]), p(v_img), p(v_ext) if rgbd else None,
+                p(v_alpha), p(order), p(cum), i_(1), p(slots), p(ws), z_(nbytes), p(v[0]), p(v[1]), p(v[2]),
+                p(v[4]) if rgbd else None, p(v[3]), stream))
+            runs.append(v if rgbd else v[:4])
+        for x, y in zip(*runs):
+            assert torch.equal(x, y) and torch.isfinite(x).all()
+        assert runs[0][0].abs().max().item() > 0
