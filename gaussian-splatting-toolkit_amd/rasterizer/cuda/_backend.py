@@ -94,6 +94,9 @@ SYMBOLS = (
     "gsr_tsdf_extract_mesh_workspace_bytes",
     "gsr_tsdf_extract_mesh_count",
     "gsr_tsdf_extract_mesh_emit",
+    "gsr_mesh_clean_workspace_bytes",
+    "gsr_mesh_label",
+    "gsr_mesh_emit",
     "gsr_debug_count_staged",
     "gsr_debug_wave_trace",
     "gsr_calibrate_valu",
@@ -136,6 +139,7 @@ def _load():
     lib.gsr_tsdf_allocate_workspace_bytes.restype = C.c_size_t
     lib.gsr_tsdf_extract_points_workspace_bytes.restype = C.c_size_t
     lib.gsr_tsdf_extract_mesh_workspace_bytes.restype = C.c_size_t
+    lib.gsr_mesh_clean_workspace_bytes.restype = C.c_size_t
     return lib
 
 

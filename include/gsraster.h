@@ -41,6 +41,7 @@ extern "C" {
 #define GSR_EINVAL -1   /* bad argument (shape / range / null pointer) */
 #define GSR_ELAUNCH -2  /* HIP reported a launch / runtime error */
 #define GSR_ENOMEM -3   /* workspace too small */
+#define GSR_ERANGE -4   /* index data on the device outside its range (gsr_mesh_label) */
 
 typedef void *gsr_stream_t; /* hipStream_t */
 
@@ -963,6 +964,50 @@ int gsr_tsdf_extract_mesh_emit(const gsr_tsdf_volume *vol, void *workspace,
                                size_t workspace_bytes, int num_vertices, int num_triangles,
                                float *vertices, float *vertex_colors, int32_t *triangles,
                                gsr_stream_t stream);
+
+/* ---- mesh cleaning: what `ExportTSDF(clean=True)` does to mesh.ply -----
+ * Input: vertices float [V,3], optional per-vertex attributes float [V,C], triangles int32
+ * [F,3], min_component_faces >= 0.  The rules, applied in this order:
+ *  1. Index check.  An index outside [0, V) is an error (GSR_ERANGE), found by a kernel
+ *     that reads `triangles` only; its verdict is read back before any kernel that
+ *     dereferences with an index is launched, and none is.
+ *  2. Null faces are removed: two equal indices, or (v1 - v0) x (v2 - v0) with all three
+ *     components exactly 0 in float32, every operation rounded on its own (a NaN coordinate
+ *     makes the product non-zero: not null; coinciding vertices under different indices:
+ *     null).  With vertices == NULL only the repeated-index part applies.
+ *  3. Duplicate faces are removed: faces with the same SET of three indices, whatever the
+ *     order or winding; of each set the lowest face index stays.
+ *  4. Components.  Two surviving faces are adjacent when they share an edge (the same
+ *     unordered pair of indices; three or more faces on one edge are all adjacent; faces
+ *     that meet in a vertex only are not).  A component is the transitive closure; it is
+ *     removed when it has < min_component_faces surviving faces (exactly min: kept).
+ *  5. Compaction.  Surviving faces keep their relative order; vertices no surviving face
+ *     references are dropped, the others keep their relative order and their rows are
+ *     copied bit for bit; indices are remapped.
+ * Every output is a pure function of the input: label[f] = the lowest face index of f's
+ * component (-1 for a null or duplicate face), size[f] = that component's number of faces
+ * (0 for a null or duplicate face), whatever `min_component_faces`.
+ *   state  int32 [8]  0 scratch of the index check, 1 null faces, 2 duplicate faces,
+ *                     3 components, 4 components kept, 5 faces kept, 6 vertices kept,
+ *                     7 non-zero: two faces on one edge ended with different labels (an
+ *                     internal error; the result must not be used)
+ * gsr_mesh_label leaves the counts in `state` and the keep flags and offsets in the workspace
+ * (labels / sizes [F] are copied out when not NULL); it synchronises `stream` once, for the
+ * index check.  gsr_mesh_emit (same workspace, untouched in between; counts = state[6],
+ * state[5] as the caller read them back) writes the compacted mesh.  The workspace query
+ * returns 0 when num_faces <= 0, when the sizes do not fit (F <= 2^28) or when a size query of
+ * rocPRIM fails (no device); F = 0 needs none. */
+size_t gsr_mesh_clean_workspace_bytes(int num_vertices, int num_faces);
+int gsr_mesh_label(int num_vertices, int num_faces, const float *vertices,
+                   const int32_t *triangles, int min_component_faces, int32_t *state,
+                   void *workspace, size_t workspace_bytes, int32_t *labels,
+                   int32_t *sizes, gsr_stream_t stream);
+int gsr_mesh_emit(int num_vertices, int num_faces, int num_attributes,
+                  const float *vertices, const float *attributes,
+                  const int32_t *triangles, const void *workspace,
+                  size_t workspace_bytes, int out_vertices, int out_faces,
+                  float *vertices_out, float *attributes_out, int32_t *triangles_out,
+                  gsr_stream_t stream);
 
 /* ---- measurement hook ---------------------------------------------------------
  * counters: two device uint64 (or NULL = off, the default).  While set, the 16x16

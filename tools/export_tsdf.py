@@ -2,12 +2,14 @@
 
     python tools/export_tsdf.py --ply MODEL.ply --poses poses.json --out DIR
         [--voxel-length 0.01171875] [--sdf-trunc 0.06] [--depth-trunc 10] [--bounds x0 y0 z0 x1 y1 z1]
-        [--capacity BLOCKS] [--alpha-min 0.5] [--background r g b]
+        [--capacity BLOCKS] [--alpha-min 0.5] [--background r g b] [--no-clean] [--min-component-faces 20000]
 
 Renders RGB + depth from every camera of `poses.json` (the trajectory file `TSDFFusion.read_trajectory` reads), fuses
 the views into a block-sparse TSDF volume (gs_fusion) and writes `point_cloud.ply` and `mesh.ply` to DIR.  File names
 and defaults are `ExportTSDF`'s (gs_toolkit/scripts/exporter.py:233-237).  Without --bounds the volume is the box of
-the Gaussians' 1st-99th percentiles per axis, padded by the truncation distance.
+the Gaussians' 1st-99th percentiles per axis, padded by the truncation distance.  With cleaning on (the default, as
+`ExportTSDF.clean`), `cleaned_mesh.ply` is written as well: `mesh.ply` without null faces, duplicate faces, connected
+components of fewer than --min-component-faces faces and unreferenced vertices (gs_fusion.clean_mesh).
 """
 import argparse
 import json
@@ -19,7 +21,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "gaussian-splatting-toolkit_amd")]
 import numpy as np
 import torch
 
-from gs_fusion import TSDFVolume, fuse_views, read_poses_json
+from gs_fusion import TSDFVolume, clean_mesh, fuse_views, read_poses_json
 from gs_io import read_gaussian_ply, write_mesh_ply, write_point_cloud_ply
 
 DEFAULT_CAPACITY = 200_000  # blocks of 10 KiB: 2 GB
@@ -38,7 +40,7 @@ def activated(raw, device):
             "sh_coeffs": torch.cat([t["features_dc"][:, None, :], t["features_rest"]], 1).contiguous()}
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--ply", required=True)
     ap.add_argument("--poses", required=True)
@@ -51,7 +53,28 @@ def main(argv=None):
     ap.add_argument("--alpha-min", type=float, default=0.5)
     ap.add_argument("--background", type=float, nargs=3, default=(0.0, 0.0, 0.0))
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--clean", dest="clean", action="store_true", default=True,
+                    help="also write cleaned_mesh.ply (default)")
+    ap.add_argument("--no-clean", dest="clean", action="store_false")
+    ap.add_argument("--min-component-faces", type=int, default=20000,
+                    help="components of fewer faces are removed from cleaned_mesh.ply")
     a = ap.parse_args(argv)
+    if a.min_component_faces < 0:
+        ap.error("--min-component-faces must not be negative")
+    return a
+
+
+def write_cleaned(out_dir, vertices, vcolors, triangles, min_component_faces):
+    """`cleaned_mesh.ply` from the device tensors of `mesh.ply` -> the rows it adds to the JSON line.  A mesh of which
+    nothing is left is written as a file with zero vertices and zero faces."""
+    cv, cc, ct, info = clean_mesh(vertices, triangles, vcolors, min_component_faces, return_info=True)
+    write_mesh_ply(os.path.join(out_dir, "cleaned_mesh.ply"), cv.cpu().numpy(), ct.cpu().numpy(), cc.cpu().numpy())
+    return {"cleaned_vertices": int(cv.shape[0]), "cleaned_triangles": int(ct.shape[0]),
+            "components": info["components"]}
+
+
+def main(argv=None):
+    a = parse_args(argv)
 
     raw = read_gaussian_ply(a.ply)
     cams = read_poses_json(a.poses)
@@ -75,9 +98,12 @@ def main(argv=None):
     cpu = lambda t: t.cpu().numpy()  # noqa: E731
     write_point_cloud_ply(os.path.join(a.out, "point_cloud.ply"), cpu(points), cpu(colors), cpu(normals))
     write_mesh_ply(os.path.join(a.out, "mesh.ply"), cpu(vertices), cpu(triangles), cpu(vcolors))
-    print(json.dumps({"views": len(cams), "blocks": [int(b) for b in vol.blocks], "capacity": vol.capacity,
-                      "allocated_blocks": vol.num_allocated_blocks, "points": int(points.shape[0]),
-                      "vertices": int(vertices.shape[0]), "triangles": int(triangles.shape[0]), "out": a.out}))
+    summary = {"views": len(cams), "blocks": [int(b) for b in vol.blocks], "capacity": vol.capacity,
+               "allocated_blocks": vol.num_allocated_blocks, "points": int(points.shape[0]),
+               "vertices": int(vertices.shape[0]), "triangles": int(triangles.shape[0]), "out": a.out}
+    if a.clean:
+        summary.update(write_cleaned(a.out, vertices, vcolors, triangles, a.min_component_faces))
+    print(json.dumps(summary))
 
 
 if __name__ == "__main__":

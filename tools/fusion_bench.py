@@ -7,7 +7,11 @@ Volume: 512^3 voxel positions of L = 6/512 (a 6 m box over the scene), sdf_trunc
 Reported per view (median over the views after the warm-up ones): render ms, touch + allocate ms, integrate ms,
 integrate bytes (40 B per updated voxel + 8 B per visited, not updated voxel) over time as a fraction of the 8 TB/s
 HBM peak, and the same integration written in plain torch ops over the same listed blocks (what a user could write
-without this package); then point-cloud and mesh extraction (host clock around a call that ends in its read-back).
+without this package); then point-cloud and mesh extraction (host clock around a call that ends in its read-back);
+then `clean`: gs_fusion.clean_mesh (label + emit, min_component_faces = 20000) on the mesh just extracted, host clock
+around the synchronised call, and next to it the same mesh's face components through
+`scipy.sparse.csgraph.connected_components` on the host (the labelling alone, the mesh already in host memory), when
+scipy imports.
 Kernel names and times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/fusion_bench.py
 --no-torch` run (tools/summarize_prof.py).
 """
@@ -23,7 +27,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "gaussian-splatting-toolkit_amd")]
 import numpy as np
 import torch
 
-from gs_fusion import TSDFVolume, view_depth
+from gs_fusion import TSDFVolume, clean_mesh, view_depth
 from gs_fusion.volume import ST_LIST
 from harness import scene as S
 from harness.pipeline import CameraTensors, render_view
@@ -60,6 +64,43 @@ def torch_integrate(vol, pool, blocks, depth, color, valid, cam, depth_trunc):
     tsdf[slots] = torch.where(upd, (tsdf[slots] * w + f) / w1, tsdf[slots])
     col[slots] = torch.where(upd[..., None], (col[slots] * w[..., None] + color[i, j]) / w1[..., None], col[slots])
     weight[slots] = torch.where(upd, w1, w)
+
+
+def scipy_components_ms(triangles, num_vertices):
+    """Face components of a host mesh with scipy (faces that share an edge linked in a sparse graph), or None."""
+    try:
+        from scipy.sparse import coo_matrix
+        from scipy.sparse.csgraph import connected_components
+    except ImportError:
+        return None
+    t0 = time.perf_counter()
+    tri = triangles.astype(np.int64)
+    he = np.sort(np.concatenate([tri[:, [0, 1]], tri[:, [1, 2]], tri[:, [2, 0]]]), axis=1)
+    key = he[:, 0] * num_vertices + he[:, 1]
+    order = np.argsort(key, kind="stable")
+    face = np.tile(np.arange(len(tri)), 3)[order]
+    same = key[order][1:] == key[order][:-1]
+    g = coo_matrix((np.ones(int(same.sum()), np.int8), (face[:-1][same], face[1:][same])), shape=(len(tri),) * 2)
+    n, _ = connected_components(g, directed=False)
+    return round((time.perf_counter() - t0) * 1e3, 3), int(n)
+
+
+def clean_stage(vertices, vcolors, triangles, min_faces=20000):
+    """-> the `clean_*` rows of the result: label + emit on the extracted mesh, and scipy on the host next to it."""
+    if triangles.shape[0] == 0:
+        return {"clean_ms": None}
+    clean_mesh(vertices, triangles, vcolors, min_faces)  # warm-up of the shape
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    cv, _, ct, info = clean_mesh(vertices, triangles, vcolors, min_faces, return_info=True)
+    torch.cuda.synchronize()
+    row = {"clean_ms": round((time.perf_counter() - t) * 1e3, 3), "clean_min_component_faces": min_faces,
+           "clean_rows": [int(cv.shape[0]), int(ct.shape[0])], "clean_info": info}
+    host = scipy_components_ms(triangles.cpu().numpy(), int(vertices.shape[0]))
+    if host is not None:
+        # (scipy sees every face: null and duplicate faces are not removed first, so its count can differ)
+        row["clean_scipy_components_ms"], row["clean_scipy_components"] = host
+    return row
 
 
 def main():
@@ -146,6 +187,7 @@ def main():
         torch.cuda.synchronize()
         res[name] = round((time.perf_counter() - t) * 1e3, 3)
         res[name.replace("_ms", "_rows")] = [int(x.shape[0]) for x in got]
+    res.update(clean_stage(*got))
     line = json.dumps(res)
     print(line)
     if a.out:
