@@ -3,8 +3,9 @@
 //
 // Behaviour restated from rasterizer/cuda/csrc/sh.cuh:33-224: svox2 sign
 // convention, view direction normalised in-kernel, 3 channels, coefficient
-// layout [n, K, 3] (basis-major), bands above `degrees_to_use` ignored
-// (forward) / zero (backward).
+// layout [n, K, 3] (basis-major), bands above `degrees_to_use` not observed
+// (forward: they may hold NaN / Inf) / exact zeros (backward); at
+// degrees_to_use == 0 the direction is not observed either.
 //
 // HBM-bound streaming op; the coefficient tensor is the largest per-Gaussian
 // read of the whole path (192 B at degree 3).  One lane per Gaussian; at K == 16
@@ -45,56 +46,63 @@ namespace {
 #define C4_7 -1.7701307697799304f
 #define C4_8 0.6258357354491761f
 
-// Basis vector for direction d (normalised here); bands above `deg` are zero.
+// Band (degree) of basis function k.
+__host__ __device__ constexpr unsigned sh_band(int k) { return k >= 16 ? 4u : k >= 9 ? 3u : k >= 4 ? 2u : k >= 1 ? 1u : 0u; }
+
+// Basis vector for direction d (normalised here); bands above `deg` are exact zeros, whatever d holds.
 // Written branch-free over constant indices on purpose: with early returns the
 // compiler keeps B[] as a memory object and promotes it to LDS, which turned
 // this streaming op into an LDS-bank-conflict-bound one (measured 0.9 TB/s
-// instead of 3.6-4.5 TB/s).
+// instead of 3.6-4.5 TB/s).  The bands are switched off by a select, not by a
+// factor of zero: 0 * NaN and 0 * Inf are NaN, and a zero or non-finite direction
+// must not reach a band that is not in use.
 template <int KMAX>
 __device__ __forceinline__ void sh_basis(unsigned deg, float dx, float dy, float dz,
                                          float (&B)[KMAX]) {
   const float inv = rsqrtf(dx * dx + dy * dy + dz * dz);
   const float x = dx * inv, y = dy * inv, z = dz * inv;
   const float xx = x * x, xy = x * y, xz = x * z, yy = y * y, yz = y * z, zz = z * z;
-  const float m1 = deg >= 1 ? 1.f : 0.f, m2 = deg >= 2 ? 1.f : 0.f;
-  const float m3 = deg >= 3 ? 1.f : 0.f, m4 = deg >= 4 ? 1.f : 0.f;
+  const bool u1 = deg >= 1, u2 = deg >= 2, u3 = deg >= 3, u4 = deg >= 4;
   B[0] = C0;
   if constexpr (KMAX >= 4) {
-    B[1] = m1 * (-C1 * y);
-    B[2] = m1 * (C1 * z);
-    B[3] = m1 * (-C1 * x);
+    B[1] = u1 ? -C1 * y : 0.f;
+    B[2] = u1 ? C1 * z : 0.f;
+    B[3] = u1 ? -C1 * x : 0.f;
   }
   if constexpr (KMAX >= 9) {
-    B[4] = m2 * (C2_0 * xy);
-    B[5] = m2 * (C2_1 * yz);
-    B[6] = m2 * (C2_2 * (2.f * zz - xx - yy));
-    B[7] = m2 * (C2_3 * xz);
-    B[8] = m2 * (C2_4 * (xx - yy));
+    B[4] = u2 ? C2_0 * xy : 0.f;
+    B[5] = u2 ? C2_1 * yz : 0.f;
+    B[6] = u2 ? C2_2 * (2.f * zz - xx - yy) : 0.f;
+    B[7] = u2 ? C2_3 * xz : 0.f;
+    B[8] = u2 ? C2_4 * (xx - yy) : 0.f;
   }
   if constexpr (KMAX >= 16) {
-    B[9] = m3 * (C3_0 * y * (3.f * xx - yy));
-    B[10] = m3 * (C3_1 * xy * z);
-    B[11] = m3 * (C3_2 * y * (4.f * zz - xx - yy));
-    B[12] = m3 * (C3_3 * z * (2.f * zz - 3.f * xx - 3.f * yy));
-    B[13] = m3 * (C3_4 * x * (4.f * zz - xx - yy));
-    B[14] = m3 * (C3_5 * z * (xx - yy));
-    B[15] = m3 * (C3_6 * x * (xx - 3.f * yy));
+    B[9] = u3 ? C3_0 * y * (3.f * xx - yy) : 0.f;
+    B[10] = u3 ? C3_1 * xy * z : 0.f;
+    B[11] = u3 ? C3_2 * y * (4.f * zz - xx - yy) : 0.f;
+    B[12] = u3 ? C3_3 * z * (2.f * zz - 3.f * xx - 3.f * yy) : 0.f;
+    B[13] = u3 ? C3_4 * x * (4.f * zz - xx - yy) : 0.f;
+    B[14] = u3 ? C3_5 * z * (xx - yy) : 0.f;
+    B[15] = u3 ? C3_6 * x * (xx - 3.f * yy) : 0.f;
   }
   if constexpr (KMAX >= 25) {
-    B[16] = m4 * (C4_0 * xy * (xx - yy));
-    B[17] = m4 * (C4_1 * yz * (3.f * xx - yy));
-    B[18] = m4 * (C4_2 * xy * (7.f * zz - 1.f));
-    B[19] = m4 * (C4_3 * yz * (7.f * zz - 3.f));
-    B[20] = m4 * (C4_4 * (zz * (35.f * zz - 30.f) + 3.f));
-    B[21] = m4 * (C4_5 * xz * (7.f * zz - 3.f));
-    B[22] = m4 * (C4_6 * (xx - yy) * (7.f * zz - 1.f));
-    B[23] = m4 * (C4_7 * xz * (xx - 3.f * yy));
-    B[24] = m4 * (C4_8 * (xx * (xx - 3.f * yy) - yy * (3.f * xx - yy)));
+    B[16] = u4 ? C4_0 * xy * (xx - yy) : 0.f;
+    B[17] = u4 ? C4_1 * yz * (3.f * xx - yy) : 0.f;
+    B[18] = u4 ? C4_2 * xy * (7.f * zz - 1.f) : 0.f;
+    B[19] = u4 ? C4_3 * yz * (7.f * zz - 3.f) : 0.f;
+    B[20] = u4 ? C4_4 * (zz * (35.f * zz - 30.f) + 3.f) : 0.f;
+    B[21] = u4 ? C4_5 * xz * (7.f * zz - 3.f) : 0.f;
+    B[22] = u4 ? C4_6 * (xx - yy) * (7.f * zz - 1.f) : 0.f;
+    B[23] = u4 ? C4_7 * xz * (xx - 3.f * yy) : 0.f;
+    B[24] = u4 ? C4_8 * (xx * (xx - 3.f * yy) - yy * (3.f * xx - yy)) : 0.f;
   }
 }
-// (a zero direction gives NaN in the bands >= 1 when they are in use, exactly
-//  like the reference's x / norm; with deg == 0 the masks multiply NaN by 0 ->
-//  guard: the degree-0 term never touches the direction)
+// Contract (include/gsraster.h): the bands above `degrees_to_use`, and at degrees_to_use == 0 the direction, are
+// not observed.  A zero direction gives NaN in the bands >= 1 that are in use, exactly like the reference's
+// x / norm, and exact zeros in the others (the selects above): the backward kernels write B[k] * v, so zeros.  The
+// forward kernels still load every coefficient (in bounds, and the loads stay coalesced) but add band k only when it
+// is in use: a select on the loaded coefficient, `sh_used`, since 0 * c is NaN for a non-finite c.
+__device__ __forceinline__ float sh_used(unsigned deg_use, int k, float c) { return deg_use >= sh_band(k) ? c : 0.f; }
 
 // ---- K == 16, 16-byte aligned coefficients ----------------------------------
 // One lane per Gaussian for the arithmetic, but the coefficients move as the
@@ -138,10 +146,6 @@ __global__ __launch_bounds__(64 * WAVES) void sh16_fwd_kernel(
   for (int i = 0; i < 12; ++i) q[i] = lds[w][lane * kShRow + i];
   float B[16];
   sh_basis<16>(deg_use, dx, dy, dz, B);
-  if (deg_use == 0) {
-#pragma unroll
-    for (int k = 1; k < 16; ++k) B[k] = 0.f;
-  }
   const float f[48] = {
       q[0].x, q[0].y, q[0].z, q[0].w, q[1].x, q[1].y, q[1].z, q[1].w, q[2].x, q[2].y, q[2].z, q[2].w,
       q[3].x, q[3].y, q[3].z, q[3].w, q[4].x, q[4].y, q[4].z, q[4].w, q[5].x, q[5].y, q[5].z, q[5].w,
@@ -150,9 +154,9 @@ __global__ __launch_bounds__(64 * WAVES) void sh16_fwd_kernel(
   float r = 0.f, gr = 0.f, b = 0.f;
 #pragma unroll
   for (int k = 0; k < 16; ++k) {
-    r += B[k] * f[3 * k];
-    gr += B[k] * f[3 * k + 1];
-    b += B[k] * f[3 * k + 2];
+    r += B[k] * sh_used(deg_use, k, f[3 * k]);
+    gr += B[k] * sh_used(deg_use, k, f[3 * k + 1]);
+    b += B[k] * sh_used(deg_use, k, f[3 * k + 2]);
   }
   colors[3 * g] = r;
   colors[3 * g + 1] = gr;
@@ -170,10 +174,6 @@ __global__ __launch_bounds__(64 * WAVES) void sh16_bwd_kernel(
   if (g < n) {
     float B[16];
     sh_basis<16>(deg_use, viewdirs[3 * g], viewdirs[3 * g + 1], viewdirs[3 * g + 2], B);
-    if (deg_use == 0) {
-#pragma unroll
-      for (int k = 1; k < 16; ++k) B[k] = 0.f;
-    }
     const float vr = v_colors[3 * g], vg = v_colors[3 * g + 1], vb = v_colors[3 * g + 2];
     float f[48];
 #pragma unroll
@@ -205,17 +205,13 @@ __global__ __launch_bounds__(256) void sh_fwd_kernel(
   if (g >= n) return;
   float B[K];
   sh_basis<K>(deg_use, viewdirs[3 * g], viewdirs[3 * g + 1], viewdirs[3 * g + 2], B);
-  if (deg_use == 0) {
-#pragma unroll
-    for (int k = 1; k < K; ++k) B[k] = 0.f;
-  }
   const float *c = coeffs + (size_t)g * K * 3;
   float r = 0.f, gr = 0.f, b = 0.f;
 #pragma unroll
   for (int k = 0; k < K; ++k) {
-    r += B[k] * c[3 * k];
-    gr += B[k] * c[3 * k + 1];
-    b += B[k] * c[3 * k + 2];
+    r += B[k] * sh_used(deg_use, k, c[3 * k]);
+    gr += B[k] * sh_used(deg_use, k, c[3 * k + 1]);
+    b += B[k] * sh_used(deg_use, k, c[3 * k + 2]);
   }
   colors[3 * g] = r;
   colors[3 * g + 1] = gr;
@@ -230,10 +226,6 @@ __global__ __launch_bounds__(256) void sh_bwd_kernel(
   if (g >= n) return;
   float B[K];
   sh_basis<K>(deg_use, viewdirs[3 * g], viewdirs[3 * g + 1], viewdirs[3 * g + 2], B);
-  if (deg_use == 0) {
-#pragma unroll
-    for (int k = 1; k < K; ++k) B[k] = 0.f;
-  }
   const float vr = v_colors[3 * g], vg = v_colors[3 * g + 1], vb = v_colors[3 * g + 2];
   float *o = v_coeffs + (size_t)g * K * 3;
 #pragma unroll
@@ -330,17 +322,13 @@ __global__ __launch_bounds__(256) void sh_split_fwd_kernel(
   if (g >= n) return;
   float B[K];
   sh_basis<K>(deg_use, dx, dy, dz, B);
-  if (deg_use == 0) {
-#pragma unroll
-    for (int k = 1; k < K; ++k) B[k] = 0.f;
-  }
   float r = B[0] * dc0, gr = B[0] * dc1, b = B[0] * dc2;
   const float *row = lds[w] + lane * STRIDE;
 #pragma unroll
   for (int k = 1; k < K; ++k) {
-    r += B[k] * row[3 * (k - 1)];
-    gr += B[k] * row[3 * (k - 1) + 1];
-    b += B[k] * row[3 * (k - 1) + 2];
+    r += B[k] * sh_used(deg_use, k, row[3 * (k - 1)]);
+    gr += B[k] * sh_used(deg_use, k, row[3 * (k - 1) + 1]);
+    b += B[k] * sh_used(deg_use, k, row[3 * (k - 1) + 2]);
   }
   // optional epilogue of the models: rgb = clamp(sh + 0.5, min=0) (vanilla_gs.py:826)
   r += shift;
@@ -373,10 +361,6 @@ __global__ __launch_bounds__(256) void sh_split_bwd_kernel(
   if (g < n) {
     float B[K];
     sh_basis<K>(deg_use, viewdirs[3 * g], viewdirs[3 * g + 1], viewdirs[3 * g + 2], B);
-    if (deg_use == 0) {
-#pragma unroll
-      for (int k = 1; k < K; ++k) B[k] = 0.f;
-    }
     float vr = v_colors[3 * g], vg = v_colors[3 * g + 1], vb = v_colors[3 * g + 2];
     if (clamped_colors) {  // forward output of the clamped epilogue: no gradient where it cut (-0.0)
       vr = __float_as_uint(clamped_colors[3 * g]) == 0x80000000u ? 0.f : vr;
@@ -525,10 +509,6 @@ __global__ __launch_bounds__(256) void sh_bwd_views_kernel(const unsigned n, con
     const float dinv = 1.f / sqrtf(dx * dx + dy * dy + dz * dz);
     float B[K];
     sh_basis<K>(deg_use, dx * dinv, dy * dinv, dz * dinv, B);
-    if (deg_use == 0) {
-#pragma unroll
-      for (int k = 1; k < K; ++k) B[k] = 0.f;
-    }
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       f[3 * k] += B[k] * vr;

@@ -87,7 +87,13 @@ int gsr_project_backward(int num_points, const float *means3d,
 /* ---- spherical harmonics ----------------------------------------------
  * replaces compute_sh_forward_tensor / compute_sh_backward_tensor
  * (bindings.cu:58-103), kernels sh.cuh:188-224.  degree in 0..4 fixes the
- * coefficient layout [n, (degree+1)^2, 3]; degrees_to_use <= degree. */
+ * coefficient layout [n, (degree+1)^2, 3]; degrees_to_use <= degree.
+ * Contract for what is not in use (all SH entries below too): the bands
+ * k >= (degrees_to_use+1)^2 of coeffs, and at degrees_to_use == 0 the view
+ * direction, are NOT OBSERVED: they may hold anything (NaN, Inf) without
+ * reaching colors.  The backward entries write exact zeros into those bands of
+ * v_coeffs whatever the direction holds (a zero or non-finite direction gives
+ * NaN only in the bands 1 .. in use, like the reference's x / norm). */
 int gsr_sh_forward(unsigned num_points, unsigned degree,
                    unsigned degrees_to_use, const float *viewdirs,
                    const float *coeffs, float *colors, gsr_stream_t stream);
@@ -497,7 +503,9 @@ int gsr_depth_l1_backward(long long num_pixels, const float *upstream,
  * `torch.clamp(rgbs + 0.5, min=0.0)`): colors = sh + shift, cut at 0 when
  * clamp_zero != 0 -- a channel that was cut is stored as -0.0, so that the backward,
  * which takes those colours (clamped_colors, NULL if not clamped), blocks the gradient
- * exactly where sh + shift < 0 and passes it where it is >= 0, like torch.clamp. */
+ * exactly where sh + shift < 0 and passes it where it is >= 0, like torch.clamp.
+ * The bands of `rest` above degrees_to_use and, at degrees_to_use == 0, viewdirs are not observed (see
+ * gsr_sh_forward); those bands of v_rest are written as exact zeros. */
 int gsr_sh_forward_split(unsigned num_points, unsigned degree,
                          unsigned degrees_to_use, const float *viewdirs,
                          const float *dc, const float *rest, float *colors,
@@ -515,7 +523,9 @@ int gsr_sh_backward_split(unsigned num_points, unsigned degree,
  * itself -- the same sum on every rank.  v_colors: view r at v_colors + r * v_colors_stride floats, [n,3] each;
  * camera_positions: view r at camera_positions + r * camera_stride floats.  Output: v_coeffs [n,K,3], or
  * (v_coeffs NULL) v_dc [n,3] and v_rest [n,K-1,3]; K = (degree+1)^2, degree in [0,3]; bands above degrees_to_use
- * are written as zeros.  The direction is formed as gsr_activate_forward forms it. */
+ * are written as exact zeros, also for a Gaussian that sits exactly at a camera position (a zero direction: NaN in the
+ * bands 1 .. in use only; at degrees_to_use == 0 the positions are not observed).  The direction is formed as
+ * gsr_activate_forward forms it. */
 int gsr_sh_backward_views(unsigned num_points, unsigned degree, unsigned degrees_to_use,
                           unsigned num_views, const float *means3d,
                           const float *camera_positions, size_t camera_stride,
