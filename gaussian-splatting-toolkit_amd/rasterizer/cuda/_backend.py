@@ -97,6 +97,10 @@ SYMBOLS = (
     "gsr_mesh_clean_workspace_bytes",
     "gsr_mesh_label",
     "gsr_mesh_emit",
+    "gsr_mesh_distance_workspace_bytes",
+    "gsr_mesh_bvh_build",
+    "gsr_mesh_distance_query",
+    "gsr_mesh_distance_stats",
     "gsr_debug_count_staged",
     "gsr_debug_wave_trace",
     "gsr_calibrate_valu",
@@ -140,6 +144,7 @@ def _load():
     lib.gsr_tsdf_extract_points_workspace_bytes.restype = C.c_size_t
     lib.gsr_tsdf_extract_mesh_workspace_bytes.restype = C.c_size_t
     lib.gsr_mesh_clean_workspace_bytes.restype = C.c_size_t
+    lib.gsr_mesh_distance_workspace_bytes.restype = C.c_size_t
     return lib
 
 

@@ -41,7 +41,7 @@ extern "C" {
 #define GSR_EINVAL -1   /* bad argument (shape / range / null pointer) */
 #define GSR_ELAUNCH -2  /* HIP reported a launch / runtime error */
 #define GSR_ENOMEM -3   /* workspace too small */
-#define GSR_ERANGE -4   /* index data on the device outside its range (gsr_mesh_label) */
+#define GSR_ERANGE -4   /* index data on the device outside its range (gsr_mesh_label, gsr_mesh_bvh_build) */
 
 typedef void *gsr_stream_t; /* hipStream_t */
 
@@ -1018,6 +1018,61 @@ int gsr_mesh_emit(int num_vertices, int num_faces, int num_attributes,
                   size_t workspace_bytes, int out_vertices, int out_faces,
                   float *vertices_out, float *attributes_out, int32_t *triangles_out,
                   gsr_stream_t stream);
+
+/* ---- surface distance: points against a triangle mesh -----------------
+ * What gs_toolkit/evaluation/surface_distance computes for every vertex of a generated mesh.
+ * Mesh: vertices float [V,3], triangles int32 [F,3] (a soup is allowed: no welding, no
+ * watertightness, no normals).  Points float [n,3].  The rule:
+ *  1. d(p) = min over the usable triangles f of |p - q_f(p)|, q_f(p) the closest point of
+ *     triangle f to p by the Voronoi-region rule (Ericson / Eberly: three vertex regions, three
+ *     edge regions, the face).  Outputs: d float [n], the index f of a minimising triangle
+ *     int32 [n] (ties: any minimiser), optionally q float [n,3].  Unsigned: there is no sign.
+ *  2. Degenerate triangles.  A triangle with |n|^2 <= 2^-40 |ab|^2 |ac|^2 (n = ab x ac; exactly
+ *     zero area included) counts as its three edges as segments; so does one on which the
+ *     rounded region tests contradict one another.  A zero-length segment counts as a point.
+ *     Every quotient is guarded: finite input never gives NaN.
+ *  3. Non-finite input.  A triangle with a non-finite vertex (or centroid) is left out of the
+ *     tree and counted in state[1].  A non-finite point gets d = NaN, f = -1, q = NaN and is
+ *     counted as invalid by the statistics, which leave it out.
+ *  4. Index check.  An index outside [0, V) is GSR_ERANGE, as in gsr_mesh_label: a face that
+ *     fails the check is not read through, and the verdict is read back before any later
+ *     kernel runs.  A mesh with no usable triangle builds a tree on which every query answers
+ *     NaN / -1 (state[1] == F tells the caller).
+ *  5. Arithmetic: float32.  The triangle is translated first (a - p, b - p, c - p), q is the
+ *     clamped closest point of the translated triangle and d = |q|, every operation rounded on
+ *     its own (no contraction), dot(x, y) = (x0 y0 + x1 y1) + x2 y2; `closest` = p + q.
+ *     tests/surface_distance_reference.py restates the sequence in NumPy.
+ * Nothing is allocated here.  gsr_mesh_distance_workspace_bytes(what, F, n): bytes of the tree
+ * (what = 0; kept as long as the mesh is queried), of the build's workspace (1), of a tree
+ * query's workspace for n points (2; the exhaustive query needs none), of the statistics'
+ * workspace (3); 0 when the sizes do not fit (F in [1, 2^28], n in [1, 2^30]) or a size query
+ * of rocPRIM fails (no device).  All buffers 256-byte aligned; none needs to be zeroed.
+ *   state  int32 [4]   0 scratch of the index check, 1 triangles left out, 2-3 unused
+ * gsr_mesh_bvh_build synchronises `stream` once (the index check).  gsr_mesh_distance_query
+ * with GSR_MESH_DISTANCE_EXHAUSTIVE tests every point against every usable triangle instead of
+ * walking the tree (the on-device cross-check, never chosen by the library itself); both paths
+ * evaluate a triangle with the same device function.
+ * gsr_mesh_distance_stats over float32 distances, accumulated in float64 in a fixed order
+ * (bit-reproducible):  stats double [8]  0 finite distances, 1 non-finite ones, 2 mean, 3 root
+ * mean square, 4 max, 5 distances <= threshold (a negative threshold counts none), 6 sum,
+ * 7 sum of squares; mean, rms and max are 0 when nothing is finite. */
+#define GSR_MESH_DISTANCE_EXHAUSTIVE 1
+#define GSR_MESH_DISTANCE_BYTES_TREE 0
+#define GSR_MESH_DISTANCE_BYTES_BUILD 1
+#define GSR_MESH_DISTANCE_BYTES_QUERY 2
+#define GSR_MESH_DISTANCE_BYTES_STATS 3
+size_t gsr_mesh_distance_workspace_bytes(int what, int num_faces, int num_points);
+int gsr_mesh_bvh_build(int num_vertices, int num_faces, const float *vertices,
+                       const int32_t *triangles, void *tree, size_t tree_bytes,
+                       void *workspace, size_t workspace_bytes, int32_t *state,
+                       gsr_stream_t stream);
+int gsr_mesh_distance_query(int num_faces, const void *tree, size_t tree_bytes,
+                            int num_points, const float *points, int flags, void *workspace,
+                            size_t workspace_bytes, float *distance, int32_t *face,
+                            float *closest, gsr_stream_t stream);
+int gsr_mesh_distance_stats(int num_points, const float *distance, float threshold,
+                            void *workspace, size_t workspace_bytes, double *stats,
+                            gsr_stream_t stream);
 
 /* ---- measurement hook ---------------------------------------------------------
  * counters: two device uint64 (or NULL = off, the default).  While set, the 16x16

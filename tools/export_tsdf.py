@@ -3,13 +3,17 @@
     python tools/export_tsdf.py --ply MODEL.ply --poses poses.json --out DIR
         [--voxel-length 0.01171875] [--sdf-trunc 0.06] [--depth-trunc 10] [--bounds x0 y0 z0 x1 y1 z1]
         [--capacity BLOCKS] [--alpha-min 0.5] [--background r g b] [--no-clean] [--min-component-faces 20000]
+        [--gt GT.{stl,ply}] [--gt-threshold T]
 
 Renders RGB + depth from every camera of `poses.json` (the trajectory file `TSDFFusion.read_trajectory` reads), fuses
 the views into a block-sparse TSDF volume (gs_fusion) and writes `point_cloud.ply` and `mesh.ply` to DIR.  File names
 and defaults are `ExportTSDF`'s (gs_toolkit/scripts/exporter.py:233-237).  Without --bounds the volume is the box of
 the Gaussians' 1st-99th percentiles per axis, padded by the truncation distance.  With cleaning on (the default, as
 `ExportTSDF.clean`), `cleaned_mesh.ply` is written as well: `mesh.ply` without null faces, duplicate faces, connected
-components of fewer than --min-component-faces faces and unreferenced vertices (gs_fusion.clean_mesh).
+components of fewer than --min-component-faces faces and unreferenced vertices (gs_fusion.clean_mesh).  With --gt the
+JSON line also carries the surface distance of `mesh.ply` (fields `mesh_average_error`, `mesh_rms`, ...) and, when it
+was written, of `cleaned_mesh.ply` (`cleaned_average_error`, ...) against that ground truth: what tools/eval_surface.py
+prints for each file.
 """
 import argparse
 import json
@@ -58,9 +62,13 @@ def parse_args(argv=None):
     ap.add_argument("--no-clean", dest="clean", action="store_false")
     ap.add_argument("--min-component-faces", type=int, default=20000,
                     help="components of fewer faces are removed from cleaned_mesh.ply")
+    ap.add_argument("--gt", default=None, help="ground-truth mesh (.stl or .ply): append surface-distance fields")
+    ap.add_argument("--gt-threshold", type=float, default=None)
     a = ap.parse_args(argv)
     if a.min_component_faces < 0:
         ap.error("--min-component-faces must not be negative")
+    if a.gt_threshold is not None and not a.gt_threshold >= 0:
+        ap.error("--gt-threshold must not be negative")
     return a
 
 
@@ -103,6 +111,14 @@ def main(argv=None):
                "vertices": int(vertices.shape[0]), "triangles": int(triangles.shape[0]), "out": a.out}
     if a.clean:
         summary.update(write_cleaned(a.out, vertices, vcolors, triangles, a.min_component_faces))
+    if a.gt:
+        from eval_surface import evaluate, load_mesh
+
+        gt = load_mesh(a.gt)
+        for name, prefix in (("mesh.ply", "mesh_"), ("cleaned_mesh.ply", "cleaned_")):
+            path = os.path.join(a.out, name)
+            if os.path.exists(path) and (name == "mesh.ply" or a.clean):
+                summary.update(evaluate(gt, load_mesh(path), vol.device, threshold=a.gt_threshold, prefix=prefix))
     print(json.dumps(summary))
 
 
