@@ -162,7 +162,9 @@ static inline int cov2d_bounds(const float *cov2d, float *conic,
 
 /* forward.cu:13-90.  viewmat: >=12 floats (3x4 rows), projmat: 16 floats.
  * Every output element of every Gaussian is written (zeros where the CUDA
- * kernel returns early on a torch::zeros buffer, bindings.cu:126-139). */
+ * kernel returns early on a torch::zeros buffer, bindings.cu:126-139).
+ * scales == quats == NULL: cov3d is an INPUT (precomputed covariances, as in
+ * csrc/project.hip) and is left untouched. */
 GSR_API void gsr_oracle_project_forward(
     int n, const float *means3d, const float *scales, float glob_scale,
     const float *quats, const float *viewmat, const float *projmat, float fx,
@@ -175,7 +177,8 @@ GSR_API void gsr_oracle_project_forward(
 #pragma omp parallel for schedule(static)
   for (int i = 0; i < n; ++i) {
     float *c3 = cov3d + 6 * i;
-    for (int k = 0; k < 6; ++k) c3[k] = 0.f;
+    if (scales)
+      for (int k = 0; k < 6; ++k) c3[k] = 0.f;
     xys[2 * i] = xys[2 * i + 1] = 0.f;
     depths[i] = 0.f;
     radii[i] = 0;
@@ -190,7 +193,7 @@ GSR_API void gsr_oracle_project_forward(
     float tz = viewmat[8] * p[0] + viewmat[9] * p[1] + viewmat[10] * p[2] + viewmat[11];
     if (tz <= clip_thresh) continue;
 
-    cov3d_from_scale_rot(scales + 3 * i, glob_scale, quats + 4 * i, c3);
+    if (scales) cov3d_from_scale_rot(scales + 3 * i, glob_scale, quats + 4 * i, c3);
 
     /* forward.cu:398-442 EWA projection */
     float limx = 1.3f * tan_fovx, limy = 1.3f * tan_fovy;
@@ -243,7 +246,9 @@ GSR_API void gsr_oracle_project_forward(
 /* ------------------------------------------------------ project backward */
 
 /* backward.cu:305-453 + helpers.cuh:62-90,125-142,161-200.
- * Outputs are fully written (zero where radii<=0, bindings.cu:182-191). */
+ * Outputs are fully written (zero where radii<=0, bindings.cu:182-191).
+ * A NULL cotangent is a zero cotangent; scales == quats == NULL: the chain
+ * ends at v_cov3d and v_scale / v_quat are not touched (csrc/project.hip). */
 GSR_API void gsr_oracle_project_backward(
     int n, const float *means3d, const float *scales, float glob_scale,
     const float *quats, const float *viewmat, const float *projmat, float fx,
@@ -257,12 +262,14 @@ GSR_API void gsr_oracle_project_backward(
 #pragma omp parallel for schedule(static)
   for (int i = 0; i < n; ++i) {
     float *o2 = v_cov2d + 3 * i, *o3 = v_cov3d + 6 * i, *om = v_mean3d + 3 * i;
-    float *os = v_scale + 3 * i, *oq = v_quat + 4 * i;
     o2[0] = o2[1] = o2[2] = 0.f;
     for (int k = 0; k < 6; ++k) o3[k] = 0.f;
     om[0] = om[1] = om[2] = 0.f;
-    os[0] = os[1] = os[2] = 0.f;
-    oq[0] = oq[1] = oq[2] = oq[3] = 0.f;
+    if (scales) {
+      float *os = v_scale + 3 * i, *oq = v_quat + 4 * i;
+      os[0] = os[1] = os[2] = 0.f;
+      oq[0] = oq[1] = oq[2] = oq[3] = 0.f;
+    }
     if (radii[i] <= 0) continue;
     const float *p = means3d + 3 * i;
 
@@ -271,8 +278,8 @@ GSR_API void gsr_oracle_project_backward(
     float hy = projmat[4] * p[0] + projmat[5] * p[1] + projmat[6] * p[2] + projmat[7];
     float hw = projmat[12] * p[0] + projmat[13] * p[1] + projmat[14] * p[2] + projmat[15];
     float rw = 1.f / (hw + 1e-6f);
-    float vnx = 0.5f * (float)img_w * v_xy[2 * i];
-    float vny = 0.5f * (float)img_h * v_xy[2 * i + 1];
+    float vnx = v_xy ? 0.5f * (float)img_w * v_xy[2 * i] : 0.f;
+    float vny = v_xy ? 0.5f * (float)img_h * v_xy[2 * i + 1] : 0.f;
     float vt0 = vnx * rw, vt1 = vny * rw;
     float vt3 = -(vnx * hx + vny * hy) * rw * rw;
     float vm[3];
@@ -280,16 +287,16 @@ GSR_API void gsr_oracle_project_backward(
       vm[k] = projmat[k] * vt0 + projmat[4 + k] * vt1 + projmat[12 + k] * vt3;
 
     /* depth = row 2 of viewmat . p */
-    float vz = v_depth[i];
+    float vz = v_depth ? v_depth[i] : 0.f;
     vm[0] += viewmat[8] * vz;
     vm[1] += viewmat[9] * vz;
     vm[2] += viewmat[10] * vz;
 
     /* cov2d_to_conic_vjp : v_cov2d = -X G X */
     const float *co = conics + 3 * i;
-    const float *vc = v_conic + 3 * i;
     float X00 = co[0], X01 = co[1], X11 = co[2];
-    float G00 = vc[0], G01 = 0.5f * vc[1], G11 = vc[2];
+    float G00 = v_conic ? v_conic[3 * i] : 0.f, G01 = v_conic ? 0.5f * v_conic[3 * i + 1] : 0.f,
+          G11 = v_conic ? v_conic[3 * i + 2] : 0.f;
     /* XG */
     float A00 = X00 * G00 + X01 * G01, A01 = X00 * G01 + X01 * G11;
     float A10 = X01 * G00 + X11 * G01, A11 = X01 * G01 + X11 * G11;
@@ -300,7 +307,7 @@ GSR_API void gsr_oracle_project_backward(
 
     /* cov2d_to_compensation_vjp */
     {
-      float comp = compensation[i], vcomp = v_compensation[i];
+      float comp = compensation[i], vcomp = v_compensation ? v_compensation[i] : 0.f;
       float inv_det = co[0] * co[2] - co[1] * co[1];
       float om2 = 1.f - comp * comp;
       float vsq = vcomp * 0.5f / (comp + 1e-6f);
@@ -359,6 +366,8 @@ GSR_API void gsr_oracle_project_backward(
     om[2] = vm[2];
 
     /* scale_rot_to_cov3d_vjp */
+    if (!scales) continue; /* precomputed covariances: the chain ends at v_cov3d */
+    float *os = v_scale + 3 * i, *oq = v_quat + 4 * i;
     m3 vS = {{{o3[0], 0.5f * o3[1], 0.5f * o3[2]},
               {0.5f * o3[1], o3[3], 0.5f * o3[4]},
               {0.5f * o3[2], 0.5f * o3[4], o3[5]}}};

@@ -62,8 +62,12 @@ def _i(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
-def _p(a: np.ndarray):
-    return a.ctypes.data_as(C.c_void_p)
+def _fo(a) -> Optional[np.ndarray]:
+    return None if a is None else _f(a)
+
+
+def _p(a: Optional[np.ndarray]):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def num_sh_bases(degree: int) -> int:
@@ -72,15 +76,18 @@ def num_sh_bases(degree: int) -> int:
 
 def project_gaussians_forward(
     num_points, means3d, scales, glob_scale, quats, viewmat, projmat,
-    fx, fy, cx, cy, img_height, img_width, block_width, clip_thresh=0.01,
+    fx, fy, cx, cy, img_height, img_width, block_width, clip_thresh=0.01, cov3d_precomp=None,
 ):
     """-> (cov3d, xys, depths, radii, conics, compensation, num_tiles_hit)
-    (native tuple order, bindings.cu:158)."""
+    (native tuple order, bindings.cu:158).  ``cov3d_precomp`` [N,6] with ``scales`` = ``quats`` = None: covariances
+    handed in (as ``rasterizer.cuda.project_gaussians_forward`` takes them); returned as ``cov3d``, untouched."""
     n = int(num_points)
-    means3d, scales, quats = _f(means3d), _f(scales), _f(quats)
+    assert (cov3d_precomp is None) == (scales is not None) == (quats is not None)
+    means3d, scales, quats = _f(means3d), _fo(scales), _fo(quats)
     viewmat, projmat = _f(viewmat).reshape(-1), _f(projmat).reshape(-1)
     assert viewmat.size >= 12 and projmat.size == 16
-    cov3d = np.empty((n, 6), np.float32)
+    cov3d = np.empty((n, 6), np.float32) if cov3d_precomp is None else _f(cov3d_precomp)
+    assert cov3d.shape == (n, 6)
     xys = np.empty((n, 2), np.float32)
     depths = np.empty((n,), np.float32)
     radii = np.empty((n,), np.int32)
@@ -102,18 +109,20 @@ def project_gaussians_backward(
     fx, fy, cx, cy, img_height, img_width, cov3d, radii, conics, compensation,
     v_xy, v_depth, v_conic, v_compensation,
 ):
-    """-> (v_cov2d, v_cov3d, v_mean3d, v_scale, v_quat)"""
+    """-> (v_cov2d, v_cov3d, v_mean3d, v_scale, v_quat).  A cotangent that is None is a zero cotangent;
+    ``scales`` = ``quats`` = None (covariances were handed in): the chain ends at v_cov3d, v_scale = v_quat = None."""
     n = int(num_points)
-    args = [_f(means3d), _f(scales)]
-    quats = _f(quats)
+    assert (scales is None) == (quats is None)
+    args = [_f(means3d), _fo(scales)]
+    quats = _fo(quats)
     viewmat, projmat = _f(viewmat).reshape(-1), _f(projmat).reshape(-1)
     cov3d, radii, conics, compensation = _f(cov3d), _i(radii), _f(conics), _f(compensation)
-    v_xy, v_depth, v_conic, v_compensation = _f(v_xy), _f(v_depth), _f(v_conic), _f(v_compensation)
+    v_xy, v_depth, v_conic, v_compensation = _fo(v_xy), _fo(v_depth), _fo(v_conic), _fo(v_compensation)
     v_cov2d = np.empty((n, 3), np.float32)
     v_cov3d = np.empty((n, 6), np.float32)
     v_mean3d = np.empty((n, 3), np.float32)
-    v_scale = np.empty((n, 3), np.float32)
-    v_quat = np.empty((n, 4), np.float32)
+    v_scale = None if scales is None else np.empty((n, 3), np.float32)
+    v_quat = None if scales is None else np.empty((n, 4), np.float32)
     lib().gsr_oracle_project_backward(
         C.c_int(n), _p(args[0]), _p(args[1]), C.c_float(glob_scale), _p(quats),
         _p(viewmat), _p(projmat), C.c_float(fx), C.c_float(fy), C.c_float(cx),

@@ -1,5 +1,6 @@
-"""CPU: a float64 restatement of the projection (torch, autograd for the VJP) -- the high-precision reference the GPU
-stage tests (tests/test_gpu_heldout.py) hold csrc/project.hip's backward to on ill-conditioned covariances.
+"""CPU: the float64 restatement of the projection's VJP (tests/projection_reference.py: torch, autograd) -- the
+high-precision reference the GPU stage tests (tests/test_gpu_heldout.py) hold csrc/project.hip's backward to on
+ill-conditioned covariances.
 
 It follows the oracle's rules (oracle/gsr_oracle.c, gsr_oracle_project_backward): the quaternion is differentiated as
 the unit quaternion q / |q| (no projection onto the tangent space), the backward's EWA Jacobian has no fov clamp (so
@@ -14,59 +15,7 @@ import torch
 
 from harness import scene as S
 from oracle import oracle as O
-
-
-def _unit_rotation(q):
-    w, x, y, z = q.unbind(-1)
-    return torch.stack([
-        torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)], -1),
-        torch.stack([2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)], -1),
-        torch.stack([2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], -1)], -2)
-
-
-def project_vjp_fp64(means3d, scales, glob_scale, quats, viewmat, projmat, fx, fy, cx, cy, img_height, img_width,
-                     compensation, v_xy, v_depth, v_conic, v_compensation):
-    """-> (v_mean3d, v_scale, v_quat, guard) float64 numpy; `guard`: the Gaussians inside the 1.3x guard band (the
-    forward's fov clamp inactive, so the unclamped backward is the forward's derivative there)."""
-    d = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))  # noqa: E731
-    m = d(means3d).requires_grad_(True)
-    s = d(scales).requires_grad_(True)
-    q = d(quats)
-    qn = (q / q.norm(dim=-1, keepdim=True)).detach().requires_grad_(True)
-    vm, pm = d(viewmat).reshape(-1, 4)[:3], d(projmat).reshape(4, 4)
-    M = _unit_rotation(qn) * (glob_scale * s)[:, None, :]
-    V = M @ M.transpose(1, 2)
-    Wr = vm[:, :3]
-    t = m @ Wr.T + vm[:, 3]
-    tx, ty, tz = t.unbind(-1)
-    zero = torch.zeros_like(tz)
-    J = torch.stack([torch.stack([fx / tz, zero, -fx * tx / tz ** 2], -1),
-                     torch.stack([zero, fy / tz, -fy * ty / tz ** 2], -1)], -2)
-    T = J @ Wr
-    Cv = T @ V @ T.transpose(1, 2)
-    a, b, c = Cv[:, 0, 0] + 0.3, Cv[:, 0, 1], Cv[:, 1, 1] + 0.3
-    det = a * c - b * b
-    conic = torch.stack([c / det, -b / det, a / det], -1)
-    comp_sq = (Cv[:, 0, 0] * Cv[:, 1, 1] - Cv[:, 0, 1] ** 2) / det  # compensation^2
-    h = m @ pm[:, :3].T + pm[:, 3]
-    rw = 1.0 / (h[:, 3] + 1e-6)
-    xy = torch.stack([0.5 * img_width * h[:, 0] * rw + cx - 0.5, 0.5 * img_height * h[:, 1] * rw + cy - 0.5], -1)
-    vcomp = d(v_compensation) * 0.5 / (d(compensation) + 1e-6)  # d comp = d(comp^2) / (2 (comp + 1e-6))
-    loss = (xy * d(v_xy)).sum() + (tz * d(v_depth)).sum() + (conic * d(v_conic)).sum() + (comp_sq * vcomp).sum()
-    g_m, g_s, g_q = torch.autograd.grad(loss, (m, s, qn))
-    with torch.no_grad():
-        limx, limy = 1.3 * 0.5 * img_width / fx, 1.3 * 0.5 * img_height / fy
-        guard = ((tx / tz).abs() < limx) & ((ty / tz).abs() < limy)
-    return g_m.numpy(), g_s.numpy(), g_q.numpy(), guard.numpy()
-
-
-def row_err(mine, ref):
-    """Per row: max |mine - ref| over the row's components."""
-    return np.abs(np.asarray(mine, np.float64) - ref).reshape(len(ref), -1).max(axis=1)
-
-
-def row_max(ref):
-    return np.abs(ref).reshape(len(ref), -1).max(axis=1)
+from projection_reference import project_vjp_fp64, row_err, row_max  # noqa: F401  (re-exported: test_gpu_heldout.py)
 
 
 def oracle_project_vjp(sc, cam, cov3d, radii, conics, comp, v_xy, v_depth, v_conic, v_comp):
