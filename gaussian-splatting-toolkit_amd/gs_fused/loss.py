@@ -163,3 +163,53 @@ def depth_l1_loss(depth_acc: Tensor, alpha: Tensor, gt_depth: Tensor) -> Tensor:
     (depth_gs.py:531-538).  ``depth_acc`` is the raw output of the depth compositing
     pass, ``alpha`` the accumulated opacity of the RGB pass; differentiable w.r.t. both."""
     return _DepthL1.apply(depth_acc, alpha, gt_depth)
+
+
+DEPTH_REG_WORKSPACE_DOUBLES = 1024  # GSR_DEPTH_REG_WORKSPACE_DOUBLES (include/gsraster.h)
+
+
+class _DepthReg(Function):
+    @staticmethod
+    def forward(ctx, pred: Tensor, mask: Tensor):
+        shape = pred.shape
+        if pred.dim() == 3 and shape[-1] == 1:
+            pred = pred[..., 0]
+        if pred.dim() != 2 or pred.shape != mask.shape or pred.numel() == 0:
+            raise ValueError(f"expected pred [H,W] (or [H,W,1]) and mask [H,W], non-empty, got {tuple(shape)} and "
+                             f"{tuple(mask.shape)}")
+        p = _check(pred.contiguous(), "pred_depth", _f32)
+        m = _check(mask.contiguous(), "mask", _f32)
+        H, W = int(p.shape[0]), int(p.shape[1])
+        dev = p.device
+        with torch.cuda.device(dev):
+            scratch = torch.empty((2, H, W), dtype=_f32, device=dev)
+            work = torch.empty((DEPTH_REG_WORKSPACE_DOUBLES,), dtype=torch.float64, device=dev)
+            loss = torch.empty((), dtype=_f32, device=dev)
+            _call("gsr_depth_reg_forward", C.c_uint(H), C.c_uint(W), _ptr(p), _ptr(m), _ptr(scratch), _ptr(work),
+                  _ptr(loss), _stream(dev))
+        ctx.save_for_backward(p, m, scratch)
+        ctx.shape = shape
+        return loss
+
+    @staticmethod
+    def backward(ctx, v_loss):
+        p, m, scratch = ctx.saved_tensors
+        H, W = int(p.shape[0]), int(p.shape[1])
+        dev = p.device
+        up = v_loss.to(_f32).reshape(1).contiguous()
+        with torch.cuda.device(dev):
+            v_pred = torch.empty_like(p)
+            _call("gsr_depth_reg_backward", C.c_uint(H), C.c_uint(W), _ptr(up), _ptr(p), _ptr(m), _ptr(scratch),
+                  _ptr(v_pred), _stream(dev))
+        return v_pred.view(ctx.shape), None
+
+
+def depth_reg_loss(pred_depth: Tensor, mask: Tensor) -> Tensor:
+    """The depth regularisation of the co-gs model (depth_gs.py:521-528 with `nearMean_map` and `l2_loss`,
+    utils/losses.py:8-9, 61-81) in two launches each way: with ``m = mask * (pred > 0)``, ``near`` = the plus-shaped
+    five-tap sum (zero padding) of ``pred * m`` over that of ``m`` plus 1e-8, returns
+    ``((near - pred * (pred > 0)) ** 2).mean()``.  ``pred_depth`` [H,W] or [H,W,1], ``mask`` [H,W] of any values (the
+    model passes the non-edge mask, ``image2canny(gt_img, 50, 150, isEdge1=False)``).  Differentiable w.r.t.
+    ``pred_depth`` only -- the mask and ``pred > 0`` are constants, as in the source.  The scalar is summed in float64
+    in a fixed order: two runs are bit-equal."""
+    return _DepthReg.apply(pred_depth, mask)

@@ -9,10 +9,16 @@ that switches them on trains through the same loop.  What each follows:
   scaled_log_depth_loss  depth_gs.py:492-518     edge-aware log(1 + |gt - (scale * pred + shift)|), weights exp(-|grad img|)
   scale_regularisation   depth_gs.py:450-460     0.1 * mean(max(max_scale / min_scale, ratio) - ratio), every 10th step
   sparse_loss            depth_gs.py:462-467     lambda * mean(log(o + 1e-6) + log(1 - o + 1e-6)), every 100th step
+  depth_reg_loss         depth_gs.py:521-528     mean (five-tap mean of the unmasked neighbours' depth - depth)^2 with
+                                                 the NON-edge Canny mask of the ground-truth image
 
-NOT restated: `depth_reg_loss` (depth_gs.py:521-528) -- it needs the Canny edge mask of the ground-truth image
-(`image2canny`, utils/losses.py:48-70: OpenCV, absent from this image) -- and the planar losses (open3d RANSAC, called
-from nowhere in the model).  `optional_depth_terms` raises for the former instead of guessing.
+`depth_reg_loss` is the one term that is not plain torch ops: the reference's `image2canny` (utils/losses.py:48-58) is
+OpenCV on the host -- a device-to-host copy of the image, `cv2.Canny` and a copy back on every step.  Here the mask
+comes from `gs_fused.image2canny` (four HIP kernels, the rule of `cv::Canny` restated in include/gsraster.h) and the
+term from `gs_fused.depth_reg_loss` (one kernel each way): no image leaves the device.  Both exist on the GPU only,
+so `optional_depth_terms` still raises for the switch on CPU tensors.
+
+NOT restated: the planar losses (open3d RANSAC, called from nowhere in the model).
 """
 from __future__ import annotations
 
@@ -119,9 +125,14 @@ def optional_depth_terms(cfg, step: int, pred_depth: torch.Tensor, gt_depth: tor
     if cfg.use_scaled_est_depth and mono_scale_shift is not None:
         terms["log_depth"] = scaled_log_depth_loss(pred, gt_depth, gt_img, *mono_scale_shift)
     if cfg.use_depth_regularization:
-        raise NotImplementedError(
-            "co-gs depth_reg_loss needs the Canny edge mask of the ground-truth image (utils/losses.py:48-70, OpenCV), "
-            "which this image does not have; the term is off in the reference's default config")
+        if not pred.is_cuda:
+            raise NotImplementedError(
+                "co-gs depth_reg_loss needs the Canny edge mask of the ground-truth image (utils/losses.py:48-58), which "
+                "is computed on the GPU only (gs_fused.image2canny): there is no CPU path for this switch")
+        from gs_fused import depth_reg_loss, image2canny
+
+        # recomputed every step, as in the reference (depth_gs.py:489-491): the mask is not cached per view
+        terms["depth_reg_loss"] = depth_reg_loss(pred, image2canny(gt_img, 50, 150, isEdge1=False))
     if cfg.using_tv_loss and step < 20_000:
         terms["tv_loss"] = tv_loss(pred)
     return terms

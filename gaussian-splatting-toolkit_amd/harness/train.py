@@ -433,7 +433,8 @@ class TrainConfig:
     # co-gs: the OPTIONAL loss terms of `DepthGSModelConfig` (depth_gs.py:93-139), every one off by default as in the
     # reference; restated in harness/cogs_losses.py (plain torch ops, outside the rasterizer's hot path).  With
     # `use_est_depth` the depth branch is the monocular-depth one (:477-531: local Pearson / scaled log-depth / TV
-    # instead of `depth_l1`); `use_depth_regularization` needs OpenCV's Canny and raises.
+    # instead of `depth_l1`); `use_depth_regularization` adds the Canny-masked neighbour-mean term (:521-528) with the
+    # mask and the term computed on the GPU (gs_fused.image2canny, gs_fused.depth_reg_loss) -- on the CPU it raises.
     use_scale_regularization: bool = False
     max_gauss_ratio: float = 10.0
     use_sparse_loss: bool = False

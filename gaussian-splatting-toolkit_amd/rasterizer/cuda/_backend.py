@@ -101,6 +101,10 @@ SYMBOLS = (
     "gsr_mesh_bvh_build",
     "gsr_mesh_distance_query",
     "gsr_mesh_distance_stats",
+    "gsr_canny_workspace_bytes",
+    "gsr_canny",
+    "gsr_depth_reg_forward",
+    "gsr_depth_reg_backward",
     "gsr_debug_count_staged",
     "gsr_debug_wave_trace",
     "gsr_calibrate_valu",
@@ -145,6 +149,7 @@ def _load():
     lib.gsr_tsdf_extract_mesh_workspace_bytes.restype = C.c_size_t
     lib.gsr_mesh_clean_workspace_bytes.restype = C.c_size_t
     lib.gsr_mesh_distance_workspace_bytes.restype = C.c_size_t
+    lib.gsr_canny_workspace_bytes.restype = C.c_size_t
     return lib
 
 

@@ -1074,6 +1074,60 @@ int gsr_mesh_distance_stats(int num_points, const float *distance, float thresho
                             void *workspace, size_t workspace_bytes, double *stats,
                             gsr_stream_t stream);
 
+/* ---- Canny edge mask: what `image2canny` hands the co-gs model ---------
+ * OpenCV's cv::Canny(img8, thres1, thres2) with its defaults (aperture 3, L2gradient = false),
+ * restated; this text is the specification.  All arithmetic is integer: results are exact.
+ * Input: image float [H,W,3] (values expected in [0,1]).  Output: edges uint8 [H,W], 255 / 0.
+ *  1. uint8.  Every channel is u8 = (uint8)trunc(x * 255.0f), the product formed in float32 (what
+ *     NumPy does for `(image * 255.0).astype(np.uint8)`).  Stated difference: a product outside
+ *     [0, 255] saturates and NaN gives 0 (NumPy's cast is platform-dependent there).
+ *  2. Sobel.  3x3, unscaled, replicate border, per channel: dx = right column - left column, dy =
+ *     row below - row above, weights 1 2 1.  norm = |dx| + |dy|; the pixel takes (mag, dx, dy)
+ *     from the channel with the largest norm, the lowest channel index on ties.  mag outside
+ *     the image is 0 (the zero padding applies to the magnitude only, not to the image).
+ *  3. Non-maximum suppression.  low = floor(thres1), high = floor(thres2), swapped if low > high.
+ *     A pixel with mag <= low is no candidate.  Otherwise, with x = |dx|, y = |dy| << 15,
+ *     t22 = x * 13573, t67 = t22 + (x << 16):
+ *       y < t22:  candidate iff mag > mag[left] && mag >= mag[right];
+ *       y > t67:  candidate iff mag > mag[above] && mag >= mag[below];
+ *       else, s = ((dx ^ dy) < 0) ? -1 : 1:
+ *                 candidate iff mag > mag[row-1][col-s] && mag > mag[row+1][col+s].
+ *     A candidate with mag > high is strong, any other candidate weak.
+ *  4. Hysteresis.  A candidate is an edge iff its 8-connected component of candidates holds a
+ *     strong pixel.
+ * H or W of 1 is legal; H * W = 0 launches nothing; H * W < 2^31, H <= 16 * 65535.
+ * Nothing is allocated here: gsr_canny_workspace_bytes(H, W) bytes of scratch (6 per pixel: an
+ * int32 parent, a map byte, a flag byte; 256-byte aligned, no part needs to be zeroed; 0 when the
+ * sizes do not fit).  Nothing is read back, no host loop depends on the data, and the output
+ * is a pure function of the input (the root of a component is its smallest pixel index whatever
+ * the order of the atomics). */
+size_t gsr_canny_workspace_bytes(int img_height, int img_width);
+int gsr_canny(int img_height, int img_width, const float *image, float thres1, float thres2,
+              void *workspace, size_t workspace_bytes, uint8_t *edges, gsr_stream_t stream);
+
+/* ---- depth regularisation of the co-gs model (depth_gs.py:521-528) ------
+ * pred, mask float [H,W] (mask: any values; the model passes the non-edge mask).
+ *   m    = mask * [pred > 0]
+ *   num  = plus-shaped five-tap sum (centre, up, down, left, right; zero padding) of pred * m
+ *   cnt  = the same sum of m;   near = num / (cnt + 1e-8)
+ *   loss = mean over all H W pixels of (near - pred [pred > 0])^2
+ * differentiable w.r.t. pred only (mask and [pred > 0] are constants, as in the source):
+ *   g = 2 (near - pred [pred > 0]) / (H W)
+ *   v_pred[q] = upstream * ( m[q] * sum_{p in plus(q)} g[p] / (cnt[p] + 1e-8) - g[q] [pred[q] > 0] )
+ * NaN propagates as in the source.  The forward sums float64 partials per workgroup in a fixed
+ * order and adds them in one workgroup: the scalar is bit-reproducible.
+ *   scratch  float [2,H,W] (may be NULL for a forward without a backward): the pixel's own share
+ *            g (m / (cnt + 1e-8) - [pred > 0]) and what its neighbours gather, g / (cnt + 1e-8)
+ *   partial  double [GSR_DEPTH_REG_WORKSPACE_DOUBLES]; needs no zeroing
+ * H * W in [1, 2^31). */
+#define GSR_DEPTH_REG_WORKSPACE_DOUBLES 1024
+int gsr_depth_reg_forward(unsigned img_height, unsigned img_width, const float *pred,
+                          const float *mask, float *scratch, double *partial, float *loss_out,
+                          gsr_stream_t stream);
+int gsr_depth_reg_backward(unsigned img_height, unsigned img_width, const float *upstream,
+                           const float *pred, const float *mask, const float *scratch,
+                           float *v_pred, gsr_stream_t stream);
+
 /* ---- measurement hook ---------------------------------------------------------
  * counters: two device uint64 (or NULL = off, the default).  While set, the 16x16
  * compositing kernels add the number of list entries they stage to counters[0]
