@@ -198,7 +198,7 @@ def random_quats(n: int, rng) -> np.ndarray:
 
 
 def seed_model(truth: Dict[str, np.ndarray], n_seed: int, kind: str, seed: int, sh_degree: int = 3,
-               sfm_noise: float = 0.01, random_scale: float = 3.4):
+               sfm_noise: float = 0.01, random_scale: float = 3.4, knn: str = "sklearn", device=None):
     """The model's start as `GaussianSplattingModel.populate_modules` builds it
     (vanilla_gs.py:128-174) -- NOT a copy of the truth:
       kind="sfm":    a sparse point cloud with 8-bit colours, standing in for the COLMAP points
@@ -209,7 +209,9 @@ def seed_model(truth: Dict[str, np.ndarray], n_seed: int, kind: str, seed: int, 
                      (the reference's 10 is for its unit-normalised real scenes; 3.4 encloses
                      this scene's radius-1.5 shells), features_dc = rand.
     Both: log-scales = log(mean distance to the 3 nearest seeds) on all three axes, random unit
-    quaternions, opacity logit(0.1), higher SH bands zero."""
+    quaternions, opacity logit(0.1), higher SH bands zero.
+    `knn`: who finds the neighbours -- "sklearn" (the reference's way, on the host) or "gpu"
+    (`gs_fused.knn_mean_distance` on `device`, default the current CUDA device); same floor."""
     rng = np.random.default_rng(seed)
     K = S.num_sh_bases(sh_degree)
     f32 = np.float32
@@ -224,7 +226,16 @@ def seed_model(truth: Dict[str, np.ndarray], n_seed: int, kind: str, seed: int, 
     else:
         raise ValueError(f"unknown seed kind {kind!r}")
     means = means.astype(f32)
-    avg = np.maximum(knn_mean_distance(means, 3), 1e-7)
+    if knn == "sklearn":
+        avg = knn_mean_distance(means, 3)
+    elif knn == "gpu":
+        from gs_fused import knn_mean_distance as gpu_knn_mean_distance
+
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        avg = gpu_knn_mean_distance(torch.from_numpy(means).to(dev), 3).cpu().numpy()
+    else:
+        raise ValueError(f"unknown knn {knn!r}")
+    avg = np.maximum(avg, 1e-7)
     return {
         "means": means,
         "scales": np.repeat(np.log(avg)[:, None], 3, axis=1).astype(f32),
@@ -376,6 +387,7 @@ class TrainConfig:
     # colour (optionally a subset, init_gaussians); "sfm" / "random" = the reference's own
     # initialisations from a sparse point cloud / uniformly random points (seed_model)
     init: str = "perturbed"
+    seed_knn: str = "sklearn"             # seed_model's neighbour search: "sklearn" (host) or "gpu" (gs_fused.knn)
     means_lr_schedule: bool = False       # exponential decay of the "means" learning rate (method_configs.py:98-104)
     # data parallel only: reduce-scatter -> Adam on this rank's rows -> all-gather (parallel.ShardedAdam)
     # instead of all-reduce + Adam over every row on every rank
@@ -543,7 +555,8 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
     raw = mk()
     rng = np.random.default_rng(cfg.seed + 1)
     if cfg.init in ("sfm", "random"):
-        raw = seed_model(raw, cfg.init_gaussians or 50_000, cfg.init, cfg.seed + 1, cfg.sh_degree)
+        raw = seed_model(raw, cfg.init_gaussians or 50_000, cfg.init, cfg.seed + 1, cfg.sh_degree,
+                         knn=cfg.seed_knn, device=device if cfg.seed_knn == "gpu" else None)
     else:
         # the model starts from the truth with perturbed geometry / washed-out colour
         raw["means"] += rng.standard_normal(raw["means"].shape).astype(np.float32) * 0.01

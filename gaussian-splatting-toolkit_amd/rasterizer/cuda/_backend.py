@@ -105,6 +105,9 @@ SYMBOLS = (
     "gsr_canny",
     "gsr_depth_reg_forward",
     "gsr_depth_reg_backward",
+    "gsr_knn_workspace_bytes",
+    "gsr_knn_build",
+    "gsr_knn_query",
     "gsr_debug_count_staged",
     "gsr_debug_wave_trace",
     "gsr_calibrate_valu",
@@ -150,6 +153,7 @@ def _load():
     lib.gsr_mesh_clean_workspace_bytes.restype = C.c_size_t
     lib.gsr_mesh_distance_workspace_bytes.restype = C.c_size_t
     lib.gsr_canny_workspace_bytes.restype = C.c_size_t
+    lib.gsr_knn_workspace_bytes.restype = C.c_size_t
     return lib
 
 

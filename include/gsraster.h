@@ -1128,6 +1128,54 @@ int gsr_depth_reg_backward(unsigned img_height, unsigned img_width, const float 
                            const float *pred, const float *mask, const float *scratch,
                            float *v_pred, gsr_stream_t stream);
 
+/* ---- k nearest neighbours: points against a point cloud ----------------
+ * What the toolkit's models ask scikit-learn for when they turn seed points into initial scales
+ * (`k_nearest_sklearn`, vanilla_gs.py:136-140, 260-280), as a general query.  Reference points P
+ * float [n,3]; queries Q float [m,3], or Q = P with GSR_KNN_SELF ("self mode": pass P again,
+ * m = n); k in [1, GSR_KNN_MAX_K].  Outputs: distance float [m,k] ascending, index int32 [m,k],
+ * row numbers into P.  The rule:
+ *  1. Arithmetic: float32, every operation rounded on its own (no contraction):
+ *     dx = q.x - p.x (likewise dy, dz), d2 = (dx*dx + dy*dy) + dz*dz, distance = sqrtf(d2).
+ *     tests/knn_reference.py restates the sequence in NumPy.
+ *  2. Order.  The result of a query is the k smallest pairs (d2, row) in lexicographic order: a tie
+ *     in d2 goes to the smaller row.  `index` is therefore a pure function of the input, and
+ *     the tree walk and the exhaustive path agree bit for bit, indices included.
+ *  3. Self mode.  Row i never returns i itself, by index.  The distances are those of the
+ *     reference, which takes k + 1 neighbours and drops column 0 (with duplicate points the k
+ *     smallest distances over j != i are the same numbers).  Stated difference for the indices:
+ *     with duplicate points the reference may drop a twin and keep i; this rule always drops i.
+ *  4. Non-finite input.  A reference point with a non-finite coordinate is left out of the tree
+ *     and counted in state[1] of the build.  A non-finite query gets distance = NaN, index = -1
+ *     in every column and is counted in state[2] of the query.
+ *  5. Too few points.  gsr_knn_query returns GSR_ERANGE, before any kernel is launched, when
+ *     num_usable < k (k + 1 in self mode); num_usable is state[0] of the build as the caller read
+ *     it back (the build synchronises `stream` once to read it itself).  The reference raises
+ *     there too (n_neighbors > n_samples).
+ *  6. m = 0 launches nothing; n = 0 is GSR_EINVAL.
+ * Nothing is allocated here.  gsr_knn_workspace_bytes(what, n, m, k): bytes of the tree (what = 0:
+ * n; kept as long as the cloud is queried), of the build's workspace (1: n), of a tree query's
+ * workspace (2: m and k; the exhaustive query needs none); 0 when the sizes do not fit (n, m in
+ * [1, 2^28], k in [1, 16] for what = 2) or a size query of rocPRIM fails (no device).  All buffers
+ * 256-byte aligned; none needs to be zeroed.
+ *   state  int32 [4]   build: 0 usable reference points, 1 reference points left out;
+ *                      query: 2 non-finite queries (0, 1 and 3 are left alone)
+ * gsr_knn_query with GSR_KNN_EXHAUSTIVE tests every query against every usable reference point
+ * instead of walking the tree (the on-device cross-check, never chosen by the library itself);
+ * both paths evaluate a pair with the same device function. */
+#define GSR_KNN_MAX_K 16
+#define GSR_KNN_EXHAUSTIVE 1
+#define GSR_KNN_SELF 2
+#define GSR_KNN_BYTES_TREE 0
+#define GSR_KNN_BYTES_BUILD 1
+#define GSR_KNN_BYTES_QUERY 2
+size_t gsr_knn_workspace_bytes(int what, int num_points, int num_queries, int k);
+int gsr_knn_build(int num_points, const float *points, void *tree, size_t tree_bytes,
+                  void *workspace, size_t workspace_bytes, int32_t *state, gsr_stream_t stream);
+int gsr_knn_query(int num_points, const void *tree, size_t tree_bytes, int num_usable,
+                  int num_queries, const float *queries, int k, int flags, void *workspace,
+                  size_t workspace_bytes, float *distance, int32_t *index, int32_t *state,
+                  gsr_stream_t stream);
+
 /* ---- measurement hook ---------------------------------------------------------
  * counters: two device uint64 (or NULL = off, the default).  While set, the 16x16
  * compositing kernels add the number of list entries they stage to counters[0]

@@ -45,6 +45,8 @@ def main():
     ap.add_argument("--scene-scale", type=float, nargs=2, default=[0.01, 0.06])
     ap.add_argument("--init", default="perturbed", choices=["perturbed", "sfm", "random"],
                     help="model start: the perturbed truth, or the reference's own initialisations (harness.train.seed_model)")
+    ap.add_argument("--seed-knn", default="sklearn", choices=["sklearn", "gpu"],
+                    help="neighbour search of the sfm / random start: scikit-learn on the host, or gs_fused.knn")
     ap.add_argument("--means-lr-schedule", action="store_true", help="exponential decay of the means' learning rate")
     ap.add_argument("--phase-every", type=int, default=0)
     ap.add_argument("--torch-activations", action="store_true", help="A/B: torch ops for exp/normalise/sigmoid/viewdirs")
@@ -77,7 +79,7 @@ def main():
                       fused_activations=not args.torch_activations, densify=args.densify,
                       init_gaussians=args.init_gaussians, refine=rcfg, log_every=args.log_every,
                       fused_render=args.fused_render, use_graph=args.graph,
-                      scene=args.scene, scene_scale=tuple(args.scene_scale), init=args.init, tex_cell=args.tex_cell, scene_objects=tuple(args.objects), cam_radius=args.cam_radius, scene_extent=args.extent,
+                      scene=args.scene, scene_scale=tuple(args.scene_scale), init=args.init, seed_knn=args.seed_knn, tex_cell=args.tex_cell, scene_objects=tuple(args.objects), cam_radius=args.cam_radius, scene_extent=args.extent,
                       means_lr_schedule=args.means_lr_schedule, phase_every=args.phase_every)
     res = train(cfg, dev, rank, world)
     if world > 1:
