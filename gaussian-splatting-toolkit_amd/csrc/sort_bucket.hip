@@ -36,7 +36,7 @@ constexpr int kCap = 2048;        // largest bucket sorted in LDS by a workgroup
 constexpr int kWaveCap = 1024;    // largest bucket sorted by a single wave
 constexpr int kElemBits = 12;     // an item's position in its chunk / bucket (< 4096)
 constexpr int kHistThreads = 1024;
-constexpr int kScatterWaves = 4, kScatterThreads = 64 * kScatterWaves, kScatterItems = kChunk / kScatterThreads;
+constexpr int kScatterWaves = 8, kScatterThreads = 64 * kScatterWaves, kScatterItems = kChunk / kScatterThreads;
 constexpr int kSortThreads = 256;  // 4 waves: 4 buckets, or one large bucket
 
 __device__ __forceinline__ unsigned depth_key(const float *__restrict__ depths, const int *__restrict__ radii,
@@ -327,6 +327,7 @@ __device__ __forceinline__ unsigned rank_round(const unsigned (&v)[kI], unsigned
       const unsigned below = (unsigned)__popcll(peers & lt);
       const unsigned prev = S.cnt[w][d];  // every peer reads before the group's first lane writes
       rank[i] = prev + below;
+      asm volatile("" : "+v"(rank[i]));  // (taken here, see scatter_kernel)
       if (live && below == 0) S.cnt[w][d] = prev + (unsigned)__popcll(peers);
     }
   }
@@ -398,6 +399,9 @@ __device__ __forceinline__ void place(int *__restrict__ order, const Gather &ga,
 // the last two from WAVE-PRIVATE 16-bit counters over a sweep of 4096 buckets (wave-level matching on the 12 bucket
 // bits gives the rank among the lanes of a round; the counter carries it across rounds): stable without sorting the
 // chunk.  B > 4096: one sweep per 4096 buckets over the same registers.
+// Eight waves of 8 items per lane: the grid has fewer workgroups than the chip has CUs, so a workgroup's waves are all
+// a SIMD has to switch between.  (Four waves of 16 items: one wave per SIMD, 253 VGPRs, spilled SGPRs.)  The counters
+// of eight waves (64 KB) and the slots (16 KB) fit the CU's 160 KB of LDS; nothing else is resident beside them.
 constexpr int kSweep = 4096;
 
 __device__ __forceinline__ unsigned long long match12(const unsigned d, const bool in) {
@@ -419,15 +423,16 @@ __global__ __launch_bounds__(kScatterThreads) void scatter_kernel(
     const unsigned *__restrict__ totals,
     uint2 *__restrict__ pairs, int *__restrict__ order, unsigned *__restrict__ bucket_base,
     int *__restrict__ stats, const Gather ga) {
-  __shared__ unsigned arr[kSweep];
+  __shared__ unsigned arr[kSweep];  // (first the bucket map: the buckets are known before the first slot is written)
   __shared__ unsigned short cnt[kScatterWaves][kSweep];
   __shared__ unsigned s_sum[kScatterWaves], s_max[kScatterWaves];
-  __shared__ OctaveMap map[256];
+  static_assert(sizeof(OctaveMap) * 256 <= sizeof(arr), "the map borrows arr");
+  OctaveMap *map = reinterpret_cast<OctaveMap *>(arr);
   constexpr int kI = kScatterItems, seg = kChunk / kScatterWaves, kPer = kSweep / kScatterThreads;
   const int B = 1 << log2_buckets;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const unsigned long long lt = (1ull << lane) - 1ull;
-  map[tid] = map_in[tid];
+  if (tid < 256) map[tid] = map_in[tid];
   const int base = blockIdx.x * kChunk;
   const int m = min(kChunk, n - base);
   unsigned key[kI], bkt[kI], rank[kI];
@@ -470,6 +475,7 @@ __global__ __launch_bounds__(kScatterThreads) void scatter_kernel(
       const unsigned below = (unsigned)__popcll(peers & lt);
       const unsigned prev = cnt[w][d];  // every peer reads before the group's first lane writes
       rank[i] = in ? prev + below : rank[i];
+      asm volatile("" : "+v"(rank[i]));  // (taken here: deferred to its use, every item keeps prev, below and d alive)
       if (in && below == 0) cnt[w][d] = (unsigned short)(prev + (unsigned)__popcll(peers));
     }
     __syncthreads();
@@ -487,14 +493,16 @@ __global__ __launch_bounds__(kScatterThreads) void scatter_kernel(
         if (lane >= o) incl += t;
       }
       if (lane == 63) s_sum[w] = incl;
+      // two adjacent buckets per 32-bit word: a chunk holds 4096 items, so neither half carries into the other
+      unsigned *c2 = reinterpret_cast<unsigned *>(&cnt[0][0]);
 #pragma unroll
-      for (int q = 0; q < kSweep / kScatterThreads; ++q) {  // (bucket q * threads + tid: conflict-free)
-        const int d = q * kScatterThreads + tid;
+      for (int q = 0; q < kSweep / 2 / kScatterThreads; ++q) {  // (word q * threads + tid: conflict-free)
+        const int d2 = q * kScatterThreads + tid;
         unsigned run = 0;
 #pragma unroll
         for (int k = 0; k < kScatterWaves; ++k) {
-          const unsigned c = cnt[k][d];
-          cnt[k][d] = (unsigned short)run;
+          const unsigned c = c2[k * (kSweep / 2) + d2];
+          c2[k * (kSweep / 2) + d2] = run;
           run += c;
         }
       }
@@ -597,6 +605,7 @@ __device__ __forceinline__ bool wave_sort(const unsigned s, const int m, const u
         const unsigned below = (unsigned)__popcll(peers & lt);
         const unsigned prev = W.cnt[d];
         rank[i] = prev + below;
+        asm volatile("" : "+v"(rank[i]));  // (taken here, see scatter_kernel)
         if (live && below == 0) W.cnt[d] = prev + (unsigned)__popcll(peers);
       }
     }
@@ -630,7 +639,7 @@ __device__ __forceinline__ bool wave_sort(const unsigned s, const int m, const u
 
 // The slow path of a bucket above kCap items: LSD rounds through HBM (pairs <-> pairs2), one workgroup.
 __device__ __noinline__ void sort_large_bucket(const unsigned s, const unsigned m, uint2 *pairs, uint2 *pairs2,
-                                               int *__restrict__ order, const Gather &ga, unsigned *run,
+                                               int *__restrict__ order, const Gather ga, unsigned *run,
                                                SortShared<4> &S) {
   constexpr int kI = 4, kTile = kI * kSortThreads;  // (small tiles: few registers; speed is not the point here)
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;

@@ -60,6 +60,27 @@ struct SlabItems {
   RowParams par[kSlab];
 };
 
+// P3's slab.  The records and row parameters are read only while a batch's items are derived (item_of); the batch's
+// item table, its sorted order and the start-mask block counts are first written after that, behind a barrier, so
+// they take the same 12 KB: 22 KB of LDS per workgroup instead of 34 KB, seven workgroups on a CU instead of four.
+// A slab of more than kItems items reloads its records at the top of every batch after the first.
+struct EmitSlab {
+  int pref[kSlab];
+  int gid[kSlab];
+  union {
+    struct {
+      SplatRec rec[kSlab];
+      RowParams par[kSlab];
+    };
+    struct {
+      unsigned it_a[kItems];             // row | t0 << 16
+      unsigned it_b[kItems];             // count | owner thread << 16
+      unsigned short sorted[kItems];
+      int blkfirst[kMaskBlocks];         // starts before the block
+    };
+  };
+};
+
 // exclusive prefix of v over the 256 threads of the workgroup (and the total); two barriers
 __device__ __forceinline__ int block_excl(const int v, int *__restrict__ wsum, int &total) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -95,7 +116,8 @@ __device__ __forceinline__ long long block_excl64(const long long v, long long *
   return base + incl - v;
 }
 
-__device__ __forceinline__ int load_slab(SlabItems &W, int *__restrict__ wsum, const int i, const int n,
+template <class Slab>
+__device__ __forceinline__ int load_slab(Slab &W, int *__restrict__ wsum, const int i, const int n,
                                          const int *__restrict__ order, const SplatRec *__restrict__ recs) {
   const int tid = threadIdx.x;
   SplatRec rec{0.f, 0.f, 1.f, 0.f, 1.f, -1.f, 0u, 0u};
@@ -115,7 +137,8 @@ __device__ __forceinline__ int load_slab(SlabItems &W, int *__restrict__ wsum, c
 }
 
 // item q of the slab -> owner thread k, tile row, tile range [t0, t1)
-__device__ __forceinline__ void item_of(const SlabItems &W, const int q, const int total, int &k, int &ty, int &t0,
+template <class Slab>
+__device__ __forceinline__ void item_of(const Slab &W, const int q, const int total, int &k, int &ty, int &t0,
                                         int &t1) {
   k = 0;
 #pragma unroll
@@ -218,15 +241,14 @@ __global__ __launch_bounds__(kSlab) void emit_kernel(const Dims D, const int cap
                                                      int *__restrict__ row_chunk_start, int *__restrict__ count_out,
                                                      unsigned short *__restrict__ tx_out, int *__restrict__ gid_out) {
   constexpr int kR = kItems / kSlab;     // items per thread and batch
-  __shared__ SlabItems W;
-  __shared__ unsigned it_a[kItems];      // row | t0 << 16
-  __shared__ unsigned it_b[kItems];      // count | owner thread << 16
-  __shared__ unsigned short sorted[kItems];
+  __shared__ EmitSlab W;
+  unsigned *it_a = W.it_a, *it_b = W.it_b;
+  unsigned short *sorted = W.sorted;
+  int *blkfirst = W.blkfirst;
   __shared__ int sout[kItems + 1];       // entry offset (within the batch) of sorted item s
   // start masks: bit e & 63 of word e >> 6 is set where a sorted item's first entry sits; the item
   // that owns entry e is (#starts at or before e) - 1: two popcounts instead of a binary search
   __shared__ unsigned long long smask[kMaskBlocks];
-  __shared__ int blkfirst[kMaskBlocks];  // starts before the block
   __shared__ int wsum[4];
   __shared__ long long wsum64[4];
   extern __shared__ int rows_lds[];      // 7 arrays of tiles_y ints
@@ -265,12 +287,31 @@ __global__ __launch_bounds__(kSlab) void emit_kernel(const Dims D, const int cap
 
   for (int qa = 0; qa < total; qa += kItems) {
     const int nb = total - qa < kItems ? total - qa : kItems;
+    if (qa > 0) {  // the item table of the batch before took the records' place
+      const int i = slab * kSlab + tid;
+      SplatRec rec{0.f, 0.f, 1.f, 0.f, 1.f, -1.f, 0u, 0u};
+      if (i < D.n) rec = recs[W.gid[tid]];
+      W.rec[tid] = rec;
+      W.par[tid] = make_row_params(rec);
+    }
     for (int r = tid; r < 4 * ny; r += kSlab) wcnt[r] = 0;
     for (int r = tid; r < ny; r += kSlab) bentc[r] = 0;
     __syncthreads();
     // 1. the batch's items; wave w ranks the w-th contiguous quarter of them (rounded up to whole
     //    rounds of 64: a short batch still keeps all four waves busy) by row, in item order
     const int per = ((nb + 255) >> 8) << 6;  // items per wave
+    unsigned ia[kR], ib[kR];
+#pragma unroll
+    for (int r = 0; r < kR; ++r) {
+      ia[r] = ib[r] = 0u;
+      if (r * 64 >= per) continue;  // (uniform)
+      const int idx = w * per + r * 64 + lane;
+      int k = 0, ty = 0, t0 = 0, t1 = 0;
+      if (idx < nb) item_of(W, qa + idx, total, k, ty, t0, t1);
+      ia[r] = (unsigned)ty | ((unsigned)t0 << 16);
+      ib[r] = (unsigned)(t1 - t0) | ((unsigned)k << 16);
+    }
+    __syncthreads();  // (every record has been read: the item table goes where they were)
     int rank[kR], myrow[kR];
 #pragma unroll
     for (int r = 0; r < kR; ++r) {
@@ -278,12 +319,10 @@ __global__ __launch_bounds__(kSlab) void emit_kernel(const Dims D, const int cap
       rank[r] = 0;
       if (r * 64 >= per) continue;  // (uniform)
       const int idx = w * per + r * 64 + lane;
-      int k = 0, ty = 0, t0 = 0, t1 = 0;
-      if (idx < nb) item_of(W, qa + idx, total, k, ty, t0, t1);
-      const int cnt = t1 - t0;
+      const int ty = (int)(ia[r] & 0xffffu), cnt = (int)(ib[r] & 0xffffu);
       if (idx < nb) {
-        it_a[idx] = (unsigned)ty | ((unsigned)t0 << 16);
-        it_b[idx] = (unsigned)cnt | ((unsigned)k << 16);
+        it_a[idx] = ia[r];
+        it_b[idx] = ib[r];
       }
       const bool live = idx < nb && cnt > 0;
       unsigned long long peers = __ballot(live);
@@ -295,6 +334,7 @@ __global__ __launch_bounds__(kSlab) void emit_kernel(const Dims D, const int cap
       const int below = __popcll(peers & lt);
       const int prev = live ? wcnt[w * ny + ty] : 0;  // every peer reads before the group's first lane writes
       rank[r] = prev + below;
+      asm volatile("" : "+v"(rank[r]));  // (taken here, not where it is used: see colscatter_kernel)
       if (live && below == 0) wcnt[w * ny + ty] = prev + __popcll(peers);
       if (live) atomicAdd(&bentc[ty], cnt);
       myrow[r] = live ? ty : -1;
@@ -592,18 +632,21 @@ __global__ __launch_bounds__(256) void colscatter_kernel(const Dims D, const int
   __syncthreads();
   int key_bits = 1;
   while ((1 << key_bits) < D.tiles_x) ++key_bits;
-  int key[kRounds], gid[kRounds], rank[kRounds];
+  // an entry's column (< 1024; kDead: past the chunk's end) and, from its ranking on, its rank (< 4096) above it
+  constexpr unsigned kDead = 0xffffu;
+  unsigned key[kRounds];
+  int gid[kRounds];
 #pragma unroll
   for (int r = 0; r < kRounds; ++r) {
     const int e = w * (kChunk / 4) + r * 64 + lane;
     const bool live = e < cnt;
-    key[r] = live ? (int)tx_in[beg + e] : -1;
+    key[r] = live ? (unsigned)tx_in[beg + e] : kDead;
     gid[r] = live ? gid_in[beg + e] : 0;
   }
 #pragma unroll
   for (int r = 0; r < kRounds; ++r) {
-    const bool live = key[r] >= 0;
-    const unsigned k = live ? (unsigned)key[r] : 0u;
+    const bool live = key[r] != kDead;
+    const unsigned k = live ? key[r] : 0u;
     unsigned long long peers = __ballot(live);
     for (int bit = 0; bit < key_bits; ++bit) {
       const bool b = (k >> bit) & 1u;
@@ -612,7 +655,10 @@ __global__ __launch_bounds__(256) void colscatter_kernel(const Dims D, const int
     }
     const int below = __popcll(peers & lt);
     const int prev = live ? wcnt[w][k] : 0;  // every peer reads before the group's first lane writes
-    rank[r] = prev + below;
+    key[r] |= (unsigned)(prev + below) << 16;
+    // the rank is taken here: left to the compiler the sum sinks below the barrier to its use, and every round keeps
+    // its counter's address, its count and its peers in registers until then (112 VGPRs, four waves per SIMD; 52 so)
+    asm volatile("" : "+v"(key[r]));
     if (live && below == 0) wcnt[w][k] = prev + __popcll(peers);
   }
   __syncthreads();
@@ -653,10 +699,11 @@ __global__ __launch_bounds__(256) void colscatter_kernel(const Dims D, const int
   __syncthreads();
 #pragma unroll
   for (int r = 0; r < kRounds; ++r) {
-    if (key[r] >= 0) {
-      const int pos = wcnt[w][key[r]] + rank[r];
+    const unsigned c = key[r] & 0xffffu;
+    if (c != kDead) {
+      const int pos = wcnt[w][c] + (int)(key[r] >> 16);
       s_gid[pos] = gid[r];
-      s_stx[pos] = (unsigned short)key[r];
+      s_stx[pos] = (unsigned short)c;
     }
   }
   __syncthreads();
