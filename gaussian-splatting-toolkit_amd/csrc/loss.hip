@@ -37,14 +37,28 @@ __constant__ float kW[kWin] = {0.00102838f, 0.00759876f, 0.03600077f, 0.10936069
                                0.00102838f};
 constexpr float kC1 = 0.01f * 0.01f, kC2 = 0.03f * 0.03f;
 
+// The masked heads (kMasked) follow the models' `pred * mask`, `gt * mask` in front of the loss
+// (vanilla_gs.py:915-924, surface_gs.py:917-925, depth_gs.py:424-437): the products are ROUNDED VALUES, as the
+// torch multiplies leave them in memory.  Contracted into the subtraction that follows, `pred * m - gt * m` would
+// be an fma on an unrounded product and sign(x - y) could differ from torch's where pred == gt.
+__device__ __forceinline__ float mul_rounded(const float a, const float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
 // img: [H,W,3] interleaved.  maps: [3 derivative kinds][3 channels][Hv][Wv] planar.
 // sums[0] += sum |x-y| over the tile's own pixels, sums[1] += sum S over its valid outputs.
 // clamp_pred: the prediction is min(pred, 1) (the models clamp the rendered image at 1
 // before the loss, vanilla_gs.py:857 `torch.clamp(rgb, max=1.0)`; folding it in here
 // saves that op and its three-kernel backward).
+// kMasked: x = min(pred, 1) * m and y = gt * m with m = mask[H,W] (one value per pixel, any real number), formed
+// here, in the staging loop -- one more global read per staged pixel, no LDS plane, nothing per blur tap; the
+// divisors stay those of the whole image.  `mask` is not read otherwise.
+template <bool kMasked>
 __global__ __launch_bounds__(256) void l1_ssim_fwd_kernel(
     const int H, const int W, const float lambda, const int clamp_pred, const float *__restrict__ pred,
-    const float *__restrict__ gt, float *__restrict__ maps, double *__restrict__ sums) {
+    const float *__restrict__ gt, const float *__restrict__ mask, float *__restrict__ maps,
+    double *__restrict__ sums) {
   __shared__ float sx[kIH][kIW + 1], sy[kIH][kIW + 1];
   __shared__ float hb[5][kIH][kTW + 1];
   __shared__ float red[2][4];
@@ -64,6 +78,11 @@ __global__ __launch_bounds__(256) void l1_ssim_fwd_kernel(
       x = pred[o];
       if (clamp_pred) x = fminf(x, 1.f);
       y = gt[o];
+      if constexpr (kMasked) {
+        const float m = mask[(size_t)gy * W + gx];
+        x = mul_rounded(x, m);
+        y = mul_rounded(y, m);
+      }
       if (r < kTH && q < kTW) l1 += fabsf(x - y);  // every pixel belongs to exactly one tile
     }
     sx[r][q] = x;
@@ -175,10 +194,12 @@ __global__ __launch_bounds__(64) void l1_ssim_finalize_kernel(const int H, const
 }
 
 // v_pred = up * [ (1-lambda) sign(x-y)/(3HW) - lambda/(3 Hv Wv) * ( blurT(Dmu) + 2x blurT(D11) + y blurT(D12) ) ]
+// kMasked: the same expression in x = min(pred, 1) * m and y = gt * m, times m (d x / d pred) at the end.
+template <bool kMasked>
 __global__ __launch_bounds__(256) void l1_ssim_bwd_kernel(
     const int H, const int W, const float lambda, const int clamp_pred, const float *__restrict__ upstream,
-    const float *__restrict__ pred, const float *__restrict__ gt, const float *__restrict__ maps,
-    float *__restrict__ v_pred) {
+    const float *__restrict__ pred, const float *__restrict__ gt, const float *__restrict__ mask,
+    const float *__restrict__ maps, float *__restrict__ v_pred) {
   __shared__ float sm[3][kIH][kIW + 1];
   __shared__ float hb[3][kIH][kTW + 1];
 
@@ -236,13 +257,54 @@ __global__ __launch_bounds__(256) void l1_ssim_bwd_kernel(
       g2 += w * hb[2][r + kHalo - k][q];
     }
     const size_t o = ((size_t)gy * W + gx) * 3 + c;
-    const float xr = pred[o], y = gt[o];
-    const float x = clamp_pred ? fminf(xr, 1.f) : xr;
+    const float xr = pred[o];
+    float y = gt[o];
+    float x = clamp_pred ? fminf(xr, 1.f) : xr;
+    float m = 1.f;
+    if constexpr (kMasked) {
+      m = mask[(size_t)gy * W + gx];
+      x = mul_rounded(x, m);
+      y = mul_rounded(y, m);
+    }
     const float d = x - y;
     const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-    const float g = k_l1 * sgn + k_ss * (g0 + 2.f * x * g1 + y * g2);
+    float g = k_l1 * sgn + k_ss * (g0 + 2.f * x * g1 + y * g2);
+    if constexpr (kMasked) g = mul_rounded(m, g);
     v_pred[o] = (clamp_pred && xr > 1.f) ? 0.f : g;  // clamp(max=1) passes the gradient where pred <= 1
   }
+}
+
+}  // namespace
+
+namespace {
+
+// mask == nullptr: the unmasked kernels
+int l1_ssim_forward_launch(unsigned img_height, unsigned img_width, float ssim_lambda, int clamp_pred,
+                           const float *pred, const float *gt, const float *mask, float *maps, double *sums,
+                           float *loss_out, float *terms_out, hipStream_t s) {
+  if (int zrc = gsr_zero_async(sums, GSR_LOSS_WORKSPACE_DOUBLES * sizeof(double), s)) return zrc;
+  const dim3 grd(gsr_cdiv(img_width, kTW), gsr_cdiv(img_height, kTH), 3);
+  if (mask)
+    hipLaunchKernelGGL(l1_ssim_fwd_kernel<true>, grd, dim3(256), 0, s, (int)img_height, (int)img_width, ssim_lambda,
+                       clamp_pred, pred, gt, mask, maps, sums);
+  else
+    hipLaunchKernelGGL(l1_ssim_fwd_kernel<false>, grd, dim3(256), 0, s, (int)img_height, (int)img_width, ssim_lambda,
+                       clamp_pred, pred, gt, mask, maps, sums);
+  hipLaunchKernelGGL(l1_ssim_finalize_kernel, dim3(1), dim3(64), 0, s, (int)img_height, (int)img_width,
+                     ssim_lambda, (const double *)sums, loss_out, terms_out);
+  return GSR_OK;
+}
+
+void l1_ssim_backward_launch(unsigned img_height, unsigned img_width, float ssim_lambda, int clamp_pred,
+                             const float *upstream, const float *pred, const float *gt, const float *mask,
+                             const float *maps, float *v_pred, hipStream_t s) {
+  const dim3 grd(gsr_cdiv(img_width, kTW), gsr_cdiv(img_height, kTH), 3);
+  if (mask)
+    hipLaunchKernelGGL(l1_ssim_bwd_kernel<true>, grd, dim3(256), 0, s, (int)img_height, (int)img_width, ssim_lambda,
+                       clamp_pred, upstream, pred, gt, mask, maps, v_pred);
+  else
+    hipLaunchKernelGGL(l1_ssim_bwd_kernel<false>, grd, dim3(256), 0, s, (int)img_height, (int)img_width, ssim_lambda,
+                       clamp_pred, upstream, pred, gt, mask, maps, v_pred);
 }
 
 }  // namespace
@@ -252,14 +314,23 @@ GSR_EXPORT int gsr_l1_ssim_forward(unsigned img_height, unsigned img_width, floa
                                    double *sums, float *loss_out, float *terms_out, gsr_stream_t stream) {
   GSR_REQUIRE(img_height > kHalo && img_width > kHalo, "l1_ssim_forward: image must be larger than 10x10");
   GSR_REQUIRE(pred && gt && maps && sums && loss_out, "l1_ssim_forward: null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  if (int zrc = gsr_zero_async(sums, GSR_LOSS_WORKSPACE_DOUBLES * sizeof(double), s)) return zrc;
-  const dim3 grd(gsr_cdiv(img_width, kTW), gsr_cdiv(img_height, kTH), 3);
-  hipLaunchKernelGGL(l1_ssim_fwd_kernel, grd, dim3(256), 0, s, (int)img_height, (int)img_width, ssim_lambda,
-                     clamp_pred, pred, gt, maps, sums);
-  hipLaunchKernelGGL(l1_ssim_finalize_kernel, dim3(1), dim3(64), 0, s, (int)img_height, (int)img_width,
-                     ssim_lambda, (const double *)sums, loss_out, terms_out);
+  if (int rc = l1_ssim_forward_launch(img_height, img_width, ssim_lambda, clamp_pred, pred, gt, nullptr, maps, sums,
+                                      loss_out, terms_out, (hipStream_t)stream))
+    return rc;
   GSR_CHECK_LAUNCH("l1_ssim_forward");
+  return GSR_OK;
+}
+
+GSR_EXPORT int gsr_l1_ssim_masked_forward(unsigned img_height, unsigned img_width, float ssim_lambda,
+                                          int clamp_pred, const float *pred, const float *gt, const float *mask,
+                                          float *maps, double *sums, float *loss_out, float *terms_out,
+                                          gsr_stream_t stream) {
+  GSR_REQUIRE(img_height > kHalo && img_width > kHalo, "l1_ssim_masked_forward: image must be larger than 10x10");
+  GSR_REQUIRE(pred && gt && mask && maps && sums && loss_out, "l1_ssim_masked_forward: null pointer");
+  if (int rc = l1_ssim_forward_launch(img_height, img_width, ssim_lambda, clamp_pred, pred, gt, mask, maps, sums,
+                                      loss_out, terms_out, (hipStream_t)stream))
+    return rc;
+  GSR_CHECK_LAUNCH("l1_ssim_masked_forward");
   return GSR_OK;
 }
 
@@ -268,10 +339,21 @@ GSR_EXPORT int gsr_l1_ssim_backward(unsigned img_height, unsigned img_width, flo
                                     const float *maps, float *v_pred, gsr_stream_t stream) {
   GSR_REQUIRE(img_height > kHalo && img_width > kHalo, "l1_ssim_backward: image must be larger than 10x10");
   GSR_REQUIRE(upstream && pred && gt && maps && v_pred, "l1_ssim_backward: null pointer");
-  const dim3 grd(gsr_cdiv(img_width, kTW), gsr_cdiv(img_height, kTH), 3);
-  hipLaunchKernelGGL(l1_ssim_bwd_kernel, grd, dim3(256), 0, (hipStream_t)stream, (int)img_height,
-                     (int)img_width, ssim_lambda, clamp_pred, upstream, pred, gt, maps, v_pred);
+  l1_ssim_backward_launch(img_height, img_width, ssim_lambda, clamp_pred, upstream, pred, gt, nullptr, maps, v_pred,
+                          (hipStream_t)stream);
   GSR_CHECK_LAUNCH("l1_ssim_backward");
+  return GSR_OK;
+}
+
+GSR_EXPORT int gsr_l1_ssim_masked_backward(unsigned img_height, unsigned img_width, float ssim_lambda,
+                                           int clamp_pred, const float *upstream, const float *pred,
+                                           const float *gt, const float *mask, const float *maps, float *v_pred,
+                                           gsr_stream_t stream) {
+  GSR_REQUIRE(img_height > kHalo && img_width > kHalo, "l1_ssim_masked_backward: image must be larger than 10x10");
+  GSR_REQUIRE(upstream && pred && gt && mask && maps && v_pred, "l1_ssim_masked_backward: null pointer");
+  l1_ssim_backward_launch(img_height, img_width, ssim_lambda, clamp_pred, upstream, pred, gt, mask, maps, v_pred,
+                          (hipStream_t)stream);
+  GSR_CHECK_LAUNCH("l1_ssim_masked_backward");
   return GSR_OK;
 }
 
@@ -284,29 +366,49 @@ GSR_EXPORT int gsr_l1_ssim_backward(unsigned img_height, unsigned img_width, flo
 // weight = 1 - ssim_lambda.  One streaming kernel each way, no maps, no blur.
 namespace {
 
+// kMasked: element e of the interleaved [H,W,3] image belongs to pixel e / 3.  The float4 at elements 4i .. 4i+3
+// starts in pixel p = 4i / 3 at channel r = 4i - 3p and always ends in pixel p + 1 (r + 3 >= 3, r + 3 < 6): two
+// mask reads, element k takes the second one from k >= 3 - r on.  p + 1 holds element 4i + 3 < n: in bounds.
+template <bool kMasked>
 __global__ __launch_bounds__(256) void l1_fwd_kernel(const long long n4, const long long n, const int clamp_pred,
                                                      const float *__restrict__ pred, const float *__restrict__ gt,
-                                                     double *__restrict__ sums) {
+                                                     const float *__restrict__ mask, double *__restrict__ sums) {
   __shared__ float red[4];
   float acc = 0.f;
   const float4 *p4 = reinterpret_cast<const float4 *>(pred);
   const float4 *g4 = reinterpret_cast<const float4 *>(gt);
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
     float4 x = p4[i];
-    const float4 y = g4[i];
+    float4 y = g4[i];
     if (clamp_pred) {
       x.x = fminf(x.x, 1.f);
       x.y = fminf(x.y, 1.f);
       x.z = fminf(x.z, 1.f);
       x.w = fminf(x.w, 1.f);
     }
+    if constexpr (kMasked) {
+      const long long p = (4 * i) / 3;
+      const int r = (int)(4 * i - 3 * p);
+      const float m0 = mask[p], m1 = mask[p + 1];
+      const float mx = m0, my = r < 2 ? m0 : m1, mz = r < 1 ? m0 : m1, mw = m1;
+      x.x = mul_rounded(x.x, mx), y.x = mul_rounded(y.x, mx);
+      x.y = mul_rounded(x.y, my), y.y = mul_rounded(y.y, my);
+      x.z = mul_rounded(x.z, mz), y.z = mul_rounded(y.z, mz);
+      x.w = mul_rounded(x.w, mw), y.w = mul_rounded(y.w, mw);
+    }
     acc += (fabsf(x.x - y.x) + fabsf(x.y - y.y)) + (fabsf(x.z - y.z) + fabsf(x.w - y.w));
   }
   if (blockIdx.x == 0) {  // the (at most three) elements behind the last float4
     const long long i = 4 * n4 + threadIdx.x;
     if (i < n) {
-      const float x = clamp_pred ? fminf(pred[i], 1.f) : pred[i];
-      acc += fabsf(x - gt[i]);
+      float x = clamp_pred ? fminf(pred[i], 1.f) : pred[i];
+      float y = gt[i];
+      if constexpr (kMasked) {
+        const float m = mask[i / 3];
+        x = mul_rounded(x, m);
+        y = mul_rounded(y, m);
+      }
+      acc += fabsf(x - y);
     }
   }
 #pragma unroll
@@ -327,18 +429,48 @@ __global__ __launch_bounds__(64) void l1_finalize_kernel(const long long n, cons
   if (threadIdx.x == 0) *loss_out = (float)((double)weight * (a / (double)n));
 }
 
+template <bool kMasked>
 __global__ __launch_bounds__(256) void l1_bwd_kernel(const long long n, const float weight, const int clamp_pred,
                                                      const float *__restrict__ upstream,
                                                      const float *__restrict__ pred, const float *__restrict__ gt,
-                                                     float *__restrict__ v_pred) {
+                                                     const float *__restrict__ mask, float *__restrict__ v_pred) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const float xr = pred[i];
-  const float x = clamp_pred ? fminf(xr, 1.f) : xr;
-  const float d = x - gt[i];
+  float x = clamp_pred ? fminf(xr, 1.f) : xr;
+  float y = gt[i];
+  float m = 1.f;
+  if constexpr (kMasked) {
+    m = mask[i / 3];
+    x = mul_rounded(x, m);
+    y = mul_rounded(y, m);
+  }
+  const float d = x - y;
   const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
   const float k = upstream[0] * weight / (float)n;
-  v_pred[i] = (clamp_pred && xr > 1.f) ? 0.f : k * sgn;
+  float g = k * sgn;
+  if constexpr (kMasked) g = mul_rounded(m, g);
+  v_pred[i] = (clamp_pred && xr > 1.f) ? 0.f : g;
+}
+
+}  // namespace
+
+namespace {
+
+int l1_forward_launch(long long num_values, float weight, int clamp_pred, const float *pred, const float *gt,
+                      const float *mask, double *sums, float *loss_out, hipStream_t s) {
+  if (int zrc = gsr_zero_async(sums, GSR_LOSS_SUM_SLOTS * sizeof(double), s)) return zrc;
+  const long long n4 = num_values / 4;
+  const unsigned blocks = (unsigned)std::max<long long>(1, std::min<long long>((n4 + 1023) / 1024, 4096));
+  if (mask)
+    hipLaunchKernelGGL(l1_fwd_kernel<true>, dim3(blocks), dim3(256), 0, s, n4, num_values, clamp_pred, pred, gt, mask,
+                       sums);
+  else
+    hipLaunchKernelGGL(l1_fwd_kernel<false>, dim3(blocks), dim3(256), 0, s, n4, num_values, clamp_pred, pred, gt, mask,
+                       sums);
+  hipLaunchKernelGGL(l1_finalize_kernel, dim3(1), dim3(64), 0, s, num_values, weight, (const double *)sums,
+                     loss_out);
+  return GSR_OK;
 }
 
 }  // namespace
@@ -348,14 +480,23 @@ GSR_EXPORT int gsr_l1_forward(long long num_values, float weight, int clamp_pred
   GSR_REQUIRE(num_values > 0, "l1_forward: empty image");
   GSR_REQUIRE(pred && gt && sums && loss_out, "l1_forward: null pointer");
   GSR_REQUIRE(((uintptr_t)pred & 15) == 0 && ((uintptr_t)gt & 15) == 0, "l1_forward: images must be 16-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  if (int zrc = gsr_zero_async(sums, GSR_LOSS_SUM_SLOTS * sizeof(double), s)) return zrc;
-  const long long n4 = num_values / 4;
-  const unsigned blocks = (unsigned)std::max<long long>(1, std::min<long long>((n4 + 1023) / 1024, 4096));
-  hipLaunchKernelGGL(l1_fwd_kernel, dim3(blocks), dim3(256), 0, s, n4, num_values, clamp_pred, pred, gt, sums);
-  hipLaunchKernelGGL(l1_finalize_kernel, dim3(1), dim3(64), 0, s, num_values, weight, (const double *)sums,
-                     loss_out);
+  if (int rc = l1_forward_launch(num_values, weight, clamp_pred, pred, gt, nullptr, sums, loss_out,
+                                 (hipStream_t)stream))
+    return rc;
   GSR_CHECK_LAUNCH("l1_forward");
+  return GSR_OK;
+}
+
+GSR_EXPORT int gsr_l1_masked_forward(long long num_values, float weight, int clamp_pred, const float *pred,
+                                     const float *gt, const float *mask, double *sums, float *loss_out,
+                                     gsr_stream_t stream) {
+  GSR_REQUIRE(num_values > 0 && num_values % 3 == 0, "l1_masked_forward: expected an [H,W,3] image");
+  GSR_REQUIRE(pred && gt && mask && sums && loss_out, "l1_masked_forward: null pointer");
+  GSR_REQUIRE(((uintptr_t)pred & 15) == 0 && ((uintptr_t)gt & 15) == 0,
+              "l1_masked_forward: images must be 16-byte aligned");
+  if (int rc = l1_forward_launch(num_values, weight, clamp_pred, pred, gt, mask, sums, loss_out, (hipStream_t)stream))
+    return rc;
+  GSR_CHECK_LAUNCH("l1_masked_forward");
   return GSR_OK;
 }
 
@@ -363,9 +504,21 @@ GSR_EXPORT int gsr_l1_backward(long long num_values, float weight, int clamp_pre
                                const float *pred, const float *gt, float *v_pred, gsr_stream_t stream) {
   GSR_REQUIRE(num_values > 0, "l1_backward: empty image");
   GSR_REQUIRE(upstream && pred && gt && v_pred, "l1_backward: null pointer");
-  hipLaunchKernelGGL(l1_bwd_kernel, dim3((unsigned)((num_values + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     num_values, weight, clamp_pred, upstream, pred, gt, v_pred);
+  hipLaunchKernelGGL(l1_bwd_kernel<false>, dim3((unsigned)((num_values + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, num_values, weight, clamp_pred, upstream, pred, gt, (const float *)nullptr,
+                     v_pred);
   GSR_CHECK_LAUNCH("l1_backward");
+  return GSR_OK;
+}
+
+GSR_EXPORT int gsr_l1_masked_backward(long long num_values, float weight, int clamp_pred, const float *upstream,
+                                      const float *pred, const float *gt, const float *mask, float *v_pred,
+                                      gsr_stream_t stream) {
+  GSR_REQUIRE(num_values > 0 && num_values % 3 == 0, "l1_masked_backward: expected an [H,W,3] image");
+  GSR_REQUIRE(upstream && pred && gt && mask && v_pred, "l1_masked_backward: null pointer");
+  hipLaunchKernelGGL(l1_bwd_kernel<true>, dim3((unsigned)((num_values + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, num_values, weight, clamp_pred, upstream, pred, gt, mask, v_pred);
+  GSR_CHECK_LAUNCH("l1_masked_backward");
   return GSR_OK;
 }
 
@@ -377,17 +530,27 @@ GSR_EXPORT int gsr_l1_backward(long long num_values, float weight, int clamp_pre
 // directly -- ~8 elementwise / indexing launches forward and ~10 backward otherwise.
 namespace {
 
+// kMasked (depth_gs.py:424-437 in front of :531-538): g' = gt * m, p' = pred * m, the measured pixels are those
+// with g' > 0 and the loss is mean |g' - p'| over them; the cotangent of pred is m * sign(p' - g') / n.
+template <bool kMasked>
 __global__ __launch_bounds__(256) void depth_l1_fwd_kernel(const long long n, const float *__restrict__ depth,
                                                            const float *__restrict__ alpha,
                                                            const float *__restrict__ gt,
+                                                           const float *__restrict__ mask,
                                                            const float *__restrict__ depth_max,
                                                            double *__restrict__ sums) {
   __shared__ float red[4];
   const float far = *depth_max;
   float acc = 0.f;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    const float a = alpha[i], g = gt[i];
-    const float pred = a > 0.f ? depth[i] / a : far;
+    const float a = alpha[i];
+    float g = gt[i];
+    float pred = a > 0.f ? depth[i] / a : far;
+    if constexpr (kMasked) {
+      const float m = mask[i];
+      g = mul_rounded(g, m);
+      pred = mul_rounded(pred, m);
+    }
     acc += g > 0.f ? fabsf(g - pred) : 0.f;
   }
 #pragma unroll
@@ -407,21 +570,30 @@ __global__ __launch_bounds__(64) void depth_l1_finalize_kernel(const long long n
   if (threadIdx.x == 0) *loss_out = (float)(a / (double)n);
 }
 
+template <bool kMasked>
 __global__ __launch_bounds__(256) void depth_l1_bwd_kernel(const long long n, const float *__restrict__ upstream,
                                                            const float *__restrict__ depth,
                                                            const float *__restrict__ alpha,
                                                            const float *__restrict__ gt,
+                                                           const float *__restrict__ mask,
                                                            const float *__restrict__ depth_max,
                                                            float *__restrict__ v_depth, float *__restrict__ v_alpha) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const float a = alpha[i], g = gt[i], d = depth[i];
+  const float a = alpha[i], d = depth[i];
+  float g = gt[i], m = 1.f;
+  if constexpr (kMasked) {
+    m = mask[i];
+    g = mul_rounded(g, m);
+  }
   float vd = 0.f, va = 0.f;
   if (a > 0.f && g > 0.f) {  // the far value of uncovered pixels is detached
     const float inv = 1.f / a;
     const float pred = d * inv;
-    const float s = pred > g ? 1.f : (pred < g ? -1.f : 0.f);
-    const float vp = upstream[0] * s / (float)n;
+    const float pm = kMasked ? mul_rounded(pred, m) : pred;
+    const float s = pm > g ? 1.f : (pm < g ? -1.f : 0.f);
+    float vp = upstream[0] * s / (float)n;
+    if constexpr (kMasked) vp = mul_rounded(vp, m);
     vd = vp * inv;
     va = -vp * pred * inv;
   }
@@ -438,10 +610,25 @@ GSR_EXPORT int gsr_depth_l1_forward(long long num_pixels, const float *depth, co
   hipStream_t s = (hipStream_t)stream;
   if (int zrc = gsr_zero_async(sums, GSR_LOSS_SUM_SLOTS * sizeof(double), s)) return zrc;
   const unsigned blocks = (unsigned)std::min<long long>((num_pixels + 1023) / 1024, 4096);
-  hipLaunchKernelGGL(depth_l1_fwd_kernel, dim3(blocks), dim3(256), 0, s, num_pixels, depth, alpha, gt, depth_max,
-                     sums);
+  hipLaunchKernelGGL(depth_l1_fwd_kernel<false>, dim3(blocks), dim3(256), 0, s, num_pixels, depth, alpha, gt,
+                     (const float *)nullptr, depth_max, sums);
   hipLaunchKernelGGL(depth_l1_finalize_kernel, dim3(1), dim3(64), 0, s, num_pixels, (const double *)sums, loss_out);
   GSR_CHECK_LAUNCH("depth_l1_forward");
+  return GSR_OK;
+}
+
+GSR_EXPORT int gsr_depth_l1_masked_forward(long long num_pixels, const float *depth, const float *alpha,
+                                           const float *gt, const float *mask, const float *depth_max, double *sums,
+                                           float *loss_out, gsr_stream_t stream) {
+  GSR_REQUIRE(num_pixels > 0, "depth_l1_masked_forward: empty image");
+  GSR_REQUIRE(depth && alpha && gt && mask && depth_max && sums && loss_out, "depth_l1_masked_forward: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  if (int zrc = gsr_zero_async(sums, GSR_LOSS_SUM_SLOTS * sizeof(double), s)) return zrc;
+  const unsigned blocks = (unsigned)std::min<long long>((num_pixels + 1023) / 1024, 4096);
+  hipLaunchKernelGGL(depth_l1_fwd_kernel<true>, dim3(blocks), dim3(256), 0, s, num_pixels, depth, alpha, gt, mask,
+                     depth_max, sums);
+  hipLaunchKernelGGL(depth_l1_finalize_kernel, dim3(1), dim3(64), 0, s, num_pixels, (const double *)sums, loss_out);
+  GSR_CHECK_LAUNCH("depth_l1_masked_forward");
   return GSR_OK;
 }
 
@@ -450,8 +637,22 @@ GSR_EXPORT int gsr_depth_l1_backward(long long num_pixels, const float *upstream
                                      float *v_alpha, gsr_stream_t stream) {
   GSR_REQUIRE(num_pixels > 0, "depth_l1_backward: empty image");
   GSR_REQUIRE(upstream && depth && alpha && gt && depth_max && v_depth && v_alpha, "depth_l1_backward: null pointer");
-  hipLaunchKernelGGL(depth_l1_bwd_kernel, dim3((unsigned)((num_pixels + 255) / 256)), dim3(256), 0,
-                     (hipStream_t)stream, num_pixels, upstream, depth, alpha, gt, depth_max, v_depth, v_alpha);
+  hipLaunchKernelGGL(depth_l1_bwd_kernel<false>, dim3((unsigned)((num_pixels + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, num_pixels, upstream, depth, alpha, gt, (const float *)nullptr, depth_max,
+                     v_depth, v_alpha);
   GSR_CHECK_LAUNCH("depth_l1_backward");
+  return GSR_OK;
+}
+
+GSR_EXPORT int gsr_depth_l1_masked_backward(long long num_pixels, const float *upstream, const float *depth,
+                                            const float *alpha, const float *gt, const float *mask,
+                                            const float *depth_max, float *v_depth, float *v_alpha,
+                                            gsr_stream_t stream) {
+  GSR_REQUIRE(num_pixels > 0, "depth_l1_masked_backward: empty image");
+  GSR_REQUIRE(upstream && depth && alpha && gt && mask && depth_max && v_depth && v_alpha,
+              "depth_l1_masked_backward: null pointer");
+  hipLaunchKernelGGL(depth_l1_bwd_kernel<true>, dim3((unsigned)((num_pixels + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, num_pixels, upstream, depth, alpha, gt, mask, depth_max, v_depth, v_alpha);
+  GSR_CHECK_LAUNCH("depth_l1_masked_backward");
   return GSR_OK;
 }

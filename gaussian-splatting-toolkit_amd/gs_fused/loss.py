@@ -11,6 +11,16 @@ with `self.ssim = pytorch_msssim.SSIM(data_range=1.0, size_average=True, channel
 `l1_ssim_loss(pred_img, gt_img, ssim_lambda)` returns the same scalar; its backward
 writes d loss / d pred_img -- the cotangent the compositing backward consumes --
 in one kernel.  Differentiable w.r.t. `pred` only (the ground truth is data).
+
+Every head takes the per-view `mask` the models multiply into both images in front of the
+loss (vanilla_gs.py:915-924, surface_gs.py:917-925, depth_gs.py:424-437):
+
+    mask = self._downscale_if_required(batch["mask"]).to(self.device)
+    gt_img, pred_img = gt_img * mask, pred_img * mask
+
+`l1_ssim_loss(pred_img, gt_img, ssim_lambda, mask=mask)` computes the loss of those two
+products inside the same two kernels: the mask is multiplied in, nothing is selected, and
+the means stay over all pixels (the reference does not renormalise by the mask's area).
 """
 import ctypes as C
 
@@ -24,9 +34,25 @@ _f32 = torch.float32
 WORKSPACE_DOUBLES = 2 * 64  # GSR_LOSS_WORKSPACE_DOUBLES (include/gsraster.h)
 
 
+def _mask_arg(mask, H: int, W: int, ref: Tensor) -> Tensor:
+    """A per-view mask as the masked kernels take it: contiguous float32 [H,W] on the images' device.  Accepts [H,W]
+    or [H,W,1]; float32 as it is, bool / uint8 through `.to(float32)`."""
+    if not isinstance(mask, Tensor):
+        raise RuntimeError("mask must be a tensor")
+    if tuple(mask.shape) not in ((H, W), (H, W, 1)):
+        raise ValueError(f"expected a mask [{H},{W}] or [{H},{W},1] for these images, got {tuple(mask.shape)}")
+    if mask.device != ref.device:
+        raise RuntimeError(f"mask must be on the images' device {ref.device}, got {mask.device}")
+    if mask.dtype in (torch.bool, torch.uint8):
+        mask = mask.to(_f32)
+    elif mask.dtype != _f32:
+        raise ValueError(f"mask must be float32, bool or uint8, got {mask.dtype}")
+    return _check(mask.detach().reshape(H, W).contiguous(), "mask", _f32)
+
+
 class _L1SSIM(Function):
     @staticmethod
-    def forward(ctx, pred: Tensor, gt: Tensor, ssim_lambda: float, clamp_pred: bool):
+    def forward(ctx, pred: Tensor, gt: Tensor, ssim_lambda: float, clamp_pred: bool, mask=None):
         if pred.dim() != 3 or pred.shape[-1] != 3 or pred.shape != gt.shape:
             raise ValueError(f"expected two [H,W,3] images, got {tuple(pred.shape)} and {tuple(gt.shape)}")
         H, W = int(pred.shape[0]), int(pred.shape[1])
@@ -34,16 +60,26 @@ class _L1SSIM(Function):
             raise ValueError("images must be larger than the 11x11 SSIM window")
         pred = _check(pred.contiguous(), "pred", _f32)
         gt = _check(gt.contiguous(), "gt", _f32)
+        if mask is not None:
+            mask = _mask_arg(mask, H, W, pred)
         dev = pred.device
         with torch.cuda.device(dev):
             maps = torch.empty((9, H - 10, W - 10), dtype=_f32, device=dev)
             work = torch.empty((WORKSPACE_DOUBLES,), dtype=torch.float64, device=dev)
             loss = torch.empty((), dtype=_f32, device=dev)
             terms = torch.empty((2,), dtype=_f32, device=dev)  # L1 mean, SSIM mean
-            _call("gsr_l1_ssim_forward", C.c_uint(H), C.c_uint(W), C.c_float(ssim_lambda),
-                  C.c_int(1 if clamp_pred else 0), _ptr(pred), _ptr(gt), _ptr(maps), _ptr(work), _ptr(loss),
-                  _ptr(terms), _stream(dev))
-        ctx.save_for_backward(pred, gt, maps)
+            if mask is None:
+                _call("gsr_l1_ssim_forward", C.c_uint(H), C.c_uint(W), C.c_float(ssim_lambda),
+                      C.c_int(1 if clamp_pred else 0), _ptr(pred), _ptr(gt), _ptr(maps), _ptr(work), _ptr(loss),
+                      _ptr(terms), _stream(dev))
+            else:
+                _call("gsr_l1_ssim_masked_forward", C.c_uint(H), C.c_uint(W), C.c_float(ssim_lambda),
+                      C.c_int(1 if clamp_pred else 0), _ptr(pred), _ptr(gt), _ptr(mask), _ptr(maps), _ptr(work),
+                      _ptr(loss), _ptr(terms), _stream(dev))
+        if mask is None:
+            ctx.save_for_backward(pred, gt, maps)
+        else:
+            ctx.save_for_backward(pred, gt, maps, mask)
         ctx.ssim_lambda = float(ssim_lambda)
         ctx.clamp_pred = bool(clamp_pred)
         ctx.hw = (H, W)
@@ -52,25 +88,37 @@ class _L1SSIM(Function):
 
     @staticmethod
     def backward(ctx, v_loss, _v_terms):
-        pred, gt, maps = ctx.saved_tensors
+        pred, gt, maps, *masks = ctx.saved_tensors
         H, W = ctx.hw
         dev = pred.device
         up = v_loss.to(_f32).reshape(1).contiguous()
         with torch.cuda.device(dev):
             v_pred = torch.empty_like(pred)
-            _call("gsr_l1_ssim_backward", C.c_uint(H), C.c_uint(W), C.c_float(ctx.ssim_lambda),
-                  C.c_int(1 if ctx.clamp_pred else 0), _ptr(up), _ptr(pred), _ptr(gt), _ptr(maps), _ptr(v_pred),
-                  _stream(dev))
-        return v_pred, None, None, None
+            if not masks:
+                _call("gsr_l1_ssim_backward", C.c_uint(H), C.c_uint(W), C.c_float(ctx.ssim_lambda),
+                      C.c_int(1 if ctx.clamp_pred else 0), _ptr(up), _ptr(pred), _ptr(gt), _ptr(maps), _ptr(v_pred),
+                      _stream(dev))
+            else:
+                _call("gsr_l1_ssim_masked_backward", C.c_uint(H), C.c_uint(W), C.c_float(ctx.ssim_lambda),
+                      C.c_int(1 if ctx.clamp_pred else 0), _ptr(up), _ptr(pred), _ptr(gt), _ptr(masks[0]), _ptr(maps),
+                      _ptr(v_pred), _stream(dev))
+        return v_pred, None, None, None, None
 
 
 def l1_ssim_loss(pred: Tensor, gt: Tensor, ssim_lambda: float = 0.2, return_terms: bool = False,
-                 clamp_pred: bool = False):
+                 clamp_pred: bool = False, mask=None):
     """Scalar loss (fp32, on device).  With `return_terms`, also the L1 mean and the
     SSIM value (detached diagnostics; gradients flow through the loss only).
     `clamp_pred`: compute the loss of `torch.clamp(pred, max=1.0)` (what the models
-    feed it, vanilla_gs.py:857) without that op and its backward."""
-    loss, terms = _L1SSIM.apply(pred, gt, ssim_lambda, clamp_pred)
+    feed it, vanilla_gs.py:857) without that op and its backward.
+    `mask` ([H,W] or [H,W,1]; float32, bool or uint8; on the images' device): the loss of
+    ``pred * mask`` and ``gt * mask`` (of ``torch.clamp(pred, max=1.0) * mask`` under
+    `clamp_pred`), as the models form them (vanilla_gs.py:915-924), without the two
+    multiplies and their backward.  Multiplied in, not selected: the means stay over all
+    pixels, fractional values are allowed, and a non-finite `pred` under a zero is what
+    ``pred * 0`` is.  The mask is a constant (no gradient); the gradient of `pred` is 0
+    wherever the mask is 0."""
+    loss, terms = _L1SSIM.apply(pred, gt, ssim_lambda, clamp_pred, mask)
     if return_terms:
         return loss, terms[0], terms[1]
     return loss
@@ -82,87 +130,124 @@ class L1SSIMLoss(torch.nn.Module):
         self.ssim_lambda = ssim_lambda
         self.clamp_pred = clamp_pred
 
-    def forward(self, pred: Tensor, gt: Tensor) -> Tensor:
-        return l1_ssim_loss(pred, gt, self.ssim_lambda, clamp_pred=self.clamp_pred)
+    def forward(self, pred: Tensor, gt: Tensor, mask=None) -> Tensor:
+        return l1_ssim_loss(pred, gt, self.ssim_lambda, clamp_pred=self.clamp_pred, mask=mask)
 
 
 class _L1(Function):
     @staticmethod
-    def forward(ctx, pred: Tensor, gt: Tensor, weight: float, clamp_pred: bool):
+    def forward(ctx, pred: Tensor, gt: Tensor, weight: float, clamp_pred: bool, mask=None):
         if pred.shape != gt.shape or pred.numel() == 0:
             raise ValueError(f"expected two images of one (non-empty) shape, got {tuple(pred.shape)} and {tuple(gt.shape)}")
+        if mask is not None and (pred.dim() != 3 or pred.shape[-1] != 3):
+            raise ValueError(f"a mask needs two [H,W,3] images, got {tuple(pred.shape)}")
         pred = _check(pred.contiguous(), "pred", _f32)
         gt = _check(gt.contiguous(), "gt", _f32)
+        if mask is not None:
+            mask = _mask_arg(mask, int(pred.shape[0]), int(pred.shape[1]), pred)
         dev = pred.device
         with torch.cuda.device(dev):
             work = torch.empty((64,), dtype=torch.float64, device=dev)
             loss = torch.empty((), dtype=_f32, device=dev)
-            _call("gsr_l1_forward", C.c_longlong(pred.numel()), C.c_float(weight), C.c_int(1 if clamp_pred else 0),
-                  _ptr(pred), _ptr(gt), _ptr(work), _ptr(loss), _stream(dev))
-        ctx.save_for_backward(pred, gt)
+            if mask is None:
+                _call("gsr_l1_forward", C.c_longlong(pred.numel()), C.c_float(weight), C.c_int(1 if clamp_pred else 0),
+                      _ptr(pred), _ptr(gt), _ptr(work), _ptr(loss), _stream(dev))
+            else:
+                _call("gsr_l1_masked_forward", C.c_longlong(pred.numel()), C.c_float(weight),
+                      C.c_int(1 if clamp_pred else 0), _ptr(pred), _ptr(gt), _ptr(mask), _ptr(work), _ptr(loss),
+                      _stream(dev))
+        if mask is None:
+            ctx.save_for_backward(pred, gt)
+        else:
+            ctx.save_for_backward(pred, gt, mask)
         ctx.weight, ctx.clamp_pred = float(weight), bool(clamp_pred)
         return loss
 
     @staticmethod
     def backward(ctx, v_loss):
-        pred, gt = ctx.saved_tensors
+        pred, gt, *masks = ctx.saved_tensors
         dev = pred.device
         up = v_loss.to(_f32).reshape(1).contiguous()
         with torch.cuda.device(dev):
             v_pred = torch.empty_like(pred)
-            _call("gsr_l1_backward", C.c_longlong(pred.numel()), C.c_float(ctx.weight),
-                  C.c_int(1 if ctx.clamp_pred else 0), _ptr(up), _ptr(pred), _ptr(gt), _ptr(v_pred), _stream(dev))
-        return v_pred, None, None, None
+            if not masks:
+                _call("gsr_l1_backward", C.c_longlong(pred.numel()), C.c_float(ctx.weight),
+                      C.c_int(1 if ctx.clamp_pred else 0), _ptr(up), _ptr(pred), _ptr(gt), _ptr(v_pred), _stream(dev))
+            else:
+                _call("gsr_l1_masked_backward", C.c_longlong(pred.numel()), C.c_float(ctx.weight),
+                      C.c_int(1 if ctx.clamp_pred else 0), _ptr(up), _ptr(pred), _ptr(gt), _ptr(masks[0]),
+                      _ptr(v_pred), _stream(dev))
+        return v_pred, None, None, None, None
 
 
-def l1_loss(pred: Tensor, gt: Tensor, weight: float = 1.0, clamp_pred: bool = False) -> Tensor:
+def l1_loss(pred: Tensor, gt: Tensor, weight: float = 1.0, clamp_pred: bool = False, mask=None) -> Tensor:
     """``weight * |gt - pred|.mean()`` in one streaming kernel each way -- the photometric loss of the co-gs
     model AS ITS SOURCE COMPUTES IT: `DepthGSModel.get_loss_dict` (depth_gs.py:445-448) writes
     ``loss_dict["main_loss"] = (1 - ssim_lambda) * Ll1`` and puts ``+ssim_lambda * simloss`` on a line of its own,
     an expression statement whose value is dropped, so ``weight = 1 - ssim_lambda`` and no SSIM term.
-    `clamp_pred`: the loss of ``torch.clamp(pred, max=1.0)`` (depth_gs.py:343) without that op."""
-    return _L1.apply(pred, gt, weight, clamp_pred)
+    `clamp_pred`: the loss of ``torch.clamp(pred, max=1.0)`` (depth_gs.py:343) without that op.
+    `mask` ([H,W] or [H,W,1] for two [H,W,3] images; float32, bool or uint8): the loss of ``pred * mask`` and
+    ``gt * mask`` (depth_gs.py:424-437), the mean still over all 3 H W values; see `l1_ssim_loss`."""
+    return _L1.apply(pred, gt, weight, clamp_pred, mask)
 
 
 class _DepthL1(Function):
     @staticmethod
-    def forward(ctx, depth: Tensor, alpha: Tensor, gt: Tensor):
+    def forward(ctx, depth: Tensor, alpha: Tensor, gt: Tensor, mask=None):
         if depth.numel() != alpha.numel() or depth.numel() != gt.numel() or depth.numel() == 0:
             raise ValueError("depth, alpha and gt_depth must have the same (non-zero) number of pixels")
+        if mask is not None and gt.dim() < 2:
+            raise ValueError(f"a mask needs gt_depth as an image [H,W] (or [H,W,1]), got {tuple(gt.shape)}")
         d = _check(depth.contiguous(), "depth", _f32)
         a = _check(alpha.contiguous(), "alpha", _f32)
         g = _check(gt.contiguous(), "gt_depth", _f32)
+        if mask is not None:
+            mask = _mask_arg(mask, int(gt.shape[0]), int(gt.shape[1]), d)
         dev = d.device
         with torch.cuda.device(dev):
             far = d.detach().max().reshape(1)  # depth_im.detach().max() of the reference
             work = torch.empty((64,), dtype=torch.float64, device=dev)
             loss = torch.empty((), dtype=_f32, device=dev)
-            _call("gsr_depth_l1_forward", C.c_longlong(d.numel()), _ptr(d), _ptr(a), _ptr(g), _ptr(far),
-                  _ptr(work), _ptr(loss), _stream(dev))
-        ctx.save_for_backward(d, a, g, far)
+            if mask is None:
+                _call("gsr_depth_l1_forward", C.c_longlong(d.numel()), _ptr(d), _ptr(a), _ptr(g), _ptr(far),
+                      _ptr(work), _ptr(loss), _stream(dev))
+            else:
+                _call("gsr_depth_l1_masked_forward", C.c_longlong(d.numel()), _ptr(d), _ptr(a), _ptr(g), _ptr(mask),
+                      _ptr(far), _ptr(work), _ptr(loss), _stream(dev))
+        if mask is None:
+            ctx.save_for_backward(d, a, g, far)
+        else:
+            ctx.save_for_backward(d, a, g, far, mask)
         ctx.shapes = (depth.shape, alpha.shape)
         return loss
 
     @staticmethod
     def backward(ctx, v_loss):
-        d, a, g, far = ctx.saved_tensors
+        d, a, g, far, *masks = ctx.saved_tensors
         dev = d.device
         up = v_loss.to(_f32).reshape(1).contiguous()
         with torch.cuda.device(dev):
             v_d = torch.empty_like(d)
             v_a = torch.empty_like(a)
-            _call("gsr_depth_l1_backward", C.c_longlong(d.numel()), _ptr(up), _ptr(d), _ptr(a), _ptr(g),
-                  _ptr(far), _ptr(v_d), _ptr(v_a), _stream(dev))
-        return v_d.view(ctx.shapes[0]), v_a.view(ctx.shapes[1]), None
+            if not masks:
+                _call("gsr_depth_l1_backward", C.c_longlong(d.numel()), _ptr(up), _ptr(d), _ptr(a), _ptr(g),
+                      _ptr(far), _ptr(v_d), _ptr(v_a), _stream(dev))
+            else:
+                _call("gsr_depth_l1_masked_backward", C.c_longlong(d.numel()), _ptr(up), _ptr(d), _ptr(a), _ptr(g),
+                      _ptr(masks[0]), _ptr(far), _ptr(v_d), _ptr(v_a), _stream(dev))
+        return v_d.view(ctx.shapes[0]), v_a.view(ctx.shapes[1]), None, None
 
 
-def depth_l1_loss(depth_acc: Tensor, alpha: Tensor, gt_depth: Tensor) -> Tensor:
+def depth_l1_loss(depth_acc: Tensor, alpha: Tensor, gt_depth: Tensor, mask=None) -> Tensor:
     """Depth head of the co-gs model in two launches (+ one max): with
     ``pred = where(alpha > 0, depth_acc / alpha, depth_acc.detach().max())``
     (depth_gs.py:356-363) returns ``|gt * (gt > 0) - pred * (gt > 0)|.mean()``
     (depth_gs.py:531-538).  ``depth_acc`` is the raw output of the depth compositing
-    pass, ``alpha`` the accumulated opacity of the RGB pass; differentiable w.r.t. both."""
-    return _DepthL1.apply(depth_acc, alpha, gt_depth)
+    pass, ``alpha`` the accumulated opacity of the RGB pass; differentiable w.r.t. both.
+    `mask` ([H,W] or [H,W,1] like ``gt_depth``; float32, bool or uint8): both depth images are multiplied by it first
+    (depth_gs.py:424-437): ``g = gt * mask``, ``p = pred * mask`` and the value is ``|g * (g > 0) - p * (g > 0)|.mean()``
+    over all pixels; the cotangents of ``depth_acc`` and ``alpha`` are scaled by the mask."""
+    return _DepthL1.apply(depth_acc, alpha, gt_depth, mask)
 
 
 DEPTH_REG_WORKSPACE_DOUBLES = 1024  # GSR_DEPTH_REG_WORKSPACE_DOUBLES (include/gsraster.h)

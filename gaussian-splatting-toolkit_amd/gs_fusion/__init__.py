@@ -6,6 +6,6 @@ csrc/mesh_clean.hip) are the exporter's cleaning step without pymeshlab: DESIGN.
 `surface_distance` (`gsr_mesh_bvh_build`, `gsr_mesh_distance_*`, csrc/mesh_distance.hip) measure the result against a
 ground-truth mesh as gs_toolkit/evaluation/surface_distance does: DESIGN.md section 4.7."""
 from .volume import TSDFVolume, invert_viewmat  # noqa: F401
-from .fuse import fuse_views, read_poses_json, view_depth  # noqa: F401
+from .fuse import export_mask, fuse_views, read_poses_json, view_depth  # noqa: F401
 from .mesh import clean_mesh, mesh_components  # noqa: F401
 from .distance import MeshDistance, distance_stats, surface_distance  # noqa: F401

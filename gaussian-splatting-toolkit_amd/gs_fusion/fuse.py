@@ -2,7 +2,7 @@
 (gs_toolkit/scripts/exporter.py:151-308), without its files."""
 import json
 import math
-from typing import Dict, List, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -24,22 +24,79 @@ def view_depth(depth_acc: Tensor, alpha: Tensor, alpha_min: float = 0.5):
     return depth.contiguous(), valid.to(torch.uint8)
 
 
+def export_mask(mask, bounding_box: bool = False, margin: int = 5) -> Tensor:
+    """An object mask as `TSDFFusion.integrate` applies it to a view's depth (exporter/tsdf_fusion.py:105-130,
+    `create_bounding_box_mask` :234-262) -> bool [H,W], True where depth is kept.  Torch ops on the mask's device
+    (NumPy arrays are taken as CPU tensors).
+
+    `mask` [H,W,3] or [H,W,4] uint8 (an annotation image; a fourth channel is not read, as there):
+    ``gray = 0.21 * R + 0.72 * G + 0.07 * B`` in float64, added left to right, truncated to uint8; kept where
+    ``gray != 0`` -- so pure red counts from 5, pure green from 2, pure blue from 15.  `mask` [H,W] (any dtype) is
+    taken as gray already: kept where non-zero.  That is an extension; the reference indexes three channels.
+
+    `bounding_box`: instead of the mask itself, the inclusive rectangle around its kept pixels, grown by `margin`
+    pixels on every side and clipped to the image.  An empty mask then raises ValueError (the reference's `np.min` of
+    an empty array does).  This reads four numbers back: the host waits for the device."""
+    m = torch.as_tensor(mask)
+    if m.dim() == 3 and m.shape[-1] in (3, 4):
+        if m.dtype != torch.uint8:
+            raise ValueError(f"a colour mask must be uint8, got {m.dtype}")
+        c = m.to(torch.float64)
+        gray = (0.21 * c[..., 0] + 0.72 * c[..., 1]) + 0.07 * c[..., 2]
+        keep = gray.to(torch.uint8) != 0
+    elif m.dim() == 2:
+        keep = m != 0
+    else:
+        raise ValueError(f"expected a mask [H,W], [H,W,3] or [H,W,4], got {tuple(m.shape)}")
+    if not bounding_box:
+        return keep
+    if margin < 0:
+        raise ValueError("margin must not be negative")
+    nz = torch.nonzero(keep)
+    if nz.shape[0] == 0:
+        raise ValueError("export_mask: the bounding box of an empty mask")
+    (y0, x0), (y1, x1) = nz.min(dim=0).values.tolist(), nz.max(dim=0).values.tolist()
+    H, W = keep.shape
+    y0, y1 = max(y0 - margin, 0), min(y1 + margin, H - 1)
+    x0, x1 = max(x0 - margin, 0), min(x1 + margin, W - 1)
+    box = torch.zeros_like(keep)
+    box[y0:y1 + 1, x0:x1 + 1] = True
+    return box
+
+
 def fuse_views(volume: TSDFVolume, params: Dict[str, Tensor], cameras: Sequence[Camera], background: Tensor,
-               sh_degree: int, alpha_min: float = 0.5, depth_trunc: float = 10.0) -> None:
+               sh_degree: int, alpha_min: float = 0.5, depth_trunc: float = 10.0, masks: Optional[Sequence] = None,
+               bounding_box: bool = False, mask_margin: int = 5) -> None:
     """Render RGB + depth from every camera (`render_view(render_depth=True, fused_depth=True)`: one compositing
     pass) and integrate it into `volume`.  `params`: activated `means3d`, `scales`, `quats`, `opacities`,
     `sh_coeffs` on the volume's device; `cameras`: `harness.scene.Camera` (host arrays).
+
+    `masks`: one object mask per camera (`export_mask`'s input; `ExportTSDF`'s `using_mask` / `mask_path`): a view's
+    depth is integrated only where `export_mask(mask, bounding_box, mask_margin)` keeps it.  A mask that is not its
+    camera's height x width raises ValueError.  All masks are converted before the first view is rendered.
 
     Everything stays on the device as float32: there is NO round trip through 8-bit colour PNG and 16-bit millimetre
     depth PNG files as in the toolkit's file-based route, hence none of their quantisation -- a deliberate difference;
     and the host is not synchronised between views."""
     dev = volume.device
+    keeps = None
+    if masks is not None:
+        if len(masks) != len(cameras):
+            raise ValueError(f"{len(masks)} masks for {len(cameras)} cameras")
+        keeps = []
+        for i, (cam, mask) in enumerate(zip(cameras, masks)):
+            m = torch.as_tensor(mask)
+            if m.dim() < 2 or (int(m.shape[0]), int(m.shape[1])) != (int(cam.height), int(cam.width)):
+                raise ValueError(f"mask {i} is {tuple(m.shape)}, its camera is {cam.height} x {cam.width}")
+            keeps.append(export_mask(m.to(dev), bounding_box, mask_margin).to(torch.uint8))
     with torch.no_grad():
-        for cam in cameras:
+        for i, cam in enumerate(cameras):
             out = render_view(params["means3d"], params["scales"], params["quats"], params["opacities"],
                               params["sh_coeffs"], CameraTensors.from_numpy(cam, dev), background, sh_degree,
                               render_depth=True, fused_depth=True, normalise_depth=False)
             depth, valid = view_depth(out["depth_acc"], out["alpha"], alpha_min)
+            if keeps is not None:
+                valid = valid & keeps[i]
             volume.integrate(depth, out["rgb"].contiguous(), cam.fx, cam.fy, cam.cx, cam.cy, cam.viewmat, valid=valid,
                              depth_trunc=depth_trunc)
 

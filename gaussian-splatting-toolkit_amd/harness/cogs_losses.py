@@ -117,7 +117,9 @@ def optional_depth_terms(cfg, step: int, pred_depth: torch.Tensor, gt_depth: tor
     sums unweighted (engine/trainer.py:497): local Pearson while step < depth_loss_stop_iteration, the scaled log-depth
     term when the batch carries a scale / shift, the TV term below step 20 000.  `cfg` carries the reference's field
     names (use_pearson_depth, local_patch_size, depth_loss_stop_iteration, use_scaled_est_depth,
-    use_depth_regularization, using_tv_loss)."""
+    use_depth_regularization, using_tv_loss).  With a per-view mask the model multiplies it into the images before
+    this branch (depth_gs.py:424-437): the caller passes ``pred_depth * mask``, ``gt_depth * mask`` and the masked
+    ground-truth image; the terms themselves know nothing of masks."""
     terms: Dict[str, torch.Tensor] = {}
     if step < cfg.depth_loss_stop_iteration and cfg.use_pearson_depth:
         terms["depth_local_pearson"] = local_pearson_loss(pred_depth, gt_depth, cfg.local_patch_size, 0.5, generator)

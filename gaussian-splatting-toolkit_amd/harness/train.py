@@ -107,6 +107,26 @@ def downscale_depth(depth: torch.Tensor, d: int) -> torch.Tensor:
                          align_corners=False, antialias=False)[0, 0]
 
 
+def downscale_mask(mask: torch.Tensor, d: int) -> torch.Tensor:
+    """`self._downscale_if_required(batch["mask"])` (vanilla_gs.py:919, surface_gs.py:921, depth_gs.py:429): the
+    [H,W,1] mask goes through the resize the image goes through -- bilinear, no antialiasing -- so under the resolution
+    schedule a 0/1 mask comes out with fractional values along its edges."""
+    return downscale_image(mask, d)
+
+
+def view_masks(kind: str, height: int, width: int, alphas, device) -> List[torch.Tensor]:
+    """`TrainConfig.mask` -> one float [H,W,1] mask per view.  "alpha": the object's silhouette, where the accumulated
+    opacity of the hidden scene's render (`alphas[v]`, [H,W,1]) is above 0.5.  "box": rows H//4 .. 3H//4 - 1 and columns
+    W//4 .. 3W//4 - 1 are 1, everything else 0, the same for every view."""
+    if kind == "alpha":
+        return [(a > 0.5).to(torch.float32).contiguous() for a in alphas]
+    if kind == "box":
+        m = torch.zeros((height, width, 1), device=device)
+        m[height // 4:3 * height // 4, width // 4:3 * width // 4] = 1.0
+        return [m for _ in alphas]
+    raise ValueError(f"unknown mask {kind!r}")
+
+
 def composite_with_background(image: torch.Tensor, background: torch.Tensor) -> torch.Tensor:
     """What the models do with a ground-truth image that carries an alpha channel (vanilla_gs.py:870-881): straight
     colour over the step's background, `a * rgb + (1 - a) * background`; an RGB image is returned as it is."""
@@ -458,6 +478,16 @@ class TrainConfig:
     use_scaled_est_depth: bool = False
     use_depth_regularization: bool = False
     using_tv_loss: bool = False
+    # a per-view mask, as a dataset with object masks delivers one in `batch["mask"]`: "none"; "alpha" = the object's
+    # silhouette (the hidden scene's accumulated opacity > 0.5); "box" = the central half of the image in both
+    # directions (`view_masks`).  Both images -- and, for co-gs, both depth images -- are MULTIPLIED by it in front of
+    # the loss (vanilla_gs.py:915-924, surface_gs.py:917-925, depth_gs.py:424-437): nothing is selected and the means
+    # stay over all pixels.  vanilla_gs.py:919 and depth_gs.py:429 `.unsqueeze(-1)` the [H,W,1] mask and then
+    # `repeat(1, 1, 3)` it, which cannot run on a four-dimensional tensor; surface_gs.py:921 multiplies the [H,W,1] mask
+    # in directly and states what is meant -- that is what is followed, for all three models (and `gt_depth [H,W]`
+    # takes the mask's one channel).  With the fused heads the multiplies happen inside the loss kernels
+    # (gs_fused.*_loss(mask=...)); otherwise they are the reference's torch ops.
+    mask: str = "none"
 
 
 def quantise_depth_mm(depth: torch.Tensor) -> torch.Tensor:
@@ -522,6 +552,9 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
     cogs = cfg.model == "co-gs"
     if cogs and (cfg.fused_render or cfg.use_graph):
         raise ValueError("co-gs runs through the separate ops (fused_depth = one RGB + depth compositing pass)")
+    if cfg.mask not in ("none", "alpha", "box"):
+        raise ValueError(f"unknown mask {cfg.mask!r}")
+    masked = cfg.mask != "none"
     mk = lambda: blob_scene(cfg.num_gaussians, seed=cfg.seed, sh_degree=cfg.sh_degree, kind=cfg.scene,
                             scale_lo=cfg.scene_scale[0], scale_hi=cfg.scene_scale[1], tex_cell=cfg.tex_cell,
                             objects=cfg.scene_objects, extent=cfg.scene_extent)
@@ -551,6 +584,12 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
                                  fused_depth=device.type == "cuda")
                 gt_depth.append(quantise_depth_mm(torch.where(o["alpha"] > 0.5, o["depth"], torch.zeros_like(o["depth"]))
                                                   [..., 0]).contiguous())
+
+        masks = None
+        if masked:
+            masks = view_masks(cfg.mask, cfg.height, cfg.width,
+                               [truth.render(c, bg, cfg.sh_degree)["alpha"] if cfg.mask == "alpha" else None
+                                for c in cams], device)
 
     raw = mk()
     rng = np.random.default_rng(cfg.seed + 1)
@@ -601,10 +640,14 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
 
         # the clamp of the rendered image at 1 (vanilla_gs.py:857) is folded into the loss kernels
         fused_clamp = True
-        loss_fn = lambda pred, target: l1_ssim_loss(pred, target, cfg.ssim_lambda, clamp_pred=fused_clamp)
+        loss_fn = lambda pred, target, m=None: l1_ssim_loss(pred, target, cfg.ssim_lambda, clamp_pred=fused_clamp,
+                                                            mask=m)
     else:
-        loss_fn = lambda pred, target: ((1 - cfg.ssim_lambda) * (pred - target).abs().mean()
-                                        + cfg.ssim_lambda * (1 - ssim(pred, target)))
+        def loss_fn(pred, target, m=None):
+            if m is not None:  # the reference's two multiplies
+                pred, target = pred * m, target * m
+            return ((1 - cfg.ssim_lambda) * (pred - target).abs().mean()
+                    + cfg.ssim_lambda * (1 - ssim(pred, target)))
 
     depth_loss_fn = None
     if cogs:
@@ -612,13 +655,15 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
         if cfg.fused_loss and device.type == "cuda":
             from gs_fused import depth_l1_loss, l1_loss
 
-            loss_fn = lambda pred, target: l1_loss(pred, target, w_l1, clamp_pred=fused_clamp)
+            loss_fn = lambda pred, target, m=None: l1_loss(pred, target, w_l1, clamp_pred=fused_clamp, mask=m)
         else:
-            loss_fn = lambda pred, target: cogs_main_loss(pred, target, cfg.ssim_lambda)
+            loss_fn = lambda pred, target, m=None: (cogs_main_loss(pred, target, cfg.ssim_lambda) if m is None else
+                                                    cogs_main_loss(pred * m, target * m, cfg.ssim_lambda))
         if cfg.fused_depth and cfg.fused_loss and device.type == "cuda":
-            depth_loss_fn = lambda out, gtd: depth_l1_loss(out["depth_acc"], out["alpha"], gtd)
+            depth_loss_fn = lambda out, gtd, m=None: depth_l1_loss(out["depth_acc"], out["alpha"], gtd, mask=m)
         else:
-            depth_loss_fn = lambda out, gtd: cogs_depth_l1(out["depth"], gtd)
+            depth_loss_fn = lambda out, gtd, m=None: (cogs_depth_l1(out["depth"], gtd) if m is None else
+                                                      cogs_depth_l1(out["depth"] * m, gtd * m[..., 0]))
 
     fused_stats = cfg.fused_activations and device.type == "cuda"
     if fused_stats:
@@ -638,19 +683,32 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
     max_dim = max(cfg.width, cfg.height)
 
     depth_err = []  # co-gs: mean |rendered depth - gt depth| over the measured pixels, at every evaluate()
+    psnr_masked = []  # with a mask: PSNR over the pixels with mask > 0.5, at every evaluate()
+
+    def masked_psnr(rgb, i):
+        sel = masks[i][..., 0] > 0.5
+        return psnr(rgb[sel], gt[i][sel])
 
     def evaluate():
         with torch.no_grad():
             idx = np.linspace(0, cfg.num_views - 1, cfg.eval_views).astype(int)
             if not cogs:
-                return float(np.mean([psnr(model.render(cams[i], bg, cfg.sh_degree)["rgb"], gt[i]) for i in idx]))
-            ps, de = [], []
+                if not masked:
+                    return float(np.mean([psnr(model.render(cams[i], bg, cfg.sh_degree)["rgb"], gt[i]) for i in idx]))
+                imgs = [model.render(cams[i], bg, cfg.sh_degree)["rgb"] for i in idx]
+                psnr_masked.append(float(np.mean([masked_psnr(im, i) for im, i in zip(imgs, idx)])))
+                return float(np.mean([psnr(im, gt[i]) for im, i in zip(imgs, idx)]))
+            ps, de, pm = [], [], []
             for i in idx:
                 o = model.render(cams[i], bg, cfg.sh_degree, render_depth=True, fused_depth=device.type == "cuda")
                 ps.append(psnr(o["rgb"], gt[i]))
+                if masked:
+                    pm.append(masked_psnr(o["rgb"], i))
                 m = gt_depth[i] > 0
                 de.append(float((o["depth"][..., 0] - gt_depth[i]).abs()[m].mean()) if bool(m.any()) else 0.0)
             depth_err.append(float(np.mean(de)))
+            if masked:
+                psnr_masked.append(float(np.mean(pm)))
             return float(np.mean(ps))
 
     start_step = 0
@@ -703,7 +761,8 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
 
         fstats = DensifyStats(model.num_points, device, max_dim)
         caps = ListCapacity()
-        graph_loss = lambda out, targets: loss_fn(out["rgb"], targets[0])
+        # (with a mask: the second static target of the graph, [h,w,1])
+        graph_loss = lambda out, targets: loss_fn(out["rgb"], targets[0], targets[1] if masked else None)
         with torch.no_grad():  # size the lists once, synchronously (vanilla: every view, utils.py:124)
             while True:
                 g_ = model.gauss
@@ -724,6 +783,7 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
     first_pending, first_vis = True, None
     rebuilds0 = _list_rebuilds()
     target_cache = {}  # (view, downscale factor) -> (resized alpha * rgb [h,w,3], resized 1 - alpha [h,w,1])
+    mask_cache = {}  # (view, downscale factor) -> resized mask [h,w,1]: it does not depend on the step
     bg_static = bg.clone() if (random_bg and cfg.use_graph) else None  # a replayed graph reads its background here
     try:  # (an exception in the loop must not leave the collector frozen for the rest of the process)
         for step in range(start_step, cfg.iters):
@@ -752,6 +812,11 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
                     bg_step = bg_static
             else:
                 bg_step, target = bg, downscale_image(gt[v], d)
+            m_step = None
+            if masked:
+                m_step = mask_cache.get((v, d))
+                if m_step is None:
+                    m_step = mask_cache[(v, d)] = downscale_mask(masks[v], d).contiguous()
             if use_fused:
                 spec = ViewSpec(cam.height, cam.width, cam.fx, cam.fy, cam.cx, cam.cy, deg)
                 fstats.enabled = not (cfg.densify and step >= rcfg.stop_split_at)
@@ -763,15 +828,17 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
                     key = (spec, model.num_points, caps.capacity, fstats.enabled, generation)
                     if vkey != key:  # new SH degree, N changed by refinement, or larger lists: capture again
                         vgraph = ViewGraph({k: g_[k] for k in PARAM_NAMES}, spec, caps.capacity, graph_loss, bg_step,
-                                           [(cam.height, cam.width, 3)], stats=fstats)
-                        vgraph.capture(cam.viewmat, cam.projmat, cam.campos, (target,))
+                                           [(cam.height, cam.width, 3)] + ([(cam.height, cam.width, 1)] if masked else []),
+                                           stats=fstats)
+                        vgraph.capture(cam.viewmat, cam.projmat, cam.campos, (target, m_step) if masked else (target,))
                         vkey = key
                     else:
                         # the count of the previous replay is in pinned memory by now
                         if not vgraph.fits():
                             overflow_views += 1
                             caps.capacity = ((int(1.5 * int(vgraph.count_host[0])) + (1 << 20)) >> 20) << 20
-                    loss, out = vgraph.replay(cam.viewmat, cam.projmat, cam.campos, (target,))
+                    loss, out = vgraph.replay(cam.viewmat, cam.projmat, cam.campos,
+                                              (target, m_step) if masked else (target,))
                     if dp:
                         exchange.start_all()
                 else:
@@ -784,7 +851,7 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
                     out = render_gaussians(g_["means"], g_["scales"], g_["quats"], g_["opacities"], g_["features_dc"],
                                            g_["features_rest"], cam.viewmat, cam.projmat, cam.campos, bg_step, spec, used,
                                            count_out=slot, stats=fstats, sh_collector=collector)
-                    loss = loss_fn(out["rgb"], target)
+                    loss = loss_fn(out["rgb"], target, m_step)
                     loss.backward()
                     caps.submitted(slot, used, device)
                     if caps.overflowed():
@@ -803,20 +870,25 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
                 rgb = out["rgb"]
                 if ph:
                     ph[1].record()
-                loss = loss_fn(rgb, target)
+                loss = loss_fn(rgb, target, m_step)
                 if cogs and cfg.use_scale_regularization and step % 10 == 0:  # depth_gs.py:450-460
                     loss = loss + cogs_losses.scale_regularisation(model.gauss["scales"], cfg.max_gauss_ratio)
                 if cogs and cfg.use_sparse_loss and step % 100 == 0:  # :462-467 (the raw opacity parameter, as written)
                     loss = loss + cogs_losses.sparse_loss(model.gauss["opacities"], cfg.sparse_lambda)
                 if depth_on and cfg.use_est_depth:
                     # the monocular-depth branch (:477-531); the synthetic ground truth is metric: scale 1, shift 0
-                    terms = cogs_losses.optional_depth_terms(cfg, step, out["depth"], downscale_depth(gt_depth[v], d),
-                                                            target, mono_scale_shift=(1.0, 0.0))
+                    gtd = downscale_depth(gt_depth[v], d)
+                    if masked:  # depth_gs.py:424-437: the optional terms see the masked images (plain torch multiplies)
+                        terms = cogs_losses.optional_depth_terms(cfg, step, out["depth"] * m_step, gtd * m_step[..., 0],
+                                                                target * m_step, mono_scale_shift=(1.0, 0.0))
+                    else:
+                        terms = cogs_losses.optional_depth_terms(cfg, step, out["depth"], gtd, target,
+                                                                mono_scale_shift=(1.0, 0.0))
                     for term in terms.values():
                         loss = loss + term
                 elif depth_on:
                     # `gt_depth = self.get_gt_img(batch["depth"])` (downscaled like the image under a resolution schedule)
-                    loss = loss + depth_loss_fn(out, downscale_depth(gt_depth[v], d))
+                    loss = loss + depth_loss_fn(out, downscale_depth(gt_depth[v], d), m_step)
                 if ph:
                     ph[2].record()
                 loss.backward()
@@ -964,7 +1036,8 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
                          "background_color": cfg.background_color, "caller_syncs": cfg.caller_syncs},
             "update": "reduce-scatter + sharded Adam + all-gather" if sharded is not None else
             ("all-reduce (geometry) + all-gathered colour cotangents (SH) + Adam" if sh_views else "all-reduce + Adam"),
-            "init": cfg.init, "model": cfg.model,
+            "init": cfg.init, "model": cfg.model, "mask": cfg.mask,
+            **({"psnr_masked_start": psnr_masked[0], "psnr_masked_end": psnr_masked[-1]} if masked else {}),
             "depth": ({"loss_from_step": cfg.depth_loss_start_iteration + 1 if cfg.use_depth_loss else None,
                        "one_compositing_pass": bool(cfg.fused_depth and device.type == "cuda"),
                        "mean_abs_error_start_end": [depth_err[0], depth_err[-1]]} if cogs else None),

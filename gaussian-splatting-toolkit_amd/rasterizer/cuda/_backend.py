@@ -57,6 +57,12 @@ SYMBOLS = (
     "gsr_l1_backward",
     "gsr_depth_l1_forward",
     "gsr_depth_l1_backward",
+    "gsr_l1_ssim_masked_forward",
+    "gsr_l1_ssim_masked_backward",
+    "gsr_l1_masked_forward",
+    "gsr_l1_masked_backward",
+    "gsr_depth_l1_masked_forward",
+    "gsr_depth_l1_masked_backward",
     "gsr_sh_forward_split",
     "gsr_sh_backward_split",
     "gsr_sh_backward_views",

@@ -493,6 +493,50 @@ int gsr_depth_l1_backward(long long num_pixels, const float *upstream,
                           const float *gt, const float *depth_max,
                           float *v_depth, float *v_alpha, gsr_stream_t stream);
 
+/* f2 with a per-view mask, as the models apply one in front of their losses
+ * (vanilla_gs.py:915-924, surface_gs.py:917-925, depth_gs.py:424-437, 533-538): both images
+ * are MULTIPLIED by the mask -- nothing is selected and no mean is renormalised by the
+ * mask's area.  mask: [H,W] fp32, one value per pixel shared by its channels, any real
+ * number (a mask resized under the resolution schedule is fractional).  With
+ *   x = (clamp_pred ? min(pred, 1) : pred) * m,   y = gt * m      (both rounded to fp32)
+ * the three heads compute from x and y exactly what the unmasked entry points compute
+ * from pred and gt, same workspaces, same divisors (3 H W, 3 (H-10) (W-10), num_values,
+ * num_pixels); their backward is v_pred = m * (d loss / d x), 0 where pred > 1 under
+ * clamp_pred.  gsr_l1_masked_*: num_values = 3 H W and element e takes mask[e / 3].
+ * Depth head: g' = gt * m, p' = pred * m, loss = mean over all pixels of |g' - p'| where
+ * g' > 0; the cotangents of `depth` and `alpha` are the unmasked chain scaled by m.
+ * The mask is a constant: it has no cotangent. */
+int gsr_l1_ssim_masked_forward(unsigned img_height, unsigned img_width,
+                               float ssim_lambda, int clamp_pred,
+                               const float *pred, const float *gt,
+                               const float *mask, float *maps, double *sums,
+                               float *loss_out, float *terms_out,
+                               gsr_stream_t stream);
+int gsr_l1_ssim_masked_backward(unsigned img_height, unsigned img_width,
+                                float ssim_lambda, int clamp_pred,
+                                const float *upstream, const float *pred,
+                                const float *gt, const float *mask,
+                                const float *maps, float *v_pred,
+                                gsr_stream_t stream);
+int gsr_l1_masked_forward(long long num_values, float weight, int clamp_pred,
+                          const float *pred, const float *gt,
+                          const float *mask, double *sums, float *loss_out,
+                          gsr_stream_t stream);
+int gsr_l1_masked_backward(long long num_values, float weight, int clamp_pred,
+                           const float *upstream, const float *pred,
+                           const float *gt, const float *mask, float *v_pred,
+                           gsr_stream_t stream);
+int gsr_depth_l1_masked_forward(long long num_pixels, const float *depth,
+                                const float *alpha, const float *gt,
+                                const float *mask, const float *depth_max,
+                                double *sums, float *loss_out,
+                                gsr_stream_t stream);
+int gsr_depth_l1_masked_backward(long long num_pixels, const float *upstream,
+                                 const float *depth, const float *alpha,
+                                 const float *gt, const float *mask,
+                                 const float *depth_max, float *v_depth,
+                                 float *v_alpha, gsr_stream_t stream);
+
 /* ---- SH colours from split coefficients (caller-side glue) --
  * gsr_sh_forward / gsr_sh_backward for models that keep the DC band and the
  * higher bands as two parameters (features_dc [n,3], features_rest [n,K-1,3])

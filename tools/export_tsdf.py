@@ -3,7 +3,7 @@
     python tools/export_tsdf.py --ply MODEL.ply --poses poses.json --out DIR
         [--voxel-length 0.01171875] [--sdf-trunc 0.06] [--depth-trunc 10] [--bounds x0 y0 z0 x1 y1 z1]
         [--capacity BLOCKS] [--alpha-min 0.5] [--background r g b] [--no-clean] [--min-component-faces 20000]
-        [--gt GT.{stl,ply}] [--gt-threshold T]
+        [--gt GT.{stl,ply}] [--gt-threshold T] [--masks MASKS.npy [--bounding-box]]
 
 Renders RGB + depth from every camera of `poses.json` (the trajectory file `TSDFFusion.read_trajectory` reads), fuses
 the views into a block-sparse TSDF volume (gs_fusion) and writes `point_cloud.ply` and `mesh.ply` to DIR.  File names
@@ -14,6 +14,13 @@ components of fewer than --min-component-faces faces and unreferenced vertices (
 JSON line also carries the surface distance of `mesh.ply` (fields `mesh_average_error`, `mesh_rms`, ...) and, when it
 was written, of `cleaned_mesh.ply` (`cleaned_average_error`, ...) against that ground truth: what tools/eval_surface.py
 prints for each file.
+
+--masks MASKS.npy restricts the fusion to an object, as `ExportTSDF`'s `using_mask` / `mask_path` do: a uint8 array
+[V,H,W] or [V,H,W,3], one mask per camera of `poses.json` in its order; a view's depth is fused only where its mask is
+non-zero (for three channels: where 0.21 R + 0.72 G + 0.07 B, truncated to 8 bits, is non-zero -- gs_fusion.export_mask).
+--bounding-box fuses inside the rectangle around each mask's non-zero pixels, grown by 5 pixels, instead (`bounding_box`).
+The toolkit reads the masks as PNG files (`Annotations/frame_%05d.png`); this project depends on no image library, so
+decoding them into the .npy array stays with the caller.
 """
 import argparse
 import json
@@ -44,6 +51,17 @@ def activated(raw, device):
             "sh_coeffs": torch.cat([t["features_dc"][:, None, :], t["features_rest"]], 1).contiguous()}
 
 
+def load_masks(path, num_views):
+    """--masks: [V,H,W] or [V,H,W,3] uint8, one mask per camera."""
+    masks = np.load(path)
+    if masks.dtype != np.uint8 or masks.ndim not in (3, 4) or (masks.ndim == 4 and masks.shape[-1] != 3):
+        raise SystemExit(f"export_tsdf: --masks must be a uint8 array [V,H,W] or [V,H,W,3], got {masks.dtype} "
+                         f"{masks.shape}")
+    if masks.shape[0] != num_views:
+        raise SystemExit(f"export_tsdf: {masks.shape[0]} masks for {num_views} cameras")
+    return masks
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--ply", required=True)
@@ -64,11 +82,18 @@ def parse_args(argv=None):
                     help="components of fewer faces are removed from cleaned_mesh.ply")
     ap.add_argument("--gt", default=None, help="ground-truth mesh (.stl or .ply): append surface-distance fields")
     ap.add_argument("--gt-threshold", type=float, default=None)
+    ap.add_argument("--masks", default=None,
+                    help="uint8 .npy [V,H,W] or [V,H,W,3], one object mask per camera: fuse depth only where it is "
+                         "non-zero (PNG masks must be decoded by the caller: no image library here)")
+    ap.add_argument("--bounding-box", action="store_true",
+                    help="with --masks: fuse inside each mask's bounding rectangle grown by 5 pixels")
     a = ap.parse_args(argv)
     if a.min_component_faces < 0:
         ap.error("--min-component-faces must not be negative")
     if a.gt_threshold is not None and not a.gt_threshold >= 0:
         ap.error("--gt-threshold must not be negative")
+    if a.bounding_box and not a.masks:
+        ap.error("--bounding-box needs --masks")
     return a
 
 
@@ -86,6 +111,7 @@ def main(argv=None):
 
     raw = read_gaussian_ply(a.ply)
     cams = read_poses_json(a.poses)
+    masks = load_masks(a.masks, len(cams)) if a.masks else None
     if a.bounds:
         lo, hi = np.asarray(a.bounds[:3]), np.asarray(a.bounds[3:])
     else:
@@ -99,7 +125,7 @@ def main(argv=None):
     K = params["sh_coeffs"].shape[1]
     bg = torch.tensor(a.background, dtype=torch.float32, device=vol.device)
     fuse_views(vol, params, cams, bg, {1: 0, 4: 1, 9: 2, 16: 3}.get(K, 4), alpha_min=a.alpha_min,
-               depth_trunc=a.depth_trunc)
+               depth_trunc=a.depth_trunc, masks=masks, bounding_box=a.bounding_box)
     points, colors, normals = vol.extract_point_cloud()
     vertices, vcolors, triangles = vol.extract_mesh()
     os.makedirs(a.out, exist_ok=True)
@@ -109,6 +135,8 @@ def main(argv=None):
     summary = {"views": len(cams), "blocks": [int(b) for b in vol.blocks], "capacity": vol.capacity,
                "allocated_blocks": vol.num_allocated_blocks, "points": int(points.shape[0]),
                "vertices": int(vertices.shape[0]), "triangles": int(triangles.shape[0]), "out": a.out}
+    if masks is not None:
+        summary["masks"] = "bounding box" if a.bounding_box else "mask"
     if a.clean:
         summary.update(write_cleaned(a.out, vertices, vcolors, triangles, a.min_component_faces))
     if a.gt:
