@@ -3,6 +3,7 @@ photometric loss head (f2), the one-launch Adam step (f1) and SH colours from
 split coefficients and the per-Gaussian activations (f4).  Same native library and C ABI (`include/gsraster.h`)
 as `rasterizer`; no CPU fallback."""
 from .loss import L1SSIMLoss, depth_l1_loss, depth_reg_loss, l1_loss, l1_ssim_loss  # noqa: F401
+from .mono_depth import local_pearson_loss, log_depth_loss, tv_loss  # noqa: F401
 from .canny import canny, canny_workspace_bytes, image2canny  # noqa: F401
 from .adam import FusedAdam  # noqa: F401
 from .sh import sh_backward_views, spherical_harmonics_split  # noqa: F401

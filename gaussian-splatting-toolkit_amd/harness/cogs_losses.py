@@ -12,7 +12,12 @@ that switches them on trains through the same loop.  What each follows:
   depth_reg_loss         depth_gs.py:521-528     mean (five-tap mean of the unmasked neighbours' depth - depth)^2 with
                                                  the NON-edge Canny mask of the ground-truth image
 
-`depth_reg_loss` is the one term that is not plain torch ops: the reference's `image2canny` (utils/losses.py:48-58) is
+`local_pearson_loss`, `scaled_log_depth_loss` and `tv_loss` also exist fused: `optional_depth_terms(fused=True)` takes
+them from `gs_fused.local_pearson_loss`, `gs_fused.log_depth_loss` and `gs_fused.tv_loss` (csrc/mono_depth.hip, DESIGN.md
+section 4.11: one kernel each way per term, float64 sums in a fixed order, the per-view mask multiplied in inside the
+kernels, the local-Pearson gradient without atomics).  The torch versions below stay the default and the CPU path.
+
+`depth_reg_loss` is the one term that has no plain-torch version: the reference's `image2canny` (utils/losses.py:48-58) is
 OpenCV on the host -- a device-to-host copy of the image, `cv2.Canny` and a copy back on every step.  Here the mask
 comes from `gs_fused.image2canny` (four HIP kernels, the rule of `cv::Canny` restated in include/gsraster.h) and the
 term from `gs_fused.depth_reg_loss` (one kernel each way): no image leaves the device.  Both exist on the GPU only,
@@ -112,14 +117,24 @@ def sparse_loss(opacities: torch.Tensor, sparse_lambda: float) -> torch.Tensor:
 
 
 def optional_depth_terms(cfg, step: int, pred_depth: torch.Tensor, gt_depth: torch.Tensor, gt_img: torch.Tensor,
-                         generator: Optional[torch.Generator] = None, mono_scale_shift=None) -> Dict[str, torch.Tensor]:
+                         generator: Optional[torch.Generator] = None, mono_scale_shift=None, fused: bool = False,
+                         mask: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
     """The `use_est_depth` branch of `DepthGSModel.get_loss_dict` (depth_gs.py:477-531) as a dict of terms the trainer
     sums unweighted (engine/trainer.py:497): local Pearson while step < depth_loss_stop_iteration, the scaled log-depth
     term when the batch carries a scale / shift, the TV term below step 20 000.  `cfg` carries the reference's field
     names (use_pearson_depth, local_patch_size, depth_loss_stop_iteration, use_scaled_est_depth,
     use_depth_regularization, using_tv_loss).  With a per-view mask the model multiplies it into the images before
     this branch (depth_gs.py:424-437): the caller passes ``pred_depth * mask``, ``gt_depth * mask`` and the masked
-    ground-truth image; the terms themselves know nothing of masks."""
+    ground-truth image; the terms themselves know nothing of masks.
+    `fused=True` (GPU tensors only; a CPU tensor raises): local Pearson, log-depth and TV come from the heads of
+    `gs_fused` on csrc/mono_depth.hip -- the same terms, the same keys in the same order.  `mask` ([H,W] or [H,W,1])
+    then goes INTO the heads: the caller passes the UNMASKED depths and the ground-truth image as it holds it (the
+    masked target, for the Canny mask); `mask` without `fused` is an error -- that path takes the products."""
+    if fused:
+        return _fused_depth_terms(cfg, step, pred_depth, gt_depth, gt_img, generator, mono_scale_shift, mask)
+    if mask is not None:
+        raise ValueError("optional_depth_terms: mask= goes into the fused heads (fused=True); without them pass "
+                         "pred_depth * mask, gt_depth * mask and the masked image")
     terms: Dict[str, torch.Tensor] = {}
     if step < cfg.depth_loss_stop_iteration and cfg.use_pearson_depth:
         terms["depth_local_pearson"] = local_pearson_loss(pred_depth, gt_depth, cfg.local_patch_size, 0.5, generator)
@@ -137,4 +152,26 @@ def optional_depth_terms(cfg, step: int, pred_depth: torch.Tensor, gt_depth: tor
         terms["depth_reg_loss"] = depth_reg_loss(pred, image2canny(gt_img, 50, 150, isEdge1=False))
     if cfg.using_tv_loss and step < 20_000:
         terms["tv_loss"] = tv_loss(pred)
+    return terms
+
+
+def _fused_depth_terms(cfg, step, pred_depth, gt_depth, gt_img, generator, mono_scale_shift, mask):
+    """`optional_depth_terms(fused=True)`: the same branch on gs_fused's heads."""
+    import gs_fused
+
+    terms: Dict[str, torch.Tensor] = {}
+    pred = pred_depth.squeeze(-1) if pred_depth.dim() == 3 else pred_depth
+    if step < cfg.depth_loss_stop_iteration and cfg.use_pearson_depth:
+        rows, cols = local_pearson_patches(pred.shape[0], pred.shape[1], cfg.local_patch_size, 0.5, generator,
+                                           pred.device)
+        terms["depth_local_pearson"] = gs_fused.local_pearson_loss(pred, gt_depth, cfg.local_patch_size, rows, cols,
+                                                                   mask=mask)
+    if cfg.use_scaled_est_depth and mono_scale_shift is not None:
+        terms["log_depth"] = gs_fused.log_depth_loss(pred, gt_depth, gt_img, *mono_scale_shift, mask=mask)
+    if cfg.use_depth_regularization:
+        masked_pred = pred if mask is None else pred * mask.reshape(pred.shape).to(pred.dtype)
+        terms["depth_reg_loss"] = gs_fused.depth_reg_loss(masked_pred,
+                                                          gs_fused.image2canny(gt_img, 50, 150, isEdge1=False))
+    if cfg.using_tv_loss and step < 20_000:
+        terms["tv_loss"] = gs_fused.tv_loss(pred, mask=mask)
     return terms

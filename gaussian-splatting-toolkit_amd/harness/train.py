@@ -478,6 +478,10 @@ class TrainConfig:
     use_scaled_est_depth: bool = False
     use_depth_regularization: bool = False
     using_tv_loss: bool = False
+    # the three monocular-depth terms (local Pearson, scaled log-depth, TV) from gs_fused's heads on csrc/mono_depth.hip
+    # instead of harness/cogs_losses.py's torch ops, the per-view mask multiplied in inside the kernels (DESIGN.md
+    # section 4.11).  GPU only.  Off until its device time has been measured against the torch path.
+    fused_mono_depth: bool = False
     # a per-view mask, as a dataset with object masks delivers one in `batch["mask"]`: "none"; "alpha" = the object's
     # silhouette (the hidden scene's accumulated opacity > 0.5); "box" = the central half of the image in both
     # directions (`view_masks`).  Both images -- and, for co-gs, both depth images -- are MULTIPLIED by it in front of
@@ -878,7 +882,12 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
                 if depth_on and cfg.use_est_depth:
                     # the monocular-depth branch (:477-531); the synthetic ground truth is metric: scale 1, shift 0
                     gtd = downscale_depth(gt_depth[v], d)
-                    if masked:  # depth_gs.py:424-437: the optional terms see the masked images (plain torch multiplies)
+                    if cfg.fused_mono_depth:  # the mask goes INTO the fused heads: unmasked depths, the masked target
+                        terms = cogs_losses.optional_depth_terms(cfg, step, out["depth"], gtd,
+                                                                target * m_step if masked else target,
+                                                                mono_scale_shift=(1.0, 0.0), fused=True,
+                                                                mask=m_step if masked else None)
+                    elif masked:  # depth_gs.py:424-437: the optional terms see the masked images (plain torch multiplies)
                         terms = cogs_losses.optional_depth_terms(cfg, step, out["depth"] * m_step, gtd * m_step[..., 0],
                                                                 target * m_step, mono_scale_shift=(1.0, 0.0))
                     else:

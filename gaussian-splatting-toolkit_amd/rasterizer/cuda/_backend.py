@@ -111,6 +111,12 @@ SYMBOLS = (
     "gsr_canny",
     "gsr_depth_reg_forward",
     "gsr_depth_reg_backward",
+    "gsr_local_pearson_forward",
+    "gsr_local_pearson_backward",
+    "gsr_log_depth_forward",
+    "gsr_log_depth_backward",
+    "gsr_tv_forward",
+    "gsr_tv_backward",
     "gsr_knn_workspace_bytes",
     "gsr_knn_build",
     "gsr_knn_query",

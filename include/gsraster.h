@@ -1172,6 +1172,68 @@ int gsr_depth_reg_backward(unsigned img_height, unsigned img_width, const float 
                            const float *pred, const float *mask, const float *scratch,
                            float *v_pred, gsr_stream_t stream);
 
+/* ---- monocular-depth terms of the co-gs model (depth_gs.py:477-531) ----
+ * pred, gt float [H,W]; mask float [H,W] or NULL.  With a mask every term is that of the float32
+ * products s = pred * mask and t = gt * mask (the model multiplies the per-view mask in before
+ * this branch, depth_gs.py:424-437; nothing is selected, the means stay over all pixels) and
+ * v_pred is scaled by the mask; without one s = pred, t = gt.  Everything else is float64 in
+ * registers; the scalars are float64 sums in a fixed order without atomics (bit-reproducible);
+ * the loss and v_pred are rounded to float32.  Differentiable w.r.t. pred only.  Every backward
+ * writes every element of v_pred (no zeroing needed) and reads `upstream` (float [1]) on the
+ * device.  NaN and inf propagate as in the source.  H * W in [1, 2^31).
+ *
+ * Local Pearson (utils/losses.py:26-45).  Patch p has its top-left corner at (rows[p], cols[p])
+ * -- int64 [n_corr] when index64 != 0, else int32 [n_corr], read on the device -- and n = box_p^2
+ * pixels.  With the means m_s, m_t and the centred sums S_ss, S_tt, S_st over the patch (two
+ * passes: means first):
+ *   loss_p = 1 - (n - 1) / n * S_st / sqrt(S_ss S_tt)     (biased covariance over unbiased
+ *                                                           deviations, as the source writes it)
+ *   loss   = (sum_p loss_p) / n_corr
+ *   v_pred[q] = upstream * mask[q] * (1 / n_corr) * sum over the patches p that cover q, in
+ *               ascending p, of A_p (B_p (s[q] - m_s) - (t[q] - m_t)),
+ *               A_p = (n - 1) / (n sqrt(S_ss S_tt)),  B_p = S_st / S_ss;   0 where none covers q
+ * A patch with S_ss = 0 or S_tt = 0, or box_p = 1, is 0 / 0: the loss is NaN and v_pred is NaN on
+ * that patch's pixels only.  A corner outside [0, H - box_p] x [0, W - box_p] is never
+ * dereferenced: its loss_p is NaN and it adds nothing to v_pred.  n_corr = 0: the loss and v_pred
+ * are NaN (0 / 0, as the source).  box_p in [1, min(H, W)], else GSR_EINVAL.
+ *   stats  double [n_corr, 5]: m_s, m_t, A, B, loss_p per patch, written by the forward, read by
+ *          the backward; needs no zeroing
+ *
+ * Scaled log-depth (depth_gs.py:492-519).  image float [H,W,3], scale_shift float [2] on the
+ * device.  With e = scale * s + shift - t, l = log(1 + |e|),
+ * lx[y,x] = exp(-mean_c |image[y,x,c] - image[y,x+1,c]|), ly the same towards row y + 1:
+ *   loss = sum_{x < W-1} lx l / (H (W - 1)) + sum_{y < H-1} ly l / ((H - 1) W)
+ *   v_pred = upstream * mask * scale * sign(e) / (1 + |e|)
+ *            * (lx / (H (W - 1)) [x < W-1] + ly / ((H - 1) W) [y < H-1]),        sign(0) = 0
+ * H = 1 or W = 1: the loss is NaN (the mean of an empty tensor).
+ *
+ * Total variation (utils/losses.py:197-207):
+ *   loss = sum_{x < W-1} |s[y,x] - s[y,x+1]| / (H (W - 1)) + sum_{y < H-1} |s[y,x] - s[y+1,x]| / ((H - 1) W)
+ *   v_pred = upstream * mask * the four-neighbour gather of the signs of those differences over
+ *            the same counts, sign(0) = 0.  H = 1 or W = 1: the loss is NaN.
+ *   partial  double [GSR_MONO_DEPTH_WORKSPACE_DOUBLES] (log-depth and TV); needs no zeroing */
+#define GSR_MONO_DEPTH_WORKSPACE_DOUBLES 2048
+int gsr_local_pearson_forward(unsigned img_height, unsigned img_width, int box_p, int n_corr,
+                              const float *pred, const float *gt, const float *mask,
+                              const void *rows, const void *cols, int index64, double *stats,
+                              float *loss_out, gsr_stream_t stream);
+int gsr_local_pearson_backward(unsigned img_height, unsigned img_width, int box_p, int n_corr,
+                               const float *upstream, const float *pred, const float *gt,
+                               const float *mask, const void *rows, const void *cols, int index64,
+                               const double *stats, float *v_pred, gsr_stream_t stream);
+int gsr_log_depth_forward(unsigned img_height, unsigned img_width, const float *pred,
+                          const float *gt, const float *image, const float *scale_shift,
+                          const float *mask, double *partial, float *loss_out,
+                          gsr_stream_t stream);
+int gsr_log_depth_backward(unsigned img_height, unsigned img_width, const float *upstream,
+                           const float *pred, const float *gt, const float *image,
+                           const float *scale_shift, const float *mask, float *v_pred,
+                           gsr_stream_t stream);
+int gsr_tv_forward(unsigned img_height, unsigned img_width, const float *pred, const float *mask,
+                   double *partial, float *loss_out, gsr_stream_t stream);
+int gsr_tv_backward(unsigned img_height, unsigned img_width, const float *upstream,
+                    const float *pred, const float *mask, float *v_pred, gsr_stream_t stream);
+
 /* ---- k nearest neighbours: points against a point cloud ----------------
  * What the toolkit's models ask scikit-learn for when they turn seed points into initial scales
  * (`k_nearest_sklearn`, vanilla_gs.py:136-140, 260-280), as a general query.  Reference points P
