@@ -24,6 +24,7 @@ calls the real models make):
 The data side (cameras on a sphere, ground truth rendered by this rasterizer
 from a hidden "true" scene) replaces the toolkit's datamanager.
 """
+import gc
 import math
 import os
 import time
@@ -533,10 +534,46 @@ def _sh_views_backward_autograd():
     return fn
 
 
-def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
-    """Fit a perturbed copy of a hidden scene to its own renders.  Returns timing
-    and quality numbers; every rank ends with identical parameters."""
-    dp = world > 1 or (cfg.force_exchange and dist.is_available() and dist.is_initialized())
+def _check_config(cfg: TrainConfig) -> None:
+    """The settings `train` refuses, before anything is rendered."""
+    if cfg.background_color not in ("random", "fixed"):
+        raise ValueError(f"unknown background_color {cfg.background_color!r}")
+    if cfg.model not in ("gaussian-splatting", "co-gs"):
+        raise ValueError(f"unknown model {cfg.model!r}")
+    if cfg.model == "co-gs" and (cfg.fused_render or cfg.use_graph):
+        raise ValueError("co-gs runs through the separate ops (fused_depth = one RGB + depth compositing pass)")
+    if cfg.mask not in ("none", "alpha", "box"):
+        raise ValueError(f"unknown mask {cfg.mask!r}")
+
+
+def _params(model: GaussianParams) -> Dict[str, torch.nn.Parameter]:
+    return {k: model.gauss[k] for k in PARAM_NAMES}
+
+
+def _zero_grads(model: GaussianParams) -> None:
+    for p in model.param_list():
+        p.grad = None
+
+
+def _hidden_scene(cfg: TrainConfig) -> Dict[str, np.ndarray]:
+    return blob_scene(cfg.num_gaussians, seed=cfg.seed, sh_degree=cfg.sh_degree, kind=cfg.scene,
+                      scale_lo=cfg.scene_scale[0], scale_hi=cfg.scene_scale[1], tex_cell=cfg.tex_cell,
+                      objects=cfg.scene_objects, extent=cfg.scene_extent)
+
+
+@dataclass
+class TrainData:
+    """What the toolkit's datamanager would deliver, rendered from the hidden scene."""
+    factors: List[int]                        # the downscale factors of the coarse-to-fine schedule, 1 included
+    cams_by_d: Dict[int, list]                # factor -> one CameraTensors per view
+    bg: torch.Tensor                          # scene.BACKGROUND: evaluation, and training unless the background is random
+    gt: List[torch.Tensor]                    # [H,W,3] per view, over `bg`
+    gt_rgba: Optional[List[torch.Tensor]]     # random background: [H,W,4] per view, straight colour
+    gt_depth: Optional[List[torch.Tensor]]    # co-gs: [H,W] per view, millimetre steps, 0 = no measurement
+    masks: Optional[List[torch.Tensor]]       # TrainConfig.mask: [H,W,1] per view
+
+
+def make_data(cfg: TrainConfig, device) -> TrainData:
     cams_np = orbit_cameras(cfg.num_views, cfg.width, cfg.height, radius=cfg.cam_radius)
     cams = [CameraTensors.from_numpy(c, device) for c in cams_np]
     # the coarse-to-fine schedule's cameras, one set per downscale factor
@@ -545,26 +582,9 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
     cams_by_d = {d: (cams if d == 1 else [CameraTensors.from_numpy(rescale_camera(c, d), device) for c in cams_np])
                  for d in factors}
     bg = torch.tensor(S.BACKGROUND, device=device)
-    random_bg = cfg.background_color == "random"
-    if cfg.background_color not in ("random", "fixed"):
-        raise ValueError(f"unknown background_color {cfg.background_color!r}")
-    # (the reference seeds every rank differently, scripts/train.py:54: the backgrounds differ per rank, as there)
-    bg_gen = torch.Generator(device=device).manual_seed(cfg.seed + 977 * (rank + 1)) if random_bg else None
-
-    if cfg.model not in ("gaussian-splatting", "co-gs"):
-        raise ValueError(f"unknown model {cfg.model!r}")
-    cogs = cfg.model == "co-gs"
-    if cogs and (cfg.fused_render or cfg.use_graph):
-        raise ValueError("co-gs runs through the separate ops (fused_depth = one RGB + depth compositing pass)")
-    if cfg.mask not in ("none", "alpha", "box"):
-        raise ValueError(f"unknown mask {cfg.mask!r}")
-    masked = cfg.mask != "none"
-    mk = lambda: blob_scene(cfg.num_gaussians, seed=cfg.seed, sh_degree=cfg.sh_degree, kind=cfg.scene,
-                            scale_lo=cfg.scene_scale[0], scale_hi=cfg.scene_scale[1], tex_cell=cfg.tex_cell,
-                            objects=cfg.scene_objects, extent=cfg.scene_extent)
-    truth = GaussianParams(mk(), device)
+    truth = GaussianParams(_hidden_scene(cfg), device)
     with torch.no_grad():
-        if random_bg:
+        if cfg.background_color == "random":
             # RGBA ground truth with straight (un-premultiplied) colour, as a blender-style dataset stores it:
             # rendered over black, C = sum c_i a_i T_i and A = 1 - T, colour = C / A
             zero = torch.zeros(3, device=device)
@@ -579,7 +599,7 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
             gt_rgba = None
             gt = [truth.render(c, bg, cfg.sh_degree)["rgb"] for c in cams]
         gt_depth = None
-        if cogs:
+        if cfg.model == "co-gs":
             # the sensor's depth image: z-depth of the hidden scene where it covers the pixel, 0 (= no measurement,
             # masked out by `gt_depth > 0`) elsewhere, in millimetre steps like the dataset's 16-bit PNGs
             gt_depth = []
@@ -588,14 +608,39 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
                                  fused_depth=device.type == "cuda")
                 gt_depth.append(quantise_depth_mm(torch.where(o["alpha"] > 0.5, o["depth"], torch.zeros_like(o["depth"]))
                                                   [..., 0]).contiguous())
-
         masks = None
-        if masked:
+        if cfg.mask != "none":
             masks = view_masks(cfg.mask, cfg.height, cfg.width,
                                [truth.render(c, bg, cfg.sh_degree)["alpha"] if cfg.mask == "alpha" else None
                                 for c in cams], device)
+    return TrainData(factors, cams_by_d, bg, gt, gt_rgba, gt_depth, masks)
 
-    raw = mk()
+
+def evaluate(model: GaussianParams, data: TrainData, cfg: TrainConfig) -> Dict[str, Optional[float]]:
+    """Means over `eval_views` full-size views: "psnr"; "psnr_masked" over the pixels with mask > 0.5 (with a mask);
+    "depth_err", mean |rendered depth - gt depth| over the measured pixels (co-gs)."""
+    cogs, masked = cfg.model == "co-gs", data.masks is not None
+    cams, bg, gt = data.cams_by_d[1], data.bg, data.gt
+    ps, pm, de = [], [], []
+    with torch.no_grad():
+        for i in np.linspace(0, cfg.num_views - 1, cfg.eval_views).astype(int):
+            if cogs:
+                o = model.render(cams[i], bg, cfg.sh_degree, render_depth=True, fused_depth=bg.is_cuda)
+            else:
+                o = model.render(cams[i], bg, cfg.sh_degree)
+            ps.append(psnr(o["rgb"], gt[i]))
+            if masked:
+                sel = data.masks[i][..., 0] > 0.5
+                pm.append(psnr(o["rgb"][sel], gt[i][sel]))
+            if cogs:
+                m = data.gt_depth[i] > 0
+                de.append(float((o["depth"][..., 0] - data.gt_depth[i]).abs()[m].mean()) if bool(m.any()) else 0.0)
+    return {"psnr": float(np.mean(ps)), "psnr_masked": float(np.mean(pm)) if masked else None,
+            "depth_err": float(np.mean(de)) if cogs else None}
+
+
+def initial_model(cfg: TrainConfig, device) -> GaussianParams:
+    raw = _hidden_scene(cfg)
     rng = np.random.default_rng(cfg.seed + 1)
     if cfg.init in ("sfm", "random"):
         raw = seed_model(raw, cfg.init_gaussians or 50_000, cfg.init, cfg.seed + 1, cfg.sh_degree,
@@ -613,382 +658,526 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
         raw = {k: np.ascontiguousarray(v[keep]) for k, v in raw.items()}
         raw["scales"] += np.float32(math.log(cfg.num_gaussians / cfg.init_gaussians) / 3.0)
     model = GaussianParams(raw, device)
-    model.split_sh = truth.split_sh = cfg.split_sh
-    model.fused_activations = truth.fused_activations = cfg.fused_activations
-    if cfg.fused_adam and device.type == "cuda":
-        # one optimiser, six parameter groups with the reference's learning rates
-        groups = [{"params": [model.gauss[k]], "lr": lr} for k, lr in LRS.items()]
-        if cfg.torch_fused_adam:
-            optims = {"all": torch.optim.Adam(groups, eps=1e-15, fused=True)}
-        else:
+    model.split_sh, model.fused_activations = cfg.split_sh, cfg.fused_activations
+    return model
+
+
+def make_optimisers(cfg: TrainConfig, model: GaussianParams, device, dp: bool):
+    """-> (optims, sharded): Adam per parameter group with the reference's learning rates -- one optimiser over six
+    groups with `fused_adam` on the GPU, six optimisers otherwise -- or, data parallel with `sharded_adam`, no
+    optimiser here and a `parallel.ShardedAdam` that runs one over this rank's rows."""
+    fused = cfg.fused_adam and device.type == "cuda"
+
+    def adam(groups):
+        if fused:
             from gs_fused import FusedAdam
 
-            optims = {"all": FusedAdam(groups, eps=1e-15)}
-    else:
-        optims = {k: torch.optim.Adam([model.gauss[k]], lr=lr, eps=1e-15) for k, lr in LRS.items()}
-    sharded = None
+            return FusedAdam(groups, eps=1e-15)
+        return torch.optim.Adam(groups, eps=1e-15)
+
     if cfg.sharded_adam and dp:
         from .parallel import ShardedAdam
 
-        if cfg.fused_adam and device.type == "cuda":
-            from gs_fused import FusedAdam
+        return {}, ShardedAdam(_params(model), LRS, adam, force=cfg.force_exchange)
+    if not fused:
+        return {k: torch.optim.Adam([model.gauss[k]], lr=lr, eps=1e-15) for k, lr in LRS.items()}, None
+    groups = [{"params": [model.gauss[k]], "lr": lr} for k, lr in LRS.items()]
+    return {"all": torch.optim.Adam(groups, eps=1e-15, fused=True) if cfg.torch_fused_adam else adam(groups)}, None
 
-            make = lambda groups: FusedAdam(groups, eps=1e-15)
+
+def make_exchange(cfg: TrainConfig, model: GaussianParams, sharded: bool, dp: bool):
+    """-> (exchange, sh_views): the gradient exchange, attached -- started per parameter from autograd hooks (overlaps
+    the rest of the backward), SH bands above the warm-up degree left out -- and whether the SH gradient travels as
+    the ranks' gathered colour cotangents (`TrainConfig.sh_exchange`)."""
+    exchange = GradientExchange(_params(model), average=True, force=cfg.force_exchange)
+    # a replayed HIP graph fires no hooks, and a hook during capture would put a collective INTO the
+    # graph (and reduce every gradient twice): under use_graph the exchange is started after the replay
+    exchange.use_hooks = not cfg.use_graph
+    if sharded:
+        exchange.enabled = False  # the gradients travel by reduce-scatter inside ShardedAdam.step()
+    exchange.attach()
+    # (through the one native call per view as well, but not under graph replay: no hooks there)
+    sh_views = dp and cfg.sh_exchange == "views" and exchange.enabled and exchange.use_hooks
+    if sh_views and not model.gauss["means"].is_cuda:
+        exchange.sh_views_backward = _sh_views_backward_autograd()  # no native kernel here: autograd of the SH op
+    return exchange, sh_views
+
+
+def loss_heads(cfg: TrainConfig, device):
+    """-> (photo, depth, fused_clamp).  `photo(pred, target, mask=None)`: (1 - lambda) L1 + lambda (1 - SSIM), for co-gs
+    (1 - lambda) L1 (`cogs_main_loss`).  `depth(out, gt_depth, mask=None)`: co-gs' depth L1 on the render's outputs,
+    None for the base model.  A mask is multiplied into both images (vanilla_gs.py:915-924, depth_gs.py:424-437).  With
+    `fused_loss` on the GPU the heads are gs_fused's kernels, the mask goes into them, and so does the clamp of the
+    rendered image at 1 (vanilla_gs.py:857): `fused_clamp`, the render then leaves it out."""
+    cogs, lam = cfg.model == "co-gs", cfg.ssim_lambda
+    fused = bool(cfg.fused_loss and device.type == "cuda")
+    if fused:
+        from gs_fused import depth_l1_loss, l1_loss, l1_ssim_loss
+
+        if cogs:
+            def photo(pred, target, mask=None):
+                return l1_loss(pred, target, 1.0 - lam, clamp_pred=True, mask=mask)
         else:
-            make = lambda groups: torch.optim.Adam(groups, eps=1e-15)
-        sharded = ShardedAdam({k: model.gauss[k] for k in PARAM_NAMES}, LRS, make, force=cfg.force_exchange)
-        optims = {}
-    fused_clamp = False
-    if cfg.fused_loss and device.type == "cuda":
-        from gs_fused import l1_ssim_loss
-
-        # the clamp of the rendered image at 1 (vanilla_gs.py:857) is folded into the loss kernels
-        fused_clamp = True
-        loss_fn = lambda pred, target, m=None: l1_ssim_loss(pred, target, cfg.ssim_lambda, clamp_pred=fused_clamp,
-                                                            mask=m)
+            def photo(pred, target, mask=None):
+                return l1_ssim_loss(pred, target, lam, clamp_pred=True, mask=mask)
     else:
-        def loss_fn(pred, target, m=None):
-            if m is not None:  # the reference's two multiplies
-                pred, target = pred * m, target * m
-            return ((1 - cfg.ssim_lambda) * (pred - target).abs().mean()
-                    + cfg.ssim_lambda * (1 - ssim(pred, target)))
+        def photo(pred, target, mask=None):
+            if mask is not None:  # the reference's two multiplies
+                pred, target = pred * mask, target * mask
+            if cogs:
+                return cogs_main_loss(pred, target, lam)
+            return (1 - lam) * (pred - target).abs().mean() + lam * (1 - ssim(pred, target))
 
-    depth_loss_fn = None
-    if cogs:
-        w_l1 = 1.0 - cfg.ssim_lambda
-        if cfg.fused_loss and device.type == "cuda":
-            from gs_fused import depth_l1_loss, l1_loss
+    if not cogs:
+        depth = None
+    elif fused and cfg.fused_depth:
+        def depth(out, gt_depth, mask=None):
+            return depth_l1_loss(out["depth_acc"], out["alpha"], gt_depth, mask=mask)
+    else:
+        def depth(out, gt_depth, mask=None):
+            if mask is None:
+                return cogs_depth_l1(out["depth"], gt_depth)
+            return cogs_depth_l1(out["depth"] * mask, gt_depth * mask[..., 0])
+    return photo, depth, fused
 
-            loss_fn = lambda pred, target, m=None: l1_loss(pred, target, w_l1, clamp_pred=fused_clamp, mask=m)
+
+class StepInputs:
+    """A step's background (vanilla_gs.py:688-690), ground truth (:859-868 downscaled, :870-881 composited over the
+    step's background) and mask for a view and a downscale factor.  What does not depend on the step is cached per
+    (view, factor): the resized mask, and with `fused_target` the two planes the target is one `addcmul` of."""
+
+    def __init__(self, cfg: TrainConfig, data: TrainData, device, rank: int = 0):
+        self.data, self.device, self.fused_target = data, device, cfg.fused_target
+        random_bg = cfg.background_color == "random"
+        # (the reference seeds every rank differently, scripts/train.py:54: the backgrounds differ per rank, as there)
+        self.bg_gen = torch.Generator(device=device).manual_seed(cfg.seed + 977 * (rank + 1)) if random_bg else None
+        self.bg_static = data.bg.clone() if (random_bg and cfg.use_graph) else None  # a replayed graph reads it here
+        self.target_cache = {}  # (view, factor) -> (resized alpha * rgb [h,w,3], resized 1 - alpha [h,w,1])
+        self.mask_cache = {}  # (view, factor) -> resized mask [h,w,1]
+
+    def __call__(self, v: int, d: int):
+        """-> (background [3], target [h,w,3], mask [h,w,1] or None); draws the step's background."""
+        data = self.data
+        if self.bg_gen is None:
+            bg, target = data.bg, downscale_image(data.gt[v], d)
         else:
-            loss_fn = lambda pred, target, m=None: (cogs_main_loss(pred, target, cfg.ssim_lambda) if m is None else
-                                                    cogs_main_loss(pred * m, target * m, cfg.ssim_lambda))
-        if cfg.fused_depth and cfg.fused_loss and device.type == "cuda":
-            depth_loss_fn = lambda out, gtd, m=None: depth_l1_loss(out["depth_acc"], out["alpha"], gtd, mask=m)
-        else:
-            depth_loss_fn = lambda out, gtd, m=None: (cogs_depth_l1(out["depth"], gtd) if m is None else
-                                                      cogs_depth_l1(out["depth"] * m, gtd * m[..., 0]))
+            bg = torch.rand(3, device=self.device, generator=self.bg_gen)
+            if self.fused_target:
+                planes = self.target_cache.get((v, d))
+                if planes is None:
+                    small = downscale_image(data.gt_rgba[v], d)
+                    a = small[..., 3:4]
+                    planes = self.target_cache[(v, d)] = ((a * small[..., :3]).contiguous(), (1 - a).contiguous())
+                target = torch.addcmul(planes[0], planes[1], bg)
+            else:
+                target = composite_with_background(downscale_image(data.gt_rgba[v], d), bg)
+            if self.bg_static is not None:
+                self.bg_static.copy_(bg)
+                bg = self.bg_static
+        mask = None
+        if data.masks is not None:
+            mask = self.mask_cache.get((v, d))
+            if mask is None:
+                mask = self.mask_cache[(v, d)] = downscale_mask(data.masks[v], d).contiguous()
+        return bg, target, mask
 
-    fused_stats = cfg.fused_activations and device.type == "cuda"
-    if fused_stats:
-        from gs_fused import densify_stats_
-    n = n0 = model.num_points
-    xys_grad_norm = torch.zeros(n, device=device)
-    vis_counts = torch.zeros(n, device=device, dtype=torch.int32)
-    max_2dsize = torch.zeros(n, device=device)
-    stats_first = cfg.densify  # the reference's `xys_grad_norm is None` (vanilla_gs.py:354)
+
+class DensifyState:
+    """`xys_grad_norm`, `vis_counts` and `max_2dsize` of after_train (vanilla_gs.py:344-372) and their restart after
+    every refinement (:491-493).  Who updates them: `update` in torch ops, or through `kernel`
+    (gs_fused.densify_stats_), or -- `native` -- the backward of gs_fused.render_gaussians itself, into a
+    `gs_fused.DensifyStats` whose tensors these then are.  `densify_until`: refinement's `stop_split_at`, from which
+    step on nothing is updated (:347); None without refinement.  `first_vis`: on the ranks above 0 of a refining
+    data-parallel run, which Gaussians the first view after a restart really saw (parallel.allreduce_densify_stats)."""
+
+    def __init__(self, n: int, device, max_dim: int, densify_until: Optional[int] = None, rank: int = 0,
+                 world: int = 1, kernel=None, native: bool = False):
+        self.device, self.max_dim, self.kernel, self.native = device, max_dim, kernel, native
+        self.stop_at = math.inf if densify_until is None else densify_until
+        self.watch_first_view = world > 1 and rank > 0 and densify_until is not None
+        self.reset(n)
+
+    def reset(self, n: int) -> None:
+        if self.native:
+            from gs_fused import DensifyStats
+
+            self.native = DensifyStats(n, self.device, self.max_dim)
+            self.xys_grad_norm, self.vis_counts, self.max_2dsize = self.native.as_tuple()
+        else:
+            self.xys_grad_norm = torch.zeros(n, device=self.device)
+            self.vis_counts = torch.zeros(n, device=self.device, dtype=torch.int32)
+            self.max_2dsize = torch.zeros(n, device=self.device)
+        self.restart()
+
+    def restart(self) -> None:
+        self.first = True  # the reference's `xys_grad_norm is None` (vanilla_gs.py:354)
+        self.first_vis = None
+        if self.native:
+            self.native.restart()
+
+    def as_tuple(self):
+        return self.xys_grad_norm, self.vis_counts, self.max_2dsize
+
+    def update(self, out, max_dim: int, step: int) -> None:
+        """After the backward of a view rendered to `out` (its "radii", and "xys" with the gradient retained)."""
+        if step < self.stop_at:
+            if self.native:
+                pass  # done by the backward
+            elif self.kernel is not None:
+                self.kernel(out["xys"].grad, out["radii"], max_dim, self.xys_grad_norm, self.vis_counts,
+                            self.max_2dsize, first=self.first)
+            else:
+                with torch.no_grad():
+                    visible = out["radii"] > 0
+                    g = out["xys"].grad
+                    gnorm = torch.zeros_like(self.xys_grad_norm) if g is None else g.norm(dim=-1)
+                    size = out["radii"].float() / max_dim
+                    if self.first:
+                        self.xys_grad_norm, self.vis_counts = gnorm.clone(), torch.ones_like(self.vis_counts)
+                        self.max_2dsize = torch.where(visible, size, torch.zeros_like(size))
+                    else:
+                        self.xys_grad_norm += torch.where(visible, gnorm, torch.zeros_like(gnorm))
+                        self.vis_counts += visible.to(torch.int32)
+                        self.max_2dsize = torch.where(visible, torch.maximum(self.max_2dsize, size), self.max_2dsize)
+            if self.first and self.watch_first_view:
+                self.first_vis = (out["radii"] > 0).to(torch.int32)
+        self.first = False
+
+
+def _round_capacity(need: int, fits: bool) -> int:
+    """Tile-list entries for a view that needed `need`: half as many again, rounded to 2^20.  `fits` (the lists it was
+    rendered with were large enough): 2^16 of slack, rounded up; otherwise the next step is taken."""
+    return ((int(1.5 * need) + 65536 + (1 << 20) - 1) >> 20) << 20 if fits else ((int(1.5 * need) + (1 << 20)) >> 20) << 20
+
+
+class FusedStep:
+    """An iteration with the view as ONE autograd node (gs_fused.render_gaussians: activations, projection, SH,
+    binning, compositing; the densification statistics from its backward), and with `use_graph` render -> loss ->
+    backward replayed as one HIP graph per view (gs_fused.render.ViewGraph).  Owns the tile lists' capacity."""
+    ph = None   # no phase events on this path
+    marks = ()
+
+    def __init__(self, cfg: TrainConfig, model, data: TrainData, stats: DensifyState, photo, exchange, sh_views: bool,
+                 dp: bool, history: list):
+        from gs_fused import ListCapacity, ViewSpec, render_gaussians
+        from gs_fused.render import ViewGraph
+
+        self.ViewSpec, self.render_gaussians, self.ViewGraph = ViewSpec, render_gaussians, ViewGraph
+        self.cfg, self.model, self.stats, self.photo, self.exchange = cfg, model, stats, photo, exchange
+        self.sh_views, self.dp, self.history = sh_views, dp, history
+
+        def graph_loss(out, targets):  # (with a mask: the second static target of the graph, [h,w,1])
+            return photo(out["rgb"], targets[0], targets[1] if len(targets) > 1 else None)
+
+        self.graph_loss = graph_loss  # (a closure over the head alone: a ViewGraph holds it, and must not hold this)
+        self.caps = ListCapacity()
+        self.vgraph = self.vkey = None
+        self.overflow_views = 0
+        cam, g_ = data.cams_by_d[1][0], model.gauss
+        with torch.no_grad():  # size the lists once, synchronously (vanilla: every view, utils.py:124)
+            while True:
+                probe = render_gaussians(g_["means"], g_["scales"], g_["quats"], g_["opacities"], g_["features_dc"],
+                                         g_["features_rest"], cam.viewmat, cam.projmat, cam.campos, data.bg,
+                                         ViewSpec(cfg.height, cfg.width, cam.fx, cam.fy, cam.cx, cam.cy, cfg.sh_degree),
+                                         self.caps.capacity)
+                need = int(probe["count"].item())
+                if need <= self.caps.capacity:
+                    self.caps.capacity = max(self.caps.capacity, _round_capacity(need, fits=True))
+                    break
+                self.caps.capacity = _round_capacity(need, fits=False)
+
+    def __call__(self, step, v, d, cam, deg, bg, target, mask):
+        cfg, caps, fstats, g_ = self.cfg, self.caps, self.stats.native, self.model.gauss
+        spec = self.ViewSpec(cam.height, cam.width, cam.fx, cam.fy, cam.cx, cam.cy, deg)
+        fstats.enabled = step < self.stats.stop_at
+        fstats.max_dim = max(cam.width, cam.height)  # `max(self.last_size)` of after_train
+        if not cfg.use_graph:
+            _zero_grads(self.model)
+            slot = caps.slot(bg.device)
+            used = caps.capacity
+            collector = self.exchange.begin_sh_views(
+                ("features_dc", "features_rest"), (g_["features_dc"], g_["features_rest"]), g_["means"], cam.campos,
+                cfg.sh_degree, deg) if self.sh_views else None
+            out = self.render_gaussians(g_["means"], g_["scales"], g_["quats"], g_["opacities"], g_["features_dc"],
+                                        g_["features_rest"], cam.viewmat, cam.projmat, cam.campos, bg, spec, used,
+                                        count_out=slot, stats=fstats, sh_collector=collector)
+            loss = self.photo(out["rgb"], target, mask)
+            loss.backward()
+            caps.submitted(slot, used, bg.device)
+            if caps.overflowed():
+                self.overflow_views += 1
+            return loss, out
+        targets = (target,) if mask is None else (target, mask)
+        # len(history) counts the refinements that swapped parameter tensors: N can come out unchanged (k culled,
+        # k duplicated) while every tensor the graph points at is gone
+        key = (spec, self.model.num_points, caps.capacity, fstats.enabled, len(self.history))
+        if self.vkey != key:  # new SH degree, N changed by refinement, or larger lists: capture again
+            self.vgraph = self.ViewGraph(_params(self.model), spec, caps.capacity, self.graph_loss, bg,
+                                         [t.shape for t in targets], stats=fstats)
+            self.vgraph.capture(cam.viewmat, cam.projmat, cam.campos, targets)
+            self.vkey = key
+        elif not self.vgraph.fits():  # the count of the previous replay is in pinned memory by now
+            self.overflow_views += 1
+            caps.capacity = _round_capacity(int(self.vgraph.count_host[0]), fits=False)
+        loss, out = self.vgraph.replay(cam.viewmat, cam.projmat, cam.campos, targets)
+        if self.dp:
+            self.exchange.start_all()  # a replayed graph fires no hooks
+        return loss, out
+
+
+def _est_depth_terms(cfg: TrainConfig, step: int, pred_depth, gt_depth, target, mask):
+    """co-gs' monocular-depth branch (depth_gs.py:477-531); the synthetic ground truth is metric: scale 1, shift 0.
+    With a mask the terms see the masked images (:424-437): plain torch multiplies here, except that
+    `fused_mono_depth`'s heads take the unmasked depths and multiply inside."""
+    if mask is not None:
+        target = target * mask
+        if not cfg.fused_mono_depth:
+            pred_depth, gt_depth, mask = pred_depth * mask, gt_depth * mask[..., 0], None
+    return cogs_losses.optional_depth_terms(cfg, step, pred_depth, gt_depth, target, mono_scale_shift=(1.0, 0.0),
+                                            fused=cfg.fused_mono_depth, mask=mask)
+
+
+def _cogs_terms(cfg: TrainConfig, step: int, model, out, target, mask, gt_depth, d: int, depth_head, depth_on: bool):
+    """What `DepthGSModel.get_loss_dict` adds to the photometric loss, in the order the trainer sums it."""
+    terms = []
+    if cfg.use_scale_regularization and step % 10 == 0:  # depth_gs.py:450-460
+        terms.append(cogs_losses.scale_regularisation(model.gauss["scales"], cfg.max_gauss_ratio))
+    if cfg.use_sparse_loss and step % 100 == 0:  # :462-467 (the raw opacity parameter, as written)
+        terms.append(cogs_losses.sparse_loss(model.gauss["opacities"], cfg.sparse_lambda))
+    if depth_on:
+        # `gt_depth = self.get_gt_img(batch["depth"])` (downscaled like the image under a resolution schedule)
+        gt_depth = downscale_depth(gt_depth, d)
+        if cfg.use_est_depth:
+            terms.extend(_est_depth_terms(cfg, step, out["depth"], gt_depth, target, mask).values())
+        else:
+            terms.append(depth_head(out, gt_depth, mask))
+    return terms
+
+
+class SeparateStep:
+    """An iteration through the models' own call sequence: `model.render` (activations, projection, SH, rasterise as
+    separate ops), the loss assembled in torch, `backward`.  On every `phase_every`-th step HIP events are recorded
+    around the phases; `end_phases` closes such a step after the optimiser."""
+    overflow_views = 0  # (the tile lists are rasterizer.rasterize's here: `_list_rebuilds`)
+
+    def __init__(self, cfg: TrainConfig, model, data: TrainData, heads, exchange, sh_views: bool, device):
+        self.cfg, self.model, self.gt_depth = cfg, model, data.gt_depth
+        self.photo, self.depth_head, fused_clamp = heads
+        cuda = device.type == "cuda"
+        cogs = self.cogs = cfg.model == "co-gs"
+        self.render_kw = dict(
+            retain_xys_grad=True, clamp_rgb=not fused_clamp, sh_exchange=exchange if sh_views else None,
+            caller_syncs=cfg.caller_syncs, render_depth=cogs, fused_depth=cogs and cfg.fused_depth and cuda,
+            normalise_depth=not (cogs and cfg.fused_depth and cfg.fused_loss and cuda and not cfg.use_est_depth))
+        self.depth_after = cfg.depth_loss_start_iteration if cogs and cfg.use_depth_loss else math.inf
+        self.phase_every = cfg.phase_every if cuda else 0
+        self.ph, self.depth_on = None, False
+        self.marks = []  # (downscale factor, 5 events, depth loss on) per sampled step
+
+    def __call__(self, step, v, d, cam, deg, bg, target, mask):
+        _zero_grads(self.model)
+        ph = self.ph = _phase_marks(5) if (self.phase_every and step % self.phase_every == 0) else None
+        if ph:
+            ph[0].record()
+        out = self.model.render(cam, bg, deg, **self.render_kw)
+        if ph:
+            ph[1].record()
+        loss = self.photo(out["rgb"], target, mask)
+        if self.cogs:
+            self.depth_on = step > self.depth_after
+            for term in _cogs_terms(self.cfg, step, self.model, out, target, mask, self.gt_depth[v], d,
+                                    self.depth_head, self.depth_on):
+                loss = loss + term
+        if ph:
+            ph[2].record()
+        loss.backward()
+        if ph:
+            ph[3].record()
+        return loss, out
+
+    def end_phases(self, d: int) -> None:
+        self.ph[4].record()
+        self.marks.append((d, self.ph, self.depth_on))
+
+
+def refine_model(cfg: TrainConfig, rcfg, step: int, model, optims, sharded, exchange, stats: DensifyState,
+                 max_dim: int, dp: bool, history: list) -> None:
+    """`refinement_after` (vanilla_gs.py:381-497): the statistics all-reduced under data parallelism, split /
+    duplicate / cull / opacity reset (`_refine`), the new tensors and their Adam moments installed in the model, the
+    optimisers, the gradient exchange and the sharded update, and the statistics restarted.  `history` gets (step, N)
+    when the model's tensors changed."""
+    branch, reset = _refinement_branch(rcfg, step, cfg.num_views)
+    if branch != "none" or reset:
+        if dp and branch == "densify":
+            allreduce_densify_stats(*stats.as_tuple(), first_visible=stats.first_vis, force=cfg.force_exchange)
+        old = _params(model)
+        moments = {}
+        for o in optims.values():
+            moments.update(_adam_moments(o, old))
+        if sharded is not None:
+            moments = sharded.full_moments()  # refinement moves whole rows of both moments
+        new, new_moments, info = _refine(old, moments, stats.as_tuple(), rcfg, step, cfg.num_views, max_dim,
+                                         seed=cfg.refine_seed + step)
+        if any(new[k] is not old[k] for k in PARAM_NAMES):
+            model.replace(new)
+            cur = _params(model)
+            for o in optims.values():
+                _swap_parameters(o, old, cur, new_moments)
+            if info["n_out"] != info["n_in"]:
+                stats.reset(info["n_out"])
+            history.append((step, model.num_points))
+            exchange.rebind(_params(model))
+        if sharded is not None:
+            # new tensors, or the same ones with an opacity reset (which zeroed moments in the
+            # gathered copies): cut this rank's rows again
+            sharded.bind(_params(model), new_moments)
+    # the statistics restart after every refinement_after past the warm-up (:491-493)
+    stats.restart()
+
+
+def phase_record(marks, cfg: TrainConfig, factors) -> Dict:
+    """The four `phase_ms_*` entries of the result from the steps' events: medians over all sampled steps, per
+    resolution under a coarse-to-fine schedule, before / after co-gs' depth loss joins, and every sample."""
+    rec = dict.fromkeys(("phase_ms_median", "phase_ms_median_by_resolution", "phase_ms_median_by_depth_loss",
+                         "phase_ms_series"))
+    if not marks:
+        return rec
+    names = ("render", "loss", "backward", "stats_exchange_optimizer")
+
+    def med(marks):
+        ms = np.array([[m[i].elapsed_time(m[i + 1]) for i in range(4)] for m in marks])
+        out = {k: round(float(np.median(ms[:, i])), 4) for i, k in enumerate(names)}
+        out["samples"] = len(marks)
+        return out
+
+    rec["phase_ms_median"] = med([m for _, m, _ in marks])
+    if len(factors) > 1:  # the coarse-to-fine schedule: one set of medians per resolution
+        rec["phase_ms_median_by_resolution"] = {
+            f"{cfg.width // d_}x{cfg.height // d_}": med([m for dd, m, _ in marks if dd == d_])
+            for d_ in sorted({dd for dd, _, _ in marks}, reverse=True)}
+    if cfg.model == "co-gs":  # before / after the depth loss joins (the depth pass then has a backward as well)
+        rec["phase_ms_median_by_depth_loss"] = {
+            ("depth_loss_on" if on else "depth_loss_off"): med([m for _, m, o in marks if o == on])
+            for on in sorted({o for _, _, o in marks})}
+    if cfg.phase_series:
+        rec["phase_ms_series"] = [[dd] + [round(m[i].elapsed_time(m[i + 1]), 4) for i in range(4)] for dd, m, _ in marks]
+    return rec
+
+
+def result_record(cfg: TrainConfig, device, world: int, model, run: Dict, eval0: Dict, eval1: Dict, phases: Dict) -> Dict:
+    """What `train` returns.  `run`: what the driver counted (see there)."""
+    steps, elapsed = cfg.iters - run["start_step"], run["elapsed"]
+    cogs, masked = cfg.model == "co-gs", cfg.mask != "none"
+    checksum = float(sum(p.detach().double().sum() for p in model.param_list()))
+    return {"iters": steps, "start_step": run["start_step"], "seconds": elapsed,
+            "iters_per_s": steps / elapsed, "psnr_start": eval0["psnr"],
+            "psnr_end": eval1["psnr"], "losses": run["losses"], "param_checksum": checksum,
+            "views_per_s": world * steps / elapsed, "num_gaussians_start": run["n0"],
+            "num_gaussians_end": model.num_points, "refinements": run["history"],
+            # (step, bytes) whenever the per-step exchange volume changed: SH warm-up, refinement
+            "allreduce_bytes": run["exchanged_bytes"],
+            "render": run["render"], "list_overflow_views": run["overflow_views"], **phases,
+            "depth_segments": _depth_segments_record(device),
+            "schedule": {"num_downscales": cfg.num_downscales, "resolution_schedule": cfg.resolution_schedule,
+                         "background_color": cfg.background_color, "caller_syncs": cfg.caller_syncs},
+            "update": run["update"], "init": cfg.init, "model": cfg.model, "mask": cfg.mask,
+            **({"psnr_masked_start": eval0["psnr_masked"], "psnr_masked_end": eval1["psnr_masked"]} if masked else {}),
+            "depth": ({"loss_from_step": cfg.depth_loss_start_iteration + 1 if cfg.use_depth_loss else None,
+                       "one_compositing_pass": bool(cfg.fused_depth and device.type == "cuda"),
+                       "mean_abs_error_start_end": [eval0["depth_err"], eval1["depth_err"]]} if cogs else None),
+            "peak_memory_bytes": (int(torch.cuda.max_memory_allocated(device)) if device.type == "cuda" else None),
+            "densify_grad_thresh": (run["rcfg"].densify_grad_thresh if cfg.densify else None)}
+
+
+def _note_bytes(log: list, step: int, nbytes: int) -> None:
+    if not log or log[-1][1] != nbytes:
+        log.append((step, nbytes))
+
+
+def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
+    """Fit a perturbed copy of a hidden scene to its own renders.  Returns timing
+    and quality numbers; every rank ends with identical parameters."""
+    _check_config(cfg)
+    cuda = device.type == "cuda"
+    dp = world > 1 or (cfg.force_exchange and dist.is_available() and dist.is_initialized())
+    data = make_data(cfg, device)
+    model = initial_model(cfg, device)
+    optims, sharded = make_optimisers(cfg, model, device, dp)
+    heads = loss_heads(cfg, device)
     rcfg = cfg.refine
-    if cfg.densify:
-        if rcfg is None:
-            from gs_fused import RefineConfig
+    if cfg.densify and rcfg is None:
+        from gs_fused import RefineConfig
 
-            rcfg = RefineConfig()
-    history = []  # (step, N) after every refinement that changed the model
-    max_dim = max(cfg.width, cfg.height)
-
-    depth_err = []  # co-gs: mean |rendered depth - gt depth| over the measured pixels, at every evaluate()
-    psnr_masked = []  # with a mask: PSNR over the pixels with mask > 0.5, at every evaluate()
-
-    def masked_psnr(rgb, i):
-        sel = masks[i][..., 0] > 0.5
-        return psnr(rgb[sel], gt[i][sel])
-
-    def evaluate():
-        with torch.no_grad():
-            idx = np.linspace(0, cfg.num_views - 1, cfg.eval_views).astype(int)
-            if not cogs:
-                if not masked:
-                    return float(np.mean([psnr(model.render(cams[i], bg, cfg.sh_degree)["rgb"], gt[i]) for i in idx]))
-                imgs = [model.render(cams[i], bg, cfg.sh_degree)["rgb"] for i in idx]
-                psnr_masked.append(float(np.mean([masked_psnr(im, i) for im, i in zip(imgs, idx)])))
-                return float(np.mean([psnr(im, gt[i]) for im, i in zip(imgs, idx)]))
-            ps, de, pm = [], [], []
-            for i in idx:
-                o = model.render(cams[i], bg, cfg.sh_degree, render_depth=True, fused_depth=device.type == "cuda")
-                ps.append(psnr(o["rgb"], gt[i]))
-                if masked:
-                    pm.append(masked_psnr(o["rgb"], i))
-                m = gt_depth[i] > 0
-                de.append(float((o["depth"][..., 0] - gt_depth[i]).abs()[m].mean()) if bool(m.any()) else 0.0)
-            depth_err.append(float(np.mean(de)))
-            if masked:
-                psnr_masked.append(float(np.mean(pm)))
-            return float(np.mean(ps))
-
+        rcfg = RefineConfig()
+    n0 = model.num_points
     start_step = 0
     if cfg.resume_from:
         from .checkpoint import load_checkpoint
 
         start_step = load_checkpoint(cfg.resume_from, model, optims, sharded=sharded)  # resizes the model to the saved N
-        n = model.num_points
-        xys_grad_norm = torch.zeros(n, device=device)
-        vis_counts = torch.zeros(n, device=device, dtype=torch.int32)
-        max_2dsize = torch.zeros(n, device=device)
-    psnr0 = evaluate()
-    losses = []
-    # gradient exchange: started per parameter from autograd hooks (overlaps the rest of the
-    # backward), SH bands above the warm-up degree left out
-    exchange = GradientExchange({k: model.gauss[k] for k in PARAM_NAMES}, average=True, force=cfg.force_exchange)
-    # a replayed HIP graph fires no hooks, and a hook during capture would put a collective INTO the
-    # graph (and reduce every gradient twice): under use_graph the exchange is started after the replay
-    exchange.use_hooks = not cfg.use_graph
-    if sharded is not None:
-        exchange.enabled = False  # the gradients travel by reduce-scatter inside ShardedAdam.step()
-    exchange.attach()
-    exchanged_bytes = []
-    if device.type == "cuda":
+    use_fused = (cfg.fused_render or cfg.use_graph) and cuda and cfg.split_sh and cfg.fused_loss \
+        and cfg.sh_degree in (0, 1, 2, 3)
+    kernel = None
+    if cfg.fused_activations and cuda and not use_fused:
+        from gs_fused import densify_stats_ as kernel
+    stats = DensifyState(model.num_points, device, max(cfg.width, cfg.height),
+                         densify_until=rcfg.stop_split_at if cfg.densify else None, rank=rank, world=world,
+                         kernel=kernel, native=use_fused)
+    eval0 = evaluate(model, data, cfg)
+    exchange, sh_views = make_exchange(cfg, model, sharded is not None, dp)
+    inputs = StepInputs(cfg, data, device, rank)
+    means_group = None  # the scheduled learning rate's param group (after load_checkpoint, which replaces the groups)
+    if cfg.means_lr_schedule and sharded is None:
+        means_group = (optims["all"] if "all" in optims else optims["means"]).param_groups[0]
+    losses, history, exchanged_bytes = [], [], []  # history: (step, N) after every refinement that changed the model
+    cams_by_d = data.cams_by_d
+    if cuda:
         torch.cuda.synchronize(device)
     if dp:
         dist.barrier()
     # the ~170 k objects that torch and the setup above leave tracked never die during training: taken out of the
     # cyclic collector's generations for the duration of the loop, so that its full passes (~30 ms each over those
     # objects) do not recur -- the loop's own garbage is still collected
-    import gc
-
     gc.collect()
     gc.freeze()
-    if device.type == "cuda":
+    if cuda:
         torch.cuda.reset_peak_memory_stats(device)
     t0 = time.perf_counter()
-    use_fused = (cfg.fused_render or cfg.use_graph) and device.type == "cuda" and cfg.split_sh and cfg.fused_loss \
-        and cfg.sh_degree in (0, 1, 2, 3)
-    # (through the one native call per view as well, but not under graph replay: no hooks there)
-    sh_views = dp and cfg.sh_exchange == "views" and exchange.enabled and exchange.use_hooks
-    if sh_views and device.type != "cuda":
-        exchange.sh_views_backward = _sh_views_backward_autograd()  # no native kernel here: autograd of the SH op
-    fstats = caps = vgraph = vkey = None
-    generation = 0
-    overflow_views = 0
-    if use_fused:
-        from gs_fused import DensifyStats, ListCapacity, ViewSpec, render_gaussians
-        from gs_fused.render import ViewGraph
-
-        fstats = DensifyStats(model.num_points, device, max_dim)
-        caps = ListCapacity()
-        # (with a mask: the second static target of the graph, [h,w,1])
-        graph_loss = lambda out, targets: loss_fn(out["rgb"], targets[0], targets[1] if masked else None)
-        with torch.no_grad():  # size the lists once, synchronously (vanilla: every view, utils.py:124)
-            while True:
-                g_ = model.gauss
-                probe = render_gaussians(g_["means"], g_["scales"], g_["quats"], g_["opacities"], g_["features_dc"],
-                                         g_["features_rest"], cams[0].viewmat, cams[0].projmat, cams[0].campos, bg,
-                                         ViewSpec(cfg.height, cfg.width, cams[0].fx, cams[0].fy, cams[0].cx,
-                                                  cams[0].cy, cfg.sh_degree), caps.capacity)
-                need = int(probe["count"].item())
-                if need <= caps.capacity:
-                    caps.capacity = max(caps.capacity, ((int(1.5 * need) + 65536 + (1 << 20) - 1) >> 20) << 20)
-                    break
-                caps.capacity = ((int(1.5 * need) + (1 << 20)) >> 20) << 20
-    def zero_grads():
-        for p_ in model.param_list():
-            p_.grad = None
-
-    phase_marks = []
-    first_pending, first_vis = True, None
-    rebuilds0 = _list_rebuilds()
-    target_cache = {}  # (view, downscale factor) -> (resized alpha * rgb [h,w,3], resized 1 - alpha [h,w,1])
-    mask_cache = {}  # (view, downscale factor) -> resized mask [h,w,1]: it does not depend on the step
-    bg_static = bg.clone() if (random_bg and cfg.use_graph) else None  # a replayed graph reads its background here
     try:  # (ADVICE r4: an exception in the loop must not leave the collector frozen for the rest of the process)
+        if use_fused:  # (sizes its tile lists with a probe render: inside the timed region, as the first view is)
+            run_step = FusedStep(cfg, model, data, stats, heads[0], exchange, sh_views, dp, history)
+        else:
+            run_step = SeparateStep(cfg, model, data, heads, exchange, sh_views, device)
+        rebuilds0 = _list_rebuilds()
         for step in range(start_step, cfg.iters):
-            ph = None
             v = view_for_rank(step, rank, world, cfg.num_views)
             deg = min(step // cfg.sh_degree_interval, cfg.sh_degree)
             exchange.active_rows["features_rest"] = (deg + 1) ** 2 - 1
-            # this step's resolution (vanilla_gs.py:646-657, 719-720), background (:688-690) and ground truth
-            # (:859-868 downscaled every step, :870-881 composited over the step's background)
+            # this step's resolution (vanilla_gs.py:646-657, 719-720), background, ground truth and mask
             d = downscale_factor(step, cfg.num_downscales, cfg.resolution_schedule)
             cam = cams_by_d[d][v]
             max_dim = max(cam.width, cam.height)  # `max(self.last_size)` of after_train / refinement_after
-            if random_bg:
-                bg_step = torch.rand(3, device=device, generator=bg_gen)
-                if cfg.fused_target:
-                    planes = target_cache.get((v, d))
-                    if planes is None:
-                        small = downscale_image(gt_rgba[v], d)
-                        a_ = small[..., 3:4]
-                        planes = target_cache[(v, d)] = ((a_ * small[..., :3]).contiguous(), (1 - a_).contiguous())
-                    target = torch.addcmul(planes[0], planes[1], bg_step)
-                else:
-                    target = composite_with_background(downscale_image(gt_rgba[v], d), bg_step)
-                if bg_static is not None:
-                    bg_static.copy_(bg_step)
-                    bg_step = bg_static
-            else:
-                bg_step, target = bg, downscale_image(gt[v], d)
-            m_step = None
-            if masked:
-                m_step = mask_cache.get((v, d))
-                if m_step is None:
-                    m_step = mask_cache[(v, d)] = downscale_mask(masks[v], d).contiguous()
-            if use_fused:
-                spec = ViewSpec(cam.height, cam.width, cam.fx, cam.fy, cam.cx, cam.cy, deg)
-                fstats.enabled = not (cfg.densify and step >= rcfg.stop_split_at)
-                fstats.max_dim = max_dim
-                g_ = model.gauss
-                if cfg.use_graph:
-                    # `generation` counts the refinements that swapped parameter tensors: N can come out
-                    # unchanged (k culled, k duplicated) while every tensor the graph points at is gone
-                    key = (spec, model.num_points, caps.capacity, fstats.enabled, generation)
-                    if vkey != key:  # new SH degree, N changed by refinement, or larger lists: capture again
-                        vgraph = ViewGraph({k: g_[k] for k in PARAM_NAMES}, spec, caps.capacity, graph_loss, bg_step,
-                                           [(cam.height, cam.width, 3)] + ([(cam.height, cam.width, 1)] if masked else []),
-                                           stats=fstats)
-                        vgraph.capture(cam.viewmat, cam.projmat, cam.campos, (target, m_step) if masked else (target,))
-                        vkey = key
-                    else:
-                        # the count of the previous replay is in pinned memory by now
-                        if not vgraph.fits():
-                            overflow_views += 1
-                            caps.capacity = ((int(1.5 * int(vgraph.count_host[0])) + (1 << 20)) >> 20) << 20
-                    loss, out = vgraph.replay(cam.viewmat, cam.projmat, cam.campos,
-                                              (target, m_step) if masked else (target,))
-                    if dp:
-                        exchange.start_all()
-                else:
-                    zero_grads()
-                    slot = caps.slot(device)
-                    used = caps.capacity
-                    collector = exchange.begin_sh_views(("features_dc", "features_rest"),
-                                                        (g_["features_dc"], g_["features_rest"]), g_["means"], cam.campos,
-                                                        cfg.sh_degree, deg) if sh_views else None
-                    out = render_gaussians(g_["means"], g_["scales"], g_["quats"], g_["opacities"], g_["features_dc"],
-                                           g_["features_rest"], cam.viewmat, cam.projmat, cam.campos, bg_step, spec, used,
-                                           count_out=slot, stats=fstats, sh_collector=collector)
-                    loss = loss_fn(out["rgb"], target, m_step)
-                    loss.backward()
-                    caps.submitted(slot, used, device)
-                    if caps.overflowed():
-                        overflow_views += 1
-            else:
-                zero_grads()
-                ph = _phase_marks(5) if (cfg.phase_every and step % cfg.phase_every == 0 and device.type == "cuda") else None
-                if ph:
-                    ph[0].record()
-                depth_on = cogs and cfg.use_depth_loss and step > cfg.depth_loss_start_iteration
-                out = model.render(cam, bg_step, deg, retain_xys_grad=True, clamp_rgb=not fused_clamp,
-                                   sh_exchange=exchange if sh_views else None, caller_syncs=cfg.caller_syncs,
-                                   render_depth=cogs, fused_depth=cogs and cfg.fused_depth and device.type == "cuda",
-                                   normalise_depth=not (cogs and cfg.fused_depth and cfg.fused_loss
-                                                        and device.type == "cuda" and not cfg.use_est_depth))
-                rgb = out["rgb"]
-                if ph:
-                    ph[1].record()
-                loss = loss_fn(rgb, target, m_step)
-                if cogs and cfg.use_scale_regularization and step % 10 == 0:  # depth_gs.py:450-460
-                    loss = loss + cogs_losses.scale_regularisation(model.gauss["scales"], cfg.max_gauss_ratio)
-                if cogs and cfg.use_sparse_loss and step % 100 == 0:  # :462-467 (the raw opacity parameter, as written)
-                    loss = loss + cogs_losses.sparse_loss(model.gauss["opacities"], cfg.sparse_lambda)
-                if depth_on and cfg.use_est_depth:
-                    # the monocular-depth branch (:477-531); the synthetic ground truth is metric: scale 1, shift 0
-                    gtd = downscale_depth(gt_depth[v], d)
-                    if cfg.fused_mono_depth:  # the mask goes INTO the fused heads: unmasked depths, the masked target
-                        terms = cogs_losses.optional_depth_terms(cfg, step, out["depth"], gtd,
-                                                                target * m_step if masked else target,
-                                                                mono_scale_shift=(1.0, 0.0), fused=True,
-                                                                mask=m_step if masked else None)
-                    elif masked:  # depth_gs.py:424-437: the optional terms see the masked images (plain torch multiplies)
-                        terms = cogs_losses.optional_depth_terms(cfg, step, out["depth"] * m_step, gtd * m_step[..., 0],
-                                                                target * m_step, mono_scale_shift=(1.0, 0.0))
-                    else:
-                        terms = cogs_losses.optional_depth_terms(cfg, step, out["depth"], gtd, target,
-                                                                mono_scale_shift=(1.0, 0.0))
-                    for term in terms.values():
-                        loss = loss + term
-                elif depth_on:
-                    # `gt_depth = self.get_gt_img(batch["depth"])` (downscaled like the image under a resolution schedule)
-                    loss = loss + depth_loss_fn(out, downscale_depth(gt_depth[v], d), m_step)
-                if ph:
-                    ph[2].record()
-                loss.backward()
-                if ph:
-                    ph[3].record()
-            # densification statistics (vanilla_gs.py:344-372; not updated past stop_split_at, :347)
-            if use_fused or (cfg.densify and step >= rcfg.stop_split_at):
-                pass
-            elif fused_stats:
-                densify_stats_(out["xys"].grad, out["radii"], max_dim, xys_grad_norm, vis_counts, max_2dsize,
-                               first=stats_first)
-            else:
-                with torch.no_grad():
-                    visible = out["radii"] > 0
-                    g = out["xys"].grad
-                    gnorm = torch.zeros_like(xys_grad_norm) if g is None else g.norm(dim=-1)
-                    size = out["radii"].float() / max_dim
-                    if stats_first:
-                        xys_grad_norm, vis_counts = gnorm.clone(), torch.ones_like(vis_counts)
-                        max_2dsize = torch.where(visible, size, torch.zeros_like(size))
-                    else:
-                        xys_grad_norm += torch.where(visible, gnorm, torch.zeros_like(xys_grad_norm))
-                        vis_counts += visible.to(torch.int32)
-                        max_2dsize = torch.where(visible, torch.maximum(max_2dsize, size), max_2dsize)
-            if first_pending and world > 1 and rank > 0 and cfg.densify and step < rcfg.stop_split_at:
-                # which Gaussians this rank's FIRST view after a refinement really saw (parallel.single_process_vis_counts)
-                first_vis = (out["radii"] > 0).to(torch.int32)
-            first_pending = False
-            stats_first = False
+            bg_step, target, m_step = inputs(v, d)
+            loss, out = run_step(step, v, d, cam, deg, bg_step, target, m_step)
+            stats.update(out, max_dim, step)
             if dp and sharded is None:
-                b = exchange.finish()
-                if not exchanged_bytes or exchanged_bytes[-1][1] != b:
-                    exchanged_bytes.append((step, b))
+                _note_bytes(exchanged_bytes, step, exchange.finish())
             if cfg.means_lr_schedule:
                 # the scheduler steps after the optimizer (trainer.py:479-525): iteration `step` runs at lr(step)
                 if sharded is not None:
                     sharded.set_lr("means", means_lr(step, LRS["means"]))
                 else:
-                    grp = optims["all"].param_groups[0] if "all" in optims else optims["means"].param_groups[0]
-                    grp["lr"] = means_lr(step, LRS["means"])
+                    means_group["lr"] = means_lr(step, LRS["means"])
             for o in optims.values():
                 o.step()
             if sharded is not None:
-                b = sharded.step()
-                if not exchanged_bytes or exchanged_bytes[-1][1] != b:
-                    exchanged_bytes.append((step, b))
-            if ph:
-                ph[4].record()
-                phase_marks.append((d, ph, bool(cogs and cfg.use_depth_loss and step > cfg.depth_loss_start_iteration)))
+                _note_bytes(exchanged_bytes, step, sharded.step())
+            if run_step.ph:
+                run_step.end_phases(d)
             # refinement_after: every refine_every iterations, after the optimizer step
             # (TrainingCallback(update_every_num_iters=refine_every), vanilla_gs.py:610-616)
             if cfg.densify and step % rcfg.refine_every == 0 and step > rcfg.warmup_length:
-                branch, reset = _refinement_branch(rcfg, step, cfg.num_views)
-                if branch != "none" or reset:
-                    if use_fused:
-                        xys_grad_norm, vis_counts, max_2dsize = fstats.as_tuple()
-                    if dp and branch == "densify":
-                        allreduce_densify_stats(xys_grad_norm, vis_counts, max_2dsize, first_visible=first_vis,
-                                                force=cfg.force_exchange)
-                    old = {k: model.gauss[k] for k in PARAM_NAMES}
-                    moments = {}
-                    for o in optims.values():
-                        moments.update(_adam_moments(o, old))
-                    if sharded is not None:
-                        moments = sharded.full_moments()  # refinement moves whole rows of both moments
-                    new, new_moments, info = _refine(old, moments, (xys_grad_norm, vis_counts, max_2dsize), rcfg, step,
-                                                     cfg.num_views, max_dim, seed=cfg.refine_seed + step)
-                    if any(new[k] is not old[k] for k in PARAM_NAMES):
-                        generation += 1
-                        model.replace(new)
-                        cur = {k: model.gauss[k] for k in PARAM_NAMES}
-                        for o in optims.values():
-                            _swap_parameters(o, old, cur, new_moments)
-                        if info["n_out"] != info["n_in"]:
-                            n = info["n_out"]
-                            xys_grad_norm = torch.empty(n, device=device)
-                            vis_counts = torch.empty(n, device=device, dtype=torch.int32)
-                            max_2dsize = torch.empty(n, device=device)
-                            if use_fused:
-                                fstats = DensifyStats(n, device, max_dim)
-                        history.append((step, model.num_points))
-                        exchange.rebind({k: model.gauss[k] for k in PARAM_NAMES})
-                    if sharded is not None:
-                        # new tensors, or the same ones with an opacity reset (which zeroed moments in the
-                        # gathered copies): cut this rank's rows again
-                        sharded.bind({k: model.gauss[k] for k in PARAM_NAMES}, new_moments)
-                # the statistics restart after every refinement_after past the warm-up (:491-493)
-                stats_first = True
-                first_pending, first_vis = True, None
-                if use_fused:
-                    fstats.restart()
+                refine_model(cfg, rcfg, step, model, optims, sharded, exchange, stats, max_dim, dp, history)
             if cfg.save_every and cfg.checkpoint_dir and step > 0 and step % cfg.save_every == 0 and \
                     (rank == 0 or sharded is not None):
                 from .checkpoint import save_checkpoint
@@ -999,59 +1188,23 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
                 losses.append(float(loss.detach()))
         if dp:
             dist.barrier()
-        if device.type == "cuda":
+        if cuda:
             torch.cuda.synchronize(device)
         elapsed = time.perf_counter() - t0
     finally:
         gc.unfreeze()
-    psnr1 = evaluate()
-    phases = phases_by_res = phases_by_depth = phase_series = None
-    if phase_marks:
-        if cfg.phase_series:
-            phase_series = [[dd] + [round(m[i].elapsed_time(m[i + 1]), 4) for i in range(4)] for dd, m, _ in phase_marks]
-        names = ("render", "loss", "backward", "stats_exchange_optimizer")
-
-        def med(marks):
-            ms = np.array([[m[i].elapsed_time(m[i + 1]) for i in range(4)] for m in marks])
-            out = {k: round(float(np.median(ms[:, i])), 4) for i, k in enumerate(names)}
-            out["samples"] = len(marks)
-            return out
-
-        phases = med([m for _, m, _ in phase_marks])
-        if len(factors) > 1:  # the coarse-to-fine schedule: one set of medians per resolution
-            phases_by_res = {f"{cfg.width // d_}x{cfg.height // d_}": med([m for dd, m, _ in phase_marks if dd == d_])
-                             for d_ in sorted({dd for dd, _, _ in phase_marks}, reverse=True)}
-        if cogs:  # before / after the depth loss joins (the depth pass then has a backward as well)
-            phases_by_depth = {("depth_loss_on" if on else "depth_loss_off"): med([m for _, m, o in phase_marks if o == on])
-                               for on in sorted({o for _, _, o in phase_marks})}
+    eval1 = evaluate(model, data, cfg)
     if cfg.export_ply and rank == 0:
         from gs_io.ply import write_gaussian_ply
 
         write_gaussian_ply(cfg.export_ply, {k: model.gauss[k].detach().cpu().numpy() for k in PARAM_NAMES})
-    checksum = float(sum(p.detach().double().sum() for p in model.param_list()))
-    return {"iters": cfg.iters - start_step, "start_step": start_step, "seconds": elapsed,
-            "iters_per_s": (cfg.iters - start_step) / elapsed, "psnr_start": psnr0,
-            "psnr_end": psnr1, "losses": losses, "param_checksum": checksum,
-            "views_per_s": world * (cfg.iters - start_step) / elapsed, "num_gaussians_start": n0,
-            "num_gaussians_end": model.num_points, "refinements": history,
-            # (step, bytes) whenever the per-step exchange volume changed: SH warm-up, refinement
-            "allreduce_bytes": exchanged_bytes,
-            "render": ("hip graph per view" if cfg.use_graph else "one fused op") if use_fused else "separate ops",
-            "list_overflow_views": overflow_views + (_list_rebuilds() - rebuilds0), "phase_ms_median": phases,
-            "phase_ms_median_by_resolution": phases_by_res, "phase_ms_median_by_depth_loss": phases_by_depth,
-            "phase_ms_series": phase_series,
-            "depth_segments": _depth_segments_record(device),
-            "schedule": {"num_downscales": cfg.num_downscales, "resolution_schedule": cfg.resolution_schedule,
-                         "background_color": cfg.background_color, "caller_syncs": cfg.caller_syncs},
-            "update": "reduce-scatter + sharded Adam + all-gather" if sharded is not None else
-            ("all-reduce (geometry) + all-gathered colour cotangents (SH) + Adam" if sh_views else "all-reduce + Adam"),
-            "init": cfg.init, "model": cfg.model, "mask": cfg.mask,
-            **({"psnr_masked_start": psnr_masked[0], "psnr_masked_end": psnr_masked[-1]} if masked else {}),
-            "depth": ({"loss_from_step": cfg.depth_loss_start_iteration + 1 if cfg.use_depth_loss else None,
-                       "one_compositing_pass": bool(cfg.fused_depth and device.type == "cuda"),
-                       "mean_abs_error_start_end": [depth_err[0], depth_err[-1]]} if cogs else None),
-            "peak_memory_bytes": (int(torch.cuda.max_memory_allocated(device)) if device.type == "cuda" else None),
-            "densify_grad_thresh": (rcfg.densify_grad_thresh if cfg.densify else None)}
+    run = {"start_step": start_step, "elapsed": elapsed, "n0": n0, "losses": losses, "history": history,
+           "exchanged_bytes": exchanged_bytes, "rcfg": rcfg,
+           "render": ("hip graph per view" if cfg.use_graph else "one fused op") if use_fused else "separate ops",
+           "overflow_views": run_step.overflow_views + (_list_rebuilds() - rebuilds0),
+           "update": "reduce-scatter + sharded Adam + all-gather" if sharded is not None else
+           ("all-reduce (geometry) + all-gathered colour cotangents (SH) + Adam" if sh_views else "all-reduce + Adam")}
+    return result_record(cfg, device, world, model, run, eval0, eval1, phase_record(run_step.marks, cfg, data.factors))
 
 
 def _phase_marks(n):
