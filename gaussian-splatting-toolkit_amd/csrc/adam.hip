@@ -13,6 +13,9 @@
 // torch/optim/adam.py `_single_tensor_adam`:
 //   m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2
 //   p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+// evaluated per element with torch's operations in torch's order -- `denom = sqrt(v) / bc2_sqrt + eps;
+// p -= step_size * (m / denom)`, step_size = lr / bc1 and bc2_sqrt formed in double on the host and rounded once --
+// so the update carries the roundings of torch's own float32 expression and no others.
 #include <cmath>
 
 #include "gsr_common.h"
@@ -31,15 +34,14 @@ struct AdamArgs {
 // c1 = 1 - b1 and c2 = 1 - b2 are formed in double on the host, as torch forms them
 // in Python floats (1.f - 0.999f is 4.7e-5 off 0.001f)
 struct Hyper {
-  float b1, c1, b2, c2, eps, bc1, inv_bc2_sqrt;
+  float b1, c1, b2, c2, eps, bc2_sqrt;
 };
 
 __device__ __forceinline__ void adam_one(float &p, const float g, float &m, float &v, const Hyper &h,
                                          const float step_size) {
   m = h.b1 * m + h.c1 * g;
   v = h.b2 * v + h.c2 * (g * g);
-  const float inv_bc2_sqrt = h.inv_bc2_sqrt, eps = h.eps;
-  const float denom = sqrtf(v) * inv_bc2_sqrt + eps;
+  const float denom = sqrtf(v) / h.bc2_sqrt + h.eps;
   p -= step_size * (m / denom);
 }
 
@@ -50,7 +52,7 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamArgs a, const Hyper
     if (i < a.num && (int)blockIdx.x >= a.first_block[i]) ti = i;
   const gsr_adam_tensor T = a.t[ti];
   const long long blk = (long long)blockIdx.x - a.first_block[ti];
-  const float step_size = T.lr / h.bc1;
+  const float step_size = T.lr;  // the host put lr / bc1 into its copy of the tensor list
   const long long n4 = T.n >> 2;
   const bool vec = ((reinterpret_cast<uintptr_t>(T.param) | reinterpret_cast<uintptr_t>(T.grad) |
                      reinterpret_cast<uintptr_t>(T.exp_avg) | reinterpret_cast<uintptr_t>(T.exp_avg_sq)) & 15) == 0;
@@ -97,6 +99,9 @@ GSR_EXPORT int gsr_adam_step(int num_tensors, const gsr_adam_tensor *tensors, do
   GSR_REQUIRE(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "adam_step: betas must be in [0,1)");
   if (num_tensors == 0) return GSR_OK;
   GSR_REQUIRE(tensors, "adam_step: null pointer");
+  // bias corrections in double, like torch (python floats), then rounded once
+  const double bc1 = 1.0 - std::pow(beta1, (double)step);
+  const double bc2 = 1.0 - std::pow(beta2, (double)step);
   AdamArgs a{};
   a.num = num_tensors;
   long long blocks = 0;
@@ -105,17 +110,15 @@ GSR_EXPORT int gsr_adam_step(int num_tensors, const gsr_adam_tensor *tensors, do
     GSR_REQUIRE(t.n >= 0, "adam_step: negative size");
     GSR_REQUIRE(t.n == 0 || (t.param && t.grad && t.exp_avg && t.exp_avg_sq), "adam_step: null pointer");
     a.t[i] = t;
+    a.t[i].lr = (float)((double)t.lr / bc1);  // step_size
     a.first_block[i] = (int)blocks;
     blocks += (t.n + 4 * kVecPerBlock - 1) / (4 * kVecPerBlock);
     GSR_REQUIRE(blocks < (1ll << 31), "adam_step: too many elements for one launch");
   }
   a.first_block[num_tensors] = (int)blocks;
   if (blocks == 0) return GSR_OK;
-  // bias corrections in double, like torch (python floats), then rounded once
-  const double bc1 = 1.0 - std::pow(beta1, (double)step);
-  const double bc2 = 1.0 - std::pow(beta2, (double)step);
-  const Hyper h{(float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)bc1,
-                (float)(1.0 / std::sqrt(bc2))};
+  const Hyper h{(float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
+                (float)std::sqrt(bc2)};
   hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, h);
   GSR_CHECK_LAUNCH("adam_step");
   return GSR_OK;

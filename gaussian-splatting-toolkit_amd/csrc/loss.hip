@@ -31,11 +31,20 @@ constexpr int kHalo = kWin - 1;
 constexpr int kTW = 32, kTH = 16;                  // tile of outputs per workgroup
 constexpr int kIW = kTW + kHalo, kIH = kTH + kHalo;  // staged inputs
 
-// normalised 11-tap Gaussian, sigma = 1.5 (pytorch_msssim._fspecial_gauss_1d)
-__constant__ float kW[kWin] = {0.00102838f, 0.00759876f, 0.03600077f, 0.10936069f, 0.21300553f,
-                               0.26601172f, 0.21300553f, 0.10936069f, 0.03600077f, 0.00759876f,
-                               0.00102838f};
-constexpr float kC1 = 0.01f * 0.01f, kC2 = 0.03f * 0.03f;
+// normalised 11-tap Gaussian, sigma = 1.5 (pytorch_msssim._fspecial_gauss_1d): the float32 values nearest to the
+// exact weights (nine digits: their sum is 1 - 1.4e-9; a window that does not sum to 1 biases E[x^2] - mu^2 with one
+// sign at every position).  The backward's transposed blur uses them.
+__constant__ float kW[kWin] = {0.0010283801f, 0.007598758f, 0.036000773f, 0.10936069f, 0.21300554f,
+                               0.26601171f,   0.21300554f,  0.10936069f,  0.036000773f, 0.007598758f,
+                               0.0010283801f};
+// The forward kernel forms the five window moments, S and its partial derivatives in double, with the exact
+// normalised weights kWd: in float32, E[x^2] and E[xy] carry ~22 roundings of size eps32 mu^2, which do not shrink with
+// the variance they are there to measure (flat backgrounds, ramps: variance <~ C2).  The inputs are float32, so their
+// products are exact in double; the three maps are rounded to float32 once, on the store.  Measurements: DESIGN.md 4.4.
+__constant__ double kWd[kWin] = {0.00102838008447911,  0.007598758135239185, 0.03600077212843083, 0.10936068950970002,
+                                 0.2130055377112537,   0.26601172486179436,  0.2130055377112537,  0.10936068950970002,
+                                 0.03600077212843083,  0.007598758135239185, 0.00102838008447911};
+constexpr double kC1 = 0.01 * 0.01, kC2 = 0.03 * 0.03;
 
 // The masked heads (kMasked) follow the models' `pred * mask`, `gt * mask` in front of the loss
 // (vanilla_gs.py:915-924, surface_gs.py:917-925, depth_gs.py:424-437): the products are ROUNDED VALUES, as the
@@ -44,6 +53,23 @@ constexpr float kC1 = 0.01f * 0.01f, kC2 = 0.03f * 0.03f;
 __device__ __forceinline__ float mul_rounded(const float a, const float b) {
 #pragma clang fp contract(off)
   return a * b;
+}
+
+// S and d S / d (mu1, E[x^2], E[xy]) (x = pred) at one position, from the five moments.  Every operation is rounded on
+// its own and S is the oracle's expression A1 A2 / (B1 B2): with pred == gt the moments of x and y are the same bits,
+// so A1 == B1 and A2 == B2 bit for bit, S is exactly 1 and the loss exactly 0, as in the reference.
+__device__ __forceinline__ void ssim_point(const double mu1, const double mu2, const double e11, const double e22,
+                                           const double e12, double &S, double &d_mu, double &d11, double &d12) {
+#pragma clang fp contract(off)
+  const double s11 = e11 - mu1 * mu1, s22 = e22 - mu2 * mu2, s12 = e12 - mu1 * mu2;
+  const double A1 = 2.0 * mu1 * mu2 + kC1, A2 = 2.0 * s12 + kC2;
+  const double B1 = mu1 * mu1 + mu2 * mu2 + kC1, B2 = s11 + s22 + kC2;
+  const double den = B1 * B2;
+  S = A1 * A2 / den;
+  const double dA1 = A2 / den, dA2 = A1 / den, dB1 = -S / B1, dB2 = -S / B2;
+  d_mu = dA1 * (2.0 * mu2) + dB1 * (2.0 * mu1) + dA2 * (-2.0 * mu2) + dB2 * (-2.0 * mu1);
+  d11 = dB2;        // d S / d E[x^2]
+  d12 = 2.0 * dA2;  // d S / d E[xy]
 }
 
 // img: [H,W,3] interleaved.  maps: [3 derivative kinds][3 channels][Hv][Wv] planar.
@@ -60,15 +86,15 @@ __global__ __launch_bounds__(256) void l1_ssim_fwd_kernel(
     const float *__restrict__ gt, const float *__restrict__ mask, float *__restrict__ maps,
     double *__restrict__ sums) {
   __shared__ float sx[kIH][kIW + 1], sy[kIH][kIW + 1];
-  __shared__ float hb[5][kIH][kTW + 1];
-  __shared__ float red[2][4];
+  __shared__ double hb[5][kIH][kTW + 1];  // 34 KB (43 KB with sx, sy)
+  __shared__ double red[2][4];
 
   const int Hv = H - kHalo, Wv = W - kHalo;
   const int c = blockIdx.z;
   const int ox = blockIdx.x * kTW, oy = blockIdx.y * kTH;
   const int tid = threadIdx.x;
 
-  float l1 = 0.f;
+  double l1 = 0.0;
   for (int i = tid; i < kIH * kIW; i += 256) {
     const int r = i / kIW, q = i % kIW;
     const int gy = oy + r, gx = ox + q;
@@ -83,7 +109,7 @@ __global__ __launch_bounds__(256) void l1_ssim_fwd_kernel(
         x = mul_rounded(x, m);
         y = mul_rounded(y, m);
       }
-      if (r < kTH && q < kTW) l1 += fabsf(x - y);  // every pixel belongs to exactly one tile
+      if (r < kTH && q < kTW) l1 += fabs((double)x - (double)y);  // every pixel belongs to exactly one tile
     }
     sx[r][q] = x;
     sy[r][q] = y;
@@ -93,10 +119,10 @@ __global__ __launch_bounds__(256) void l1_ssim_fwd_kernel(
   // horizontal pass of the five quantities
   for (int i = tid; i < kIH * kTW; i += 256) {
     const int r = i / kTW, q = i % kTW;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0;
 #pragma unroll
     for (int k = 0; k < kWin; ++k) {
-      const float x = sx[r][q + k], y = sy[r][q + k], w = kW[k];
+      const double x = sx[r][q + k], y = sy[r][q + k], w = kWd[k];
       a0 += w * x;
       a1 += w * y;
       a2 += w * (x * x);
@@ -112,35 +138,29 @@ __global__ __launch_bounds__(256) void l1_ssim_fwd_kernel(
   __syncthreads();
 
   // vertical pass + SSIM and its partials: 512 outputs, 2 per lane
-  float ssum = 0.f;
+  double ssum = 0.0;
   const size_t plane = (size_t)Hv * Wv;
   for (int i = tid; i < kTH * kTW; i += 256) {
     const int r = i / kTW, q = i % kTW;
     const int gy = oy + r, gx = ox + q;
     if (gy >= Hv || gx >= Wv) continue;
-    float mu1 = 0.f, mu2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
+    double mu1 = 0.0, mu2 = 0.0, e11 = 0.0, e22 = 0.0, e12 = 0.0;
 #pragma unroll
     for (int k = 0; k < kWin; ++k) {
-      const float w = kW[k];
+      const double w = kWd[k];
       mu1 += w * hb[0][r + k][q];
       mu2 += w * hb[1][r + k][q];
       e11 += w * hb[2][r + k][q];
       e22 += w * hb[3][r + k][q];
       e12 += w * hb[4][r + k][q];
     }
-    const float s11 = e11 - mu1 * mu1, s22 = e22 - mu2 * mu2, s12 = e12 - mu1 * mu2;
-    const float A1 = 2.f * mu1 * mu2 + kC1, A2 = 2.f * s12 + kC2;
-    const float B1 = mu1 * mu1 + mu2 * mu2 + kC1, B2 = s11 + s22 + kC2;
-    const float inv = 1.f / (B1 * B2);
-    const float S = A1 * A2 * inv;
+    double S, d_mu, d11, d12;
+    ssim_point(mu1, mu2, e11, e22, e12, S, d_mu, d11, d12);
     ssum += S;
-    // d S / d (mu1, E[x^2], E[xy]) with x = pred
-    const float dA1 = A2 * inv, dA2 = A1 * inv, dB1 = -S / B1, dB2 = -S / B2;
-    const float d_mu = dA1 * (2.f * mu2) + dB1 * (2.f * mu1) + dA2 * (-2.f * mu2) + dB2 * (-2.f * mu1);
     const size_t o = (size_t)c * plane + (size_t)gy * Wv + gx;
-    maps[o] = d_mu;
-    maps[3 * plane + o] = dB2;        // d S / d E[x^2]
-    maps[6 * plane + o] = 2.f * dA2;  // d S / d E[xy]
+    maps[o] = (float)d_mu;
+    maps[3 * plane + o] = (float)d11;
+    maps[6 * plane + o] = (float)d12;
   }
 
   // block reduction -> two double atomics
@@ -159,8 +179,8 @@ __global__ __launch_bounds__(256) void l1_ssim_fwd_kernel(
     // same two addresses serialised in the L2 (that alone was ~250 us of this kernel)
     const unsigned linear = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
     const unsigned slot = linear % GSR_LOSS_SUM_SLOTS;
-    atomicAdd(&sums[slot], (double)red[0][0] + red[0][1] + red[0][2] + red[0][3]);
-    atomicAdd(&sums[GSR_LOSS_SUM_SLOTS + slot], (double)red[1][0] + red[1][1] + red[1][2] + red[1][3]);
+    atomicAdd(&sums[slot], red[0][0] + red[0][1] + red[0][2] + red[0][3]);
+    atomicAdd(&sums[GSR_LOSS_SUM_SLOTS + slot], red[1][0] + red[1][1] + red[1][2] + red[1][3]);
   }
 }
 
