@@ -170,6 +170,111 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(
   num_tiles_hit[i] = o_tiles;
 }
 
+// What the chain of project_bwd_kernel holds for one VISIBLE Gaussian between the cotangents and v_mean3d: shared
+// with project_pose_partial_kernel (the camera gradients are sums of these terms), so that both kernels evaluate
+// every expression in the same float32 operations and order.
+struct BwdChain {
+  float px, py, pz;     // the centre
+  float vt0, vt1, vt3;  // cotangent of rows 0, 1, 3 of P p~
+  float vz;             // cotangent of depth = V[2,:] . p~
+  float vtx, vty, vtz;  // cotangent of the view-space centre t = V p~ through J
+  float j00, j02, j11, j12;  // the non-zero entries of J
+  M3 vT;                // cotangent of T = J W
+  float g2[3], g3[6], gm[3];
+};
+
+__device__ __forceinline__ void project_bwd_chain(
+    const int i, const float *__restrict__ means3d, const float *__restrict__ viewmat,
+    const float *__restrict__ projmat, const float fx, const float fy, const int img_w, const int img_h,
+    const float *__restrict__ cov3d, const float *__restrict__ conics, const float *__restrict__ compensation,
+    const float *__restrict__ v_xy, const float *__restrict__ v_depth, const float *__restrict__ v_conic,
+    const float *__restrict__ v_compensation, BwdChain &c) {
+  float *const g2 = c.g2, *const g3 = c.g3, *const gm = c.gm;
+  const float px = means3d[3 * i], py = means3d[3 * i + 1], pz = means3d[3 * i + 2];
+  const float *P = projmat;
+  const float *V = viewmat;
+
+  // pixel = ndc2pix(P p / (w + eps))  ->  d/dp  (helpers.cuh:125-142)
+  const float hx = P[0] * px + P[1] * py + P[2] * pz + P[3];
+  const float hy = P[4] * px + P[5] * py + P[6] * pz + P[7];
+  const float hw = P[12] * px + P[13] * py + P[14] * pz + P[15];
+  const float rw = 1.f / (hw + 1e-6f);
+  const float vnx = v_xy ? 0.5f * (float)img_w * v_xy[2 * i] : 0.f;
+  const float vny = v_xy ? 0.5f * (float)img_h * v_xy[2 * i + 1] : 0.f;
+  const float vt0 = vnx * rw, vt1 = vny * rw;
+  const float vt3 = -(vnx * hx + vny * hy) * rw * rw;
+  gm[0] = P[0] * vt0 + P[4] * vt1 + P[12] * vt3;
+  gm[1] = P[1] * vt0 + P[5] * vt1 + P[13] * vt3;
+  gm[2] = P[2] * vt0 + P[6] * vt1 + P[14] * vt3;
+
+  // depth = V[2,:] . p
+  const float vz = v_depth ? v_depth[i] : 0.f;
+  gm[0] += V[8] * vz;
+  gm[1] += V[9] * vz;
+  gm[2] += V[10] * vz;
+
+  // conic = inv(cov2d)  ->  v_cov2d = -X G X  (helpers.cuh:62-74)
+  const float X00 = conics[3 * i], X01 = conics[3 * i + 1], X11 = conics[3 * i + 2];
+  const float G00 = v_conic ? v_conic[3 * i] : 0.f, G01 = v_conic ? 0.5f * v_conic[3 * i + 1] : 0.f,
+              G11 = v_conic ? v_conic[3 * i + 2] : 0.f;
+  const float A00 = X00 * G00 + X01 * G01, A01 = X00 * G01 + X01 * G11;
+  const float A10 = X01 * G00 + X11 * G01, A11 = X01 * G01 + X11 * G11;
+  g2[0] = -(A00 * X00 + A01 * X01);
+  g2[1] = -(A00 * X01 + A01 * X11) - (A10 * X00 + A11 * X01);
+  g2[2] = -(A10 * X01 + A11 * X11);
+
+  // compensation = sqrt(det(cov2d - 0.3 I) / det(cov2d))  (helpers.cuh:76-90)
+  {
+    const float comp = compensation[i];
+    const float inv_det = X00 * X11 - X01 * X01;
+    const float om2 = 1.f - comp * comp;
+    const float vsq = (v_compensation ? v_compensation[i] : 0.f) * 0.5f / (comp + 1e-6f);
+    g2[0] += vsq * (om2 * X00 - 0.3f * inv_det);
+    g2[1] += 2.f * vsq * (om2 * X01);
+    g2[2] += vsq * (om2 * X11 - 0.3f * inv_det);
+  }
+
+  // cov2d = T V T^T, T = J W  (backward.cu:350-423; no fov clamp here)
+  const M3 W{V[0], V[1], V[2], V[4], V[5], V[6], V[8], V[9], V[10]};
+  const float tx = V[0] * px + V[1] * py + V[2] * pz + V[3];
+  const float ty = V[4] * px + V[5] * py + V[6] * pz + V[7];
+  const float tz = V[8] * px + V[9] * py + V[10] * pz + V[11];
+  const float rz = 1.f / tz, rz2 = rz * rz, rz3 = rz2 * rz;
+  const M3 J{fx * rz, 0.f, -fx * tx * rz2, 0.f, fy * rz, -fy * ty * rz2, 0.f, 0.f, 0.f};
+  const float *c3 = cov3d + 6 * i;
+  const M3 Vs{c3[0], c3[1], c3[2], c3[1], c3[3], c3[4], c3[2], c3[4], c3[5]};
+  const M3 Gc{g2[0], 0.5f * g2[1], 0.f, 0.5f * g2[1], g2[2], 0.f, 0.f, 0.f, 0.f};
+  const M3 T = mul(J, W);
+  const M3 vV = mul(mul(transpose(T), Gc), T);
+  g3[0] = vV.a00;
+  g3[1] = vV.a01 + vV.a10;
+  g3[2] = vV.a02 + vV.a20;
+  g3[3] = vV.a11;
+  g3[4] = vV.a12 + vV.a21;
+  g3[5] = vV.a22;
+  // v_T = G T V^T + G^T T V
+  const M3 P1 = mul(mul(Gc, T), transpose(Vs));
+  const M3 P2 = mul(mul(transpose(Gc), T), Vs);
+  const M3 vT{P1.a00 + P2.a00, P1.a01 + P2.a01, P1.a02 + P2.a02,
+              P1.a10 + P2.a10, P1.a11 + P2.a11, P1.a12 + P2.a12,
+              P1.a20 + P2.a20, P1.a21 + P2.a21, P1.a22 + P2.a22};
+  const M3 vJ = mul(vT, transpose(W));
+  const float vtx = -fx * rz2 * vJ.a02;
+  const float vty = -fy * rz2 * vJ.a12;
+  const float vtz = -fx * rz2 * vJ.a00 + 2.f * fx * tx * rz3 * vJ.a02 -
+                    fy * rz2 * vJ.a11 + 2.f * fy * ty * rz3 * vJ.a12;
+  gm[0] += vtx * W.a00 + vty * W.a10 + vtz * W.a20;
+  gm[1] += vtx * W.a01 + vty * W.a11 + vtz * W.a21;
+  gm[2] += vtx * W.a02 + vty * W.a12 + vtz * W.a22;
+
+  c.px = px; c.py = py; c.pz = pz;
+  c.vt0 = vt0; c.vt1 = vt1; c.vt3 = vt3;
+  c.vz = vz;
+  c.vtx = vtx; c.vty = vty; c.vtz = vtz;
+  c.j00 = J.a00; c.j02 = J.a02; c.j11 = J.a11; c.j12 = J.a12;
+  c.vT = vT;
+}
+
 __global__ __launch_bounds__(256) void project_bwd_kernel(
     const int n, const float *__restrict__ means3d,
     const float *__restrict__ scales, const float glob_scale,
@@ -185,89 +290,17 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
 
-  float g2[3] = {0.f, 0.f, 0.f};
-  float g3[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  float gm[3] = {0.f, 0.f, 0.f};
+  BwdChain c;
+  float *const g2 = c.g2, *const g3 = c.g3, *const gm = c.gm;
+  g2[0] = g2[1] = g2[2] = 0.f;
+  g3[0] = g3[1] = g3[2] = g3[3] = g3[4] = g3[5] = 0.f;
+  gm[0] = gm[1] = gm[2] = 0.f;
   float gs[3] = {0.f, 0.f, 0.f};
   float gq[4] = {0.f, 0.f, 0.f, 0.f};
 
   if (radii[i] > 0) {
-    const float px = means3d[3 * i], py = means3d[3 * i + 1], pz = means3d[3 * i + 2];
-    const float *P = projmat;
-    const float *V = viewmat;
-
-    // pixel = ndc2pix(P p / (w + eps))  ->  d/dp  (helpers.cuh:125-142)
-    const float hx = P[0] * px + P[1] * py + P[2] * pz + P[3];
-    const float hy = P[4] * px + P[5] * py + P[6] * pz + P[7];
-    const float hw = P[12] * px + P[13] * py + P[14] * pz + P[15];
-    const float rw = 1.f / (hw + 1e-6f);
-    const float vnx = v_xy ? 0.5f * (float)img_w * v_xy[2 * i] : 0.f;
-    const float vny = v_xy ? 0.5f * (float)img_h * v_xy[2 * i + 1] : 0.f;
-    const float vt0 = vnx * rw, vt1 = vny * rw;
-    const float vt3 = -(vnx * hx + vny * hy) * rw * rw;
-    gm[0] = P[0] * vt0 + P[4] * vt1 + P[12] * vt3;
-    gm[1] = P[1] * vt0 + P[5] * vt1 + P[13] * vt3;
-    gm[2] = P[2] * vt0 + P[6] * vt1 + P[14] * vt3;
-
-    // depth = V[2,:] . p
-    const float vz = v_depth ? v_depth[i] : 0.f;
-    gm[0] += V[8] * vz;
-    gm[1] += V[9] * vz;
-    gm[2] += V[10] * vz;
-
-    // conic = inv(cov2d)  ->  v_cov2d = -X G X  (helpers.cuh:62-74)
-    const float X00 = conics[3 * i], X01 = conics[3 * i + 1], X11 = conics[3 * i + 2];
-    const float G00 = v_conic ? v_conic[3 * i] : 0.f, G01 = v_conic ? 0.5f * v_conic[3 * i + 1] : 0.f,
-                G11 = v_conic ? v_conic[3 * i + 2] : 0.f;
-    const float A00 = X00 * G00 + X01 * G01, A01 = X00 * G01 + X01 * G11;
-    const float A10 = X01 * G00 + X11 * G01, A11 = X01 * G01 + X11 * G11;
-    g2[0] = -(A00 * X00 + A01 * X01);
-    g2[1] = -(A00 * X01 + A01 * X11) - (A10 * X00 + A11 * X01);
-    g2[2] = -(A10 * X01 + A11 * X11);
-
-    // compensation = sqrt(det(cov2d - 0.3 I) / det(cov2d))  (helpers.cuh:76-90)
-    {
-      const float comp = compensation[i];
-      const float inv_det = X00 * X11 - X01 * X01;
-      const float om2 = 1.f - comp * comp;
-      const float vsq = (v_compensation ? v_compensation[i] : 0.f) * 0.5f / (comp + 1e-6f);
-      g2[0] += vsq * (om2 * X00 - 0.3f * inv_det);
-      g2[1] += 2.f * vsq * (om2 * X01);
-      g2[2] += vsq * (om2 * X11 - 0.3f * inv_det);
-    }
-
-    // cov2d = T V T^T, T = J W  (backward.cu:350-423; no fov clamp here)
-    const M3 W{V[0], V[1], V[2], V[4], V[5], V[6], V[8], V[9], V[10]};
-    const float tx = V[0] * px + V[1] * py + V[2] * pz + V[3];
-    const float ty = V[4] * px + V[5] * py + V[6] * pz + V[7];
-    const float tz = V[8] * px + V[9] * py + V[10] * pz + V[11];
-    const float rz = 1.f / tz, rz2 = rz * rz, rz3 = rz2 * rz;
-    const M3 J{fx * rz, 0.f, -fx * tx * rz2, 0.f, fy * rz, -fy * ty * rz2, 0.f, 0.f, 0.f};
-    const float *c3 = cov3d + 6 * i;
-    const M3 Vs{c3[0], c3[1], c3[2], c3[1], c3[3], c3[4], c3[2], c3[4], c3[5]};
-    const M3 Gc{g2[0], 0.5f * g2[1], 0.f, 0.5f * g2[1], g2[2], 0.f, 0.f, 0.f, 0.f};
-    const M3 T = mul(J, W);
-    const M3 vV = mul(mul(transpose(T), Gc), T);
-    g3[0] = vV.a00;
-    g3[1] = vV.a01 + vV.a10;
-    g3[2] = vV.a02 + vV.a20;
-    g3[3] = vV.a11;
-    g3[4] = vV.a12 + vV.a21;
-    g3[5] = vV.a22;
-    // v_T = G T V^T + G^T T V
-    const M3 P1 = mul(mul(Gc, T), transpose(Vs));
-    const M3 P2 = mul(mul(transpose(Gc), T), Vs);
-    const M3 vT{P1.a00 + P2.a00, P1.a01 + P2.a01, P1.a02 + P2.a02,
-                P1.a10 + P2.a10, P1.a11 + P2.a11, P1.a12 + P2.a12,
-                P1.a20 + P2.a20, P1.a21 + P2.a21, P1.a22 + P2.a22};
-    const M3 vJ = mul(vT, transpose(W));
-    const float vtx = -fx * rz2 * vJ.a02;
-    const float vty = -fy * rz2 * vJ.a12;
-    const float vtz = -fx * rz2 * vJ.a00 + 2.f * fx * tx * rz3 * vJ.a02 -
-                      fy * rz2 * vJ.a11 + 2.f * fy * ty * rz3 * vJ.a12;
-    gm[0] += vtx * W.a00 + vty * W.a10 + vtz * W.a20;
-    gm[1] += vtx * W.a01 + vty * W.a11 + vtz * W.a21;
-    gm[2] += vtx * W.a02 + vty * W.a12 + vtz * W.a22;
+    project_bwd_chain(i, means3d, viewmat, projmat, fx, fy, img_w, img_h, cov3d, conics, compensation, v_xy, v_depth,
+                      v_conic, v_compensation, c);
 
     // cov3d = M M^T, M = R S  (backward.cu:427-453)
     const M3 vS{g3[0], 0.5f * g3[1], 0.5f * g3[2], 0.5f * g3[1], g3[3],
@@ -312,6 +345,106 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
 #pragma unroll
     for (int k = 0; k < 4; ++k) v_quat[4 * i + k] = gq[k];
   }
+}
+
+// ---- camera gradients ------------------------------------------------------------------
+// v_viewmat [3,4] and v_projmat [4,4] are sums over the visible Gaussians of terms project_bwd_chain already holds:
+//   v_projmat[r,:]  = sum vt_r p~            r = 0, 1, 3 (row 2 is never read by the forward: exactly zero)
+//   v_viewmat[r,:]  = sum v_t[r] p~  (+ v_depth p~ for r = 2)  +  [ (J^T vT)[r,:3], 0 ]
+// The chain's factors are the float32 numbers project_bwd_kernel forms; their products (exact in float64) and the
+// 24 sums are float64: per lane over the GSR_POSE_PER_LANE Gaussians of the lane, then wave (xor butterfly) ->
+// workgroup (the four waves in order, through LDS) -> grid (project_pose_final_kernel over the per-workgroup
+// partials), every step in a fixed order and no atomics, rounded to float32 once.
+#define GSR_POSE_SUMS 24
+#define GSR_POSE_PER_LANE 4
+#define GSR_POSE_SHARE (256 * GSR_POSE_PER_LANE)  // Gaussians per workgroup
+
+__device__ __forceinline__ double pose_wave_sum(double v) {
+#pragma unroll
+  for (int m = 1; m < GSR_WAVE; m <<= 1) v += __shfl_xor(v, m, GSR_WAVE);
+  return v;  // (the same bits in every lane: a + b and b + a round alike)
+}
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void project_pose_partial_kernel(
+    const int n, const float *__restrict__ means3d, const float *__restrict__ viewmat,
+    const float *__restrict__ projmat, const float fx, const float fy, const int img_w, const int img_h,
+    const float *__restrict__ cov3d, const int *__restrict__ radii, const float *__restrict__ conics,
+    const float *__restrict__ compensation, const float *__restrict__ v_xy, const float *__restrict__ v_depth,
+    const float *__restrict__ v_conic, const float *__restrict__ v_compensation, double *__restrict__ partials) {
+  __shared__ double wave_sums[4][GSR_POSE_SUMS];
+  double acc[GSR_POSE_SUMS];  // [0,12): v_viewmat row-major; [12,24): rows 0, 1, 3 of v_projmat
+#pragma unroll
+  for (int k = 0; k < GSR_POSE_SUMS; ++k) acc[k] = 0.0;
+
+  const long long base = (long long)blockIdx.x * GSR_POSE_SHARE + threadIdx.x;
+#pragma unroll 1
+  for (int j = 0; j < GSR_POSE_PER_LANE; ++j) {
+    const long long ii = base + (long long)j * 256;
+    if (ii >= n) break;
+    const int i = (int)ii;
+    if (radii[i] <= 0) continue;
+    BwdChain c;
+    project_bwd_chain(i, means3d, viewmat, projmat, fx, fy, img_w, img_h, cov3d, conics, compensation, v_xy, v_depth,
+                      v_conic, v_compensation, c);
+    const double p[4] = {(double)c.px, (double)c.py, (double)c.pz, 1.0};
+    const double vt[3] = {(double)c.vtx, (double)c.vty, (double)c.vtz + (double)c.vz};
+    const double vp[3] = {(double)c.vt0, (double)c.vt1, (double)c.vt3};
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        acc[4 * r + q] += vt[r] * p[q];
+        acc[12 + 4 * r + q] += vp[r] * p[q];
+      }
+    }
+    // v_W = J^T vT (rows 0 and 1 of J only)
+    const double j00 = c.j00, j02 = c.j02, j11 = c.j11, j12 = c.j12;
+    const double t0[3] = {(double)c.vT.a00, (double)c.vT.a01, (double)c.vT.a02};
+    const double t1[3] = {(double)c.vT.a10, (double)c.vT.a11, (double)c.vT.a12};
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      acc[q] += j00 * t0[q];
+      acc[4 + q] += j11 * t1[q];
+      acc[8 + q] += j02 * t0[q] + j12 * t1[q];
+    }
+  }
+
+  const int wave = threadIdx.x / GSR_WAVE, lane = threadIdx.x % GSR_WAVE;
+#pragma unroll
+  for (int k = 0; k < GSR_POSE_SUMS; ++k) {
+    const double s = pose_wave_sum(acc[k]);
+    if (lane == 0) wave_sums[wave][k] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < GSR_POSE_SUMS) {
+    const int k = threadIdx.x;
+    partials[(size_t)blockIdx.x * GSR_POSE_SUMS + k] =
+        ((wave_sums[0][k] + wave_sums[1][k]) + wave_sums[2][k]) + wave_sums[3][k];
+  }
+}
+
+// One workgroup: wave w owns the sums 6 w .. 6 w + 5; lane l adds the partials l, l + 64, l + 128, ... in that
+// order, the wave's butterfly adds the lanes.
+__global__ __launch_bounds__(256) void project_pose_final_kernel(
+    const int num_partials, const double *__restrict__ partials, float *__restrict__ v_viewmat,
+    float *__restrict__ v_projmat) {
+  const int wave = threadIdx.x / GSR_WAVE, lane = threadIdx.x % GSR_WAVE;
+#pragma unroll 1
+  for (int s = 0; s < GSR_POSE_SUMS / 4; ++s) {
+    const int k = wave * (GSR_POSE_SUMS / 4) + s;
+    double a = 0.0;
+    for (int b = lane; b < num_partials; b += GSR_WAVE) a += partials[(size_t)b * GSR_POSE_SUMS + k];
+    a = pose_wave_sum(a);
+    if (lane == 0) {
+      if (k < 12) {
+        v_viewmat[k] = (float)a;
+      } else {
+        const int r = (k - 12) / 4, q = (k - 12) % 4;
+        v_projmat[4 * (r == 2 ? 3 : r) + q] = (float)a;
+      }
+    }
+  }
+  if (threadIdx.x < 4) v_projmat[8 + threadIdx.x] = 0.f;
 }
 
 __global__ __launch_bounds__(256) void cov2d_bounds_kernel(
@@ -380,6 +513,41 @@ GSR_EXPORT int gsr_project_backward(
                      conics, compensation, v_xy, v_depth, v_conic, v_compensation, v_cov2d,
                      v_cov3d, v_mean3d, v_scale, v_quat);
   GSR_CHECK_LAUNCH("project_backward");
+  return GSR_OK;
+}
+
+GSR_EXPORT size_t gsr_project_backward_pose_workspace(int num_points) {
+  return num_points > 0 ? (size_t)gsr_cdiv((unsigned)num_points, GSR_POSE_SHARE) * GSR_POSE_SUMS * sizeof(double) : 0;
+}
+
+GSR_EXPORT int gsr_project_backward_pose(
+    int num_points, const float *means3d, const float *viewmat, const float *projmat, float fx, float fy,
+    unsigned img_height, unsigned img_width, const float *cov3d, const int32_t *radii, const float *conics,
+    const float *compensation, const float *v_xy, const float *v_depth, const float *v_conic,
+    const float *v_compensation, void *workspace, size_t workspace_bytes, float *v_viewmat, float *v_projmat,
+    gsr_stream_t stream) {
+  GSR_REQUIRE(num_points >= 0, "project_backward_pose: num_points < 0");
+  GSR_REQUIRE(v_viewmat && v_projmat, "project_backward_pose: null pointer");
+  if (num_points == 0) {  // no Gaussian, no term: zeros
+    if (int rc = gsr_zero_async(v_viewmat, 12 * sizeof(float), (hipStream_t)stream)) return rc;
+    return gsr_zero_async(v_projmat, 16 * sizeof(float), (hipStream_t)stream);
+  }
+  GSR_REQUIRE(means3d && viewmat && projmat && cov3d && radii && conics && compensation && workspace,
+              "project_backward_pose: null pointer");
+  GSR_REQUIRE(((uintptr_t)workspace & 7u) == 0, "project_backward_pose: workspace must be 8-byte aligned");
+  if (workspace_bytes < gsr_project_backward_pose_workspace(num_points)) {
+    gsr_set_error("project_backward_pose: workspace of %zu bytes, %zu needed", workspace_bytes,
+                  gsr_project_backward_pose_workspace(num_points));
+    return GSR_ENOMEM;
+  }
+  const unsigned blocks = gsr_cdiv((unsigned)num_points, GSR_POSE_SHARE);
+  hipLaunchKernelGGL(project_pose_partial_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, num_points,
+                     means3d, viewmat, projmat, fx, fy, (int)img_width, (int)img_height, cov3d, radii, conics,
+                     compensation, v_xy, v_depth, v_conic, v_compensation, (double *)workspace);
+  GSR_CHECK_LAUNCH("project_backward_pose");
+  hipLaunchKernelGGL(project_pose_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (int)blocks,
+                     (const double *)workspace, v_viewmat, v_projmat);
+  GSR_CHECK_LAUNCH("project_backward_pose (final)");
   return GSR_OK;
 }
 

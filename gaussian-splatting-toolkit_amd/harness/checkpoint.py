@@ -23,6 +23,10 @@ import torch
 
 PARAM_NAMES = ("means", "scales", "quats", "features_dc", "features_rest", "opacities")
 _PREFIX = "_model.gauss_params."  # pipeline.state_dict() key prefix of the reference
+# the camera optimizer is the model's `camera_optimizer` submodule (models/depth_gs.py:89-92,
+# cameras/camera_optimizers.py:63-65); its Adam is the `camera_opt` group (camera_optimizers.py:145-150)
+_CAMERA_KEY = "_model.camera_optimizer.pose_adjustment"
+_CAMERA_GROUP = "camera_opt"
 
 
 def checkpoint_path(directory: str, step: int) -> str:
@@ -84,18 +88,24 @@ def sharded_state_dicts(sharded) -> Dict[str, dict]:
 
 
 def save_checkpoint(directory: str, step: int, model, optims: Dict[str, torch.optim.Optimizer],
-                    save_only_latest: bool = True, sharded=None, write: bool = True) -> Optional[str]:
+                    save_only_latest: bool = True, sharded=None, write: bool = True, camera=None) -> Optional[str]:
     """trainer.py:444-476.  With `sharded` (a `parallel.ShardedAdam`) EVERY rank calls this -- the moments are
     gathered by a collective -- and only the rank with `write=True` touches the disk (the reference: rank 0,
-    trainer.py:446 `@check_main_thread`)."""
+    trainer.py:446 `@check_main_thread`).  `camera`: (harness.camera_opt.CameraOptimizer, its torch.optim.Adam) --
+    `pose_adjustment` joins the pipeline's state under the key the toolkit's module tree gives it, its optimizer's
+    state dict the `camera_opt` group."""
     opt_state = sharded_state_dicts(sharded) if sharded is not None else optimizer_state_dicts(model, optims)
+    pipeline = {_PREFIX + k: model.gauss[k].detach() for k in PARAM_NAMES}
+    if camera is not None:
+        pipeline[_CAMERA_KEY] = camera[0].pose_adjustment.detach()
+        opt_state[_CAMERA_GROUP] = camera[1].state_dict()
     if not write:
         return None
     os.makedirs(directory, exist_ok=True)
     path = checkpoint_path(directory, step)
     torch.save({
         "step": step,
-        "pipeline": {_PREFIX + k: model.gauss[k].detach() for k in PARAM_NAMES},
+        "pipeline": pipeline,
         "optimizers": opt_state,
         "schedulers": {},
         # exactly what the reference writes for this method: mixed_precision=False -> a DISABLED
@@ -132,8 +142,24 @@ def load_model_state(model, state: Dict[str, torch.Tensor]) -> int:
     return newp
 
 
+def load_camera_state(camera, loaded: dict) -> None:
+    """`pose_adjustment` and its Adam state from a loaded checkpoint; a checkpoint written without a camera optimizer
+    leaves both as they are (zero adjustment, fresh moments)."""
+    opt, adam = camera
+    saved = loaded["pipeline"].get(_CAMERA_KEY)
+    if saved is None:
+        return
+    if saved.shape != opt.pose_adjustment.shape:
+        raise ValueError(f"checkpoint has pose adjustments for {saved.shape[0]} views, the run {opt.pose_adjustment.shape[0]}")
+    with torch.no_grad():
+        opt.pose_adjustment.copy_(saved)
+    sd = loaded.get("optimizers", {}).get(_CAMERA_GROUP)
+    if sd:
+        adam.load_state_dict(sd)
+
+
 def load_checkpoint(path: str, model, optims: Dict[str, torch.optim.Optimizer], trust_pickle: bool = False,
-                    sharded=None) -> int:
+                    sharded=None, camera=None) -> int:
     """trainer.py:404-443 for one file or a directory (latest step).  The model is resized,
     every optimizer is pointed at the new parameter objects and gets the saved Adam state
     (``step``, ``exp_avg``, ``exp_avg_sq``) and learning rate.  Returns the step to resume
@@ -146,6 +172,8 @@ def load_checkpoint(path: str, model, optims: Dict[str, torch.optim.Optimizer], 
     loaded = torch.load(path, map_location="cpu", weights_only=not trust_pickle)
     old = {k: model.gauss[k] for k in PARAM_NAMES}
     load_model_state(model, loaded["pipeline"])
+    if camera is not None:
+        load_camera_state(camera, loaded)
     if sharded is not None:
         moments, steps = {}, []
         for name in PARAM_NAMES:

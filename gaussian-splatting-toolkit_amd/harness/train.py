@@ -493,6 +493,23 @@ class TrainConfig:
     # takes the mask's one channel).  With the fused heads the multiplies happen inside the loss kernels
     # (gs_fused.*_loss(mask=...)); otherwise they are the reference's torch ops.
     mask: str = "none"
+    # camera pose refinement (harness/camera_opt.py; gs_toolkit/cameras/camera_optimizers.py): "off", "SO3xR3" or "SE3".
+    # A seventh parameter group -- `pose_adjustment` [num_views,6] under a plain torch.optim.Adam (eps 1e-15, the
+    # `camera_opt` group of configs/method_configs.py:75-80: lr 1e-3 decaying exponentially to 5e-5 over 30 000 steps),
+    # outside FusedAdam and refinement (it has no per-Gaussian rows) -- fed by the projection's camera gradients
+    # (rasterizer.cuda.project_gaussians_backward_pose).  Runs the separate-ops path on one GPU: `fused_render`,
+    # `use_graph`, a world size above 1 and CPU tensors are refused.  "off": nothing in the step changes.
+    camera_optimizer: str = "off"
+    camera_trans_l2_penalty: float = 1e-2
+    camera_rot_l2_penalty: float = 1e-3
+    camera_lr: float = 1e-3
+    camera_lr_final: float = 5e-5
+    camera_lr_max_steps: int = 30000
+    # (translation sigma in scene units, rotation sigma in radians): the training cameras the trainer is given are
+    # moved once by a rigid error drawn from `pose_noise_seed` (camera_opt.perturb_cameras), standing in for COLMAP's;
+    # the ground truth stays rendered from the true poses, so a synthetic run has something to recover
+    pose_noise: tuple = (0.0, 0.0)
+    pose_noise_seed: int = 20241019
 
 
 def quantise_depth_mm(depth: torch.Tensor) -> torch.Tensor:
@@ -544,6 +561,25 @@ def _check_config(cfg: TrainConfig) -> None:
         raise ValueError("co-gs runs through the separate ops (fused_depth = one RGB + depth compositing pass)")
     if cfg.mask not in ("none", "alpha", "box"):
         raise ValueError(f"unknown mask {cfg.mask!r}")
+    if cfg.camera_optimizer not in ("off", "SO3xR3", "SE3"):
+        raise ValueError(f"unknown camera_optimizer {cfg.camera_optimizer!r}")
+    if cfg.camera_optimizer != "off":
+        if cfg.fused_render:
+            raise ValueError("camera_optimizer needs the separate-ops path: the one-node view (fused_render, "
+                             "gsr_view_backward) returns no camera gradient")
+        if cfg.use_graph:
+            raise ValueError("camera_optimizer needs the separate-ops path: a replayed HIP graph (use_graph) holds the "
+                             "camera's matrices as constants of the capture")
+
+
+def _check_camera_optimizer(cfg: TrainConfig, device, world: int) -> None:
+    """What else `camera_optimizer` refuses, once the device and the world size are known."""
+    if cfg.camera_optimizer == "off":
+        return
+    if world > 1:
+        raise ValueError("camera_optimizer runs on one GPU: the pose gradients of a data-parallel run are not exchanged")
+    if device.type != "cuda":
+        raise ValueError("camera_optimizer needs CUDA tensors: the camera gradients come from the HIP projection")
 
 
 def _params(model: GaussianParams) -> Dict[str, torch.nn.Parameter]:
@@ -571,11 +607,18 @@ class TrainData:
     gt_rgba: Optional[List[torch.Tensor]]     # random background: [H,W,4] per view, straight colour
     gt_depth: Optional[List[torch.Tensor]]    # co-gs: [H,W] per view, millimetre steps, 0 = no measurement
     masks: Optional[List[torch.Tensor]]       # TrainConfig.mask: [H,W,1] per view
+    cams_np: Optional[list] = None            # the training cameras as given (scene.Camera; `pose_noise` applied)
+    true_cams_np: Optional[list] = None       # the cameras the ground truth was rendered from
 
 
 def make_data(cfg: TrainConfig, device) -> TrainData:
-    cams_np = orbit_cameras(cfg.num_views, cfg.width, cfg.height, radius=cfg.cam_radius)
-    cams = [CameraTensors.from_numpy(c, device) for c in cams_np]
+    true_np = cams_np = orbit_cameras(cfg.num_views, cfg.width, cfg.height, radius=cfg.cam_radius)
+    true_cams = cams = [CameraTensors.from_numpy(c, device) for c in cams_np]
+    if tuple(cfg.pose_noise) != (0.0, 0.0):  # the trainer's cameras carry a pose error; the images do not
+        from .camera_opt import perturb_cameras
+
+        cams_np = perturb_cameras(true_np, cfg.pose_noise[0], cfg.pose_noise[1], cfg.pose_noise_seed)
+        cams = [CameraTensors.from_numpy(c, device) for c in cams_np]
     # the coarse-to-fine schedule's cameras, one set per downscale factor
     factors = sorted({downscale_factor(s_, cfg.num_downscales, cfg.resolution_schedule)
                       for s_ in range(0, max(cfg.iters, 1), max(min(cfg.resolution_schedule, cfg.iters), 1))} | {1})
@@ -589,7 +632,7 @@ def make_data(cfg: TrainConfig, device) -> TrainData:
             # rendered over black, C = sum c_i a_i T_i and A = 1 - T, colour = C / A
             zero = torch.zeros(3, device=device)
             gt_rgba, gt = [], []
-            for c in cams:
+            for c in true_cams:
                 o = truth.render(c, zero, cfg.sh_degree, clamp_rgb=False)
                 a = o["alpha"]
                 gt_rgba.append(torch.cat((torch.where(a > 0, o["rgb"] / a.clamp_min(1e-12), torch.zeros_like(o["rgb"]))
@@ -597,13 +640,13 @@ def make_data(cfg: TrainConfig, device) -> TrainData:
                 gt.append(composite_with_background(gt_rgba[-1], bg))  # evaluation: over the fixed background
         else:
             gt_rgba = None
-            gt = [truth.render(c, bg, cfg.sh_degree)["rgb"] for c in cams]
+            gt = [truth.render(c, bg, cfg.sh_degree)["rgb"] for c in true_cams]
         gt_depth = None
         if cfg.model == "co-gs":
             # the sensor's depth image: z-depth of the hidden scene where it covers the pixel, 0 (= no measurement,
             # masked out by `gt_depth > 0`) elsewhere, in millimetre steps like the dataset's 16-bit PNGs
             gt_depth = []
-            for c in cams:
+            for c in true_cams:
                 o = truth.render(c, torch.zeros(3, device=device), cfg.sh_degree, render_depth=True,
                                  fused_depth=device.type == "cuda")
                 gt_depth.append(quantise_depth_mm(torch.where(o["alpha"] > 0.5, o["depth"], torch.zeros_like(o["depth"]))
@@ -612,15 +655,16 @@ def make_data(cfg: TrainConfig, device) -> TrainData:
         if cfg.mask != "none":
             masks = view_masks(cfg.mask, cfg.height, cfg.width,
                                [truth.render(c, bg, cfg.sh_degree)["alpha"] if cfg.mask == "alpha" else None
-                                for c in cams], device)
-    return TrainData(factors, cams_by_d, bg, gt, gt_rgba, gt_depth, masks)
+                                for c in true_cams], device)
+    return TrainData(factors, cams_by_d, bg, gt, gt_rgba, gt_depth, masks, cams_np, true_np)
 
 
-def evaluate(model: GaussianParams, data: TrainData, cfg: TrainConfig) -> Dict[str, Optional[float]]:
+def evaluate(model: GaussianParams, data: TrainData, cfg: TrainConfig, cams=None) -> Dict[str, Optional[float]]:
     """Means over `eval_views` full-size views: "psnr"; "psnr_masked" over the pixels with mask > 0.5 (with a mask);
-    "depth_err", mean |rendered depth - gt depth| over the measured pixels (co-gs)."""
+    "depth_err", mean |rendered depth - gt depth| over the measured pixels (co-gs).  `cams`: the full-size cameras to
+    render from (default: the ones the trainer was given; with a camera optimizer, the corrected ones)."""
     cogs, masked = cfg.model == "co-gs", data.masks is not None
-    cams, bg, gt = data.cams_by_d[1], data.bg, data.gt
+    cams, bg, gt = data.cams_by_d[1] if cams is None else cams, data.bg, data.gt
     ps, pm, de = [], [], []
     with torch.no_grad():
         for i in np.linspace(0, cfg.num_views - 1, cfg.eval_views).astype(int):
@@ -973,6 +1017,7 @@ class SeparateStep:
         self.phase_every = cfg.phase_every if cuda else 0
         self.ph, self.depth_on = None, False
         self.marks = []  # (downscale factor, 5 events, depth loss on) per sampled step
+        self.camera_opt = None  # a camera_opt.CameraOptimizer: its regulariser joins the loss (get_loss_dict)
 
     def __call__(self, step, v, d, cam, deg, bg, target, mask):
         _zero_grads(self.model)
@@ -988,6 +1033,8 @@ class SeparateStep:
             for term in _cogs_terms(self.cfg, step, self.model, out, target, mask, self.gt_depth[v], d,
                                     self.depth_head, self.depth_on):
                 loss = loss + term
+        if self.camera_opt is not None:
+            loss = loss + self.camera_opt.regulariser()
         if ph:
             ph[2].record()
         loss.backward()
@@ -998,6 +1045,58 @@ class SeparateStep:
     def end_phases(self, d: int) -> None:
         self.ph[4].record()
         self.marks.append((d, self.ph, self.depth_on))
+
+
+class CameraGroup:
+    """The seventh parameter group: `camera_opt.CameraOptimizer` over the training views, its Adam with the
+    `camera_opt` schedule, and the cameras it corrects."""
+
+    def __init__(self, cfg: TrainConfig, data: TrainData, device):
+        from .camera_opt import CameraOptimizer, PosedCameras
+
+        self.cfg = cfg
+        self.opt = CameraOptimizer(cfg.camera_optimizer, cfg.num_views, device, cfg.camera_trans_l2_penalty,
+                                   cfg.camera_rot_l2_penalty)
+        self.posed = PosedCameras(data.cams_np, device, true_cams_np=data.true_cams_np)
+        self.adam = torch.optim.Adam([self.opt.pose_adjustment], lr=cfg.camera_lr, eps=1e-15)
+
+    def step_camera(self, step: int, v: int, like: CameraTensors) -> CameraTensors:
+        """Zero the group's gradient, set this step's learning rate, and return view `v` corrected."""
+        self.adam.zero_grad(set_to_none=True)
+        self.adam.param_groups[0]["lr"] = means_lr(step, self.cfg.camera_lr, self.cfg.camera_lr_final,
+                                                   self.cfg.camera_lr_max_steps)
+        return self.posed.camera(self.opt, v, like)
+
+    def eval_cameras(self, data: TrainData):
+        with torch.no_grad():
+            return [self.posed.camera(self.opt, v, c) for v, c in enumerate(data.cams_by_d[1])]
+
+
+def make_camera_optimiser(cfg: TrainConfig, data: TrainData, device) -> Optional[CameraGroup]:
+    return None if cfg.camera_optimizer == "off" else CameraGroup(cfg, data, device)
+
+
+def pose_errors(cfg: TrainConfig, data: TrainData, camera: Optional[CameraGroup], device):
+    """-> (degrees, scene units): means over the training views of the angle and the distance between the (corrected)
+    camera and the true one; None where the run has neither a camera optimizer nor pose noise."""
+    if camera is not None:
+        return camera.posed.pose_errors(camera.opt)
+    if tuple(cfg.pose_noise) == (0.0, 0.0):
+        return None
+    from .camera_opt import PosedCameras
+
+    return PosedCameras(data.cams_np, device, true_cams_np=data.true_cams_np).pose_errors(None)
+
+
+def pose_record(camera: Optional[CameraGroup], start, end) -> Dict:
+    if start is None:
+        return {}
+    rec = {"pose_err_rot_deg_start": start[0], "pose_err_rot_deg_end": end[0],
+           "pose_err_trans_start": start[1], "pose_err_trans_end": end[1]}
+    if camera is not None:
+        rec.update({k: float(v.detach()) for k, v in camera.opt.metrics().items()})
+        rec["pose_adjustment"] = camera.opt.pose_adjustment.detach().cpu().tolist()
+    return rec
 
 
 def refine_model(cfg: TrainConfig, rcfg, step: int, model, optims, sharded, exchange, stats: DensifyState,
@@ -1086,7 +1185,8 @@ def result_record(cfg: TrainConfig, device, world: int, model, run: Dict, eval0:
                        "one_compositing_pass": bool(cfg.fused_depth and device.type == "cuda"),
                        "mean_abs_error_start_end": [eval0["depth_err"], eval1["depth_err"]]} if cogs else None),
             "peak_memory_bytes": (int(torch.cuda.max_memory_allocated(device)) if device.type == "cuda" else None),
-            "densify_grad_thresh": (run["rcfg"].densify_grad_thresh if cfg.densify else None)}
+            "densify_grad_thresh": (run["rcfg"].densify_grad_thresh if cfg.densify else None),
+            **run.get("pose", {})}
 
 
 def _note_bytes(log: list, step: int, nbytes: int) -> None:
@@ -1098,6 +1198,7 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
     """Fit a perturbed copy of a hidden scene to its own renders.  Returns timing
     and quality numbers; every rank ends with identical parameters."""
     _check_config(cfg)
+    _check_camera_optimizer(cfg, device, world)
     cuda = device.type == "cuda"
     dp = world > 1 or (cfg.force_exchange and dist.is_available() and dist.is_initialized())
     data = make_data(cfg, device)
@@ -1111,10 +1212,12 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
         rcfg = RefineConfig()
     n0 = model.num_points
     start_step = 0
+    camera = make_camera_optimiser(cfg, data, device)
     if cfg.resume_from:
         from .checkpoint import load_checkpoint
 
-        start_step = load_checkpoint(cfg.resume_from, model, optims, sharded=sharded)  # resizes the model to the saved N
+        start_step = load_checkpoint(cfg.resume_from, model, optims, sharded=sharded,  # resizes the model to the saved N
+                                     camera=None if camera is None else (camera.opt, camera.adam))
     use_fused = (cfg.fused_render or cfg.use_graph) and cuda and cfg.split_sh and cfg.fused_loss \
         and cfg.sh_degree in (0, 1, 2, 3)
     kernel = None
@@ -1123,7 +1226,8 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
     stats = DensifyState(model.num_points, device, max(cfg.width, cfg.height),
                          densify_until=rcfg.stop_split_at if cfg.densify else None, rank=rank, world=world,
                          kernel=kernel, native=use_fused)
-    eval0 = evaluate(model, data, cfg)
+    eval0 = evaluate(model, data, cfg, None if camera is None else camera.eval_cameras(data))
+    pose0 = pose_errors(cfg, data, camera, device)
     exchange, sh_views = make_exchange(cfg, model, sharded is not None, dp)
     inputs = StepInputs(cfg, data, device, rank)
     means_group = None  # the scheduled learning rate's param group (after load_checkpoint, which replaces the groups)
@@ -1148,6 +1252,7 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
             run_step = FusedStep(cfg, model, data, stats, heads[0], exchange, sh_views, dp, history)
         else:
             run_step = SeparateStep(cfg, model, data, heads, exchange, sh_views, device)
+            run_step.camera_opt = None if camera is None else camera.opt
         rebuilds0 = _list_rebuilds()
         for step in range(start_step, cfg.iters):
             v = view_for_rank(step, rank, world, cfg.num_views)
@@ -1158,6 +1263,8 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
             cam = cams_by_d[d][v]
             max_dim = max(cam.width, cam.height)  # `max(self.last_size)` of after_train / refinement_after
             bg_step, target, m_step = inputs(v, d)
+            if camera is not None:  # this step's camera, a function of the view's six numbers
+                cam = camera.step_camera(step, v, cam)
             loss, out = run_step(step, v, d, cam, deg, bg_step, target, m_step)
             stats.update(out, max_dim, step)
             if dp and sharded is None:
@@ -1170,6 +1277,8 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
                     means_group["lr"] = means_lr(step, LRS["means"])
             for o in optims.values():
                 o.step()
+            if camera is not None:
+                camera.adam.step()
             if sharded is not None:
                 _note_bytes(exchanged_bytes, step, sharded.step())
             if run_step.ph:
@@ -1183,7 +1292,8 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
                 from .checkpoint import save_checkpoint
 
                 # (sharded moments are gathered by a collective: every rank calls, rank 0 writes)
-                save_checkpoint(cfg.checkpoint_dir, step, model, optims, sharded=sharded, write=rank == 0)
+                save_checkpoint(cfg.checkpoint_dir, step, model, optims, sharded=sharded, write=rank == 0,
+                                camera=None if camera is None else (camera.opt, camera.adam))
             if cfg.log_every and step % cfg.log_every == 0:
                 losses.append(float(loss.detach()))
         if dp:
@@ -1193,7 +1303,8 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
         elapsed = time.perf_counter() - t0
     finally:
         gc.unfreeze()
-    eval1 = evaluate(model, data, cfg)
+    eval1 = evaluate(model, data, cfg, None if camera is None else camera.eval_cameras(data))
+    pose1 = pose_errors(cfg, data, camera, device)
     if cfg.export_ply and rank == 0:
         from gs_io.ply import write_gaussian_ply
 
@@ -1202,6 +1313,7 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
            "exchanged_bytes": exchanged_bytes, "rcfg": rcfg,
            "render": ("hip graph per view" if cfg.use_graph else "one fused op") if use_fused else "separate ops",
            "overflow_views": run_step.overflow_views + (_list_rebuilds() - rebuilds0),
+           "pose": pose_record(camera, pose0, pose1),
            "update": "reduce-scatter + sharded Adam + all-gather" if sharded is not None else
            ("all-reduce (geometry) + all-gathered colour cotangents (SH) + Adam" if sh_views else "all-reduce + Adam")}
     return result_record(cfg, device, world, model, run, eval0, eval1, phase_record(run_step.marks, cfg, data.factors))

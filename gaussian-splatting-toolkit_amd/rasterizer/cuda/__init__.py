@@ -170,6 +170,55 @@ def project_gaussians_backward(
     return v_cov2d, v_cov3d, v_mean3d, v_scale, v_quat
 
 
+def project_gaussians_backward_pose(
+    num_points: int, means3d: Tensor, viewmat: Tensor, projmat: Tensor, fx: float, fy: float,
+    img_height: int, img_width: int, cov3d: Tensor, radii: Tensor, conics: Tensor, compensation: Tensor,
+    v_xy: Optional[Tensor], v_depth: Optional[Tensor], v_conic: Optional[Tensor], v_compensation: Optional[Tensor],
+    trusted: bool = False,
+) -> Tuple[Tensor, Tensor]:
+    """-> (v_viewmat [3,4], v_projmat [4,4]): the camera's gradient through the projection, which the reference does
+    not have (its backward returns None for both matrices, project_gaussians.py:156-232).  The sums over the visible
+    Gaussians of the terms ``project_gaussians_backward`` forms per Gaussian, under its conventions: no fov clamp (so
+    outside the 1.3x guard band this is not the forward's derivative, as for ``v_mean3d``), the compensation's
+    cotangent scaled by ``0.5 / (compensation + 1e-6)``, a cotangent that is None is zero.  Row 2 of ``v_projmat`` is
+    exactly zero.  The colour's view dependence contributes nothing: the SH op has no gradient with respect to
+    ``viewdirs``, in the reference or here.  Reads ``cov3d``, never scales or quats.  Float64 sums in a fixed order:
+    two calls give the same bits.  ``trusted`` as in ``project_gaussians_backward``."""
+    n = int(num_points)
+    dev = means3d.device
+    if not trusted:
+        for t, nm in ((means3d, "means3d"), (viewmat, "viewmat"), (projmat, "projmat"), (cov3d, "cov3d"),
+                      (conics, "conics"), (compensation, "compensation")):
+            _check(t, nm, _f32)
+        _check(radii, "radii", _i32)
+        if viewmat.numel() < 12 or projmat.numel() != 16:
+            raise RuntimeError("viewmat must hold at least 3x4 and projmat 4x4 values")
+        if means3d.numel() != 3 * n or cov3d.numel() != 6 * n or radii.numel() != n or conics.numel() != 3 * n \
+                or compensation.numel() != n:
+            raise RuntimeError("means3d/cov3d/radii/conics/compensation do not match num_points")
+    cots = []
+    for t, nm, width in ((v_xy, "v_xy", 2), (v_depth, "v_depth", 1), (v_conic, "v_conic", 3),
+                         (v_compensation, "v_compensation", 1)):
+        if t is not None:
+            t = _check(t.contiguous(), nm, _f32)
+            if t.numel() != width * n:
+                raise RuntimeError(f"{nm} does not match num_points")
+        cots.append(t)
+    _opt = lambda t: None if t is None else _ptr(t)
+    with _on(dev):
+        nbytes = int(_lib().gsr_project_backward_pose_workspace(C.c_int(n)))
+        workspace = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=dev)
+        v_viewmat = torch.empty((3, 4), dtype=_f32, device=dev)
+        v_projmat = torch.empty((4, 4), dtype=_f32, device=dev)
+        _call(
+            "gsr_project_backward_pose", C.c_int(n), _ptr(means3d), _ptr(viewmat), _ptr(projmat), _cf(fx), _cf(fy),
+            C.c_uint(img_height), C.c_uint(img_width), _ptr(cov3d), _ptr(radii), _ptr(conics), _ptr(compensation),
+            *(_opt(t) for t in cots), _ptr(workspace), C.c_size_t(nbytes), _ptr(v_viewmat), _ptr(v_projmat),
+            _stream(dev),
+        )
+    return v_viewmat, v_projmat
+
+
 def _num_sh_bases(degree: int) -> int:
     return {0: 1, 1: 4, 2: 9, 3: 16}.get(int(degree), 25)
 

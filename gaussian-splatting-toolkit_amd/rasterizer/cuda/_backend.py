@@ -21,6 +21,8 @@ SYMBOLS = (
     "gsr_last_error",
     "gsr_project_forward",
     "gsr_project_backward",
+    "gsr_project_backward_pose_workspace",
+    "gsr_project_backward_pose",
     "gsr_sh_forward",
     "gsr_sh_backward",
     "gsr_cumsum_workspace_bytes",
@@ -148,6 +150,7 @@ def _load():
     lib.gsr_version.restype = C.c_int
     lib.gsr_calibrate_valu.restype = C.c_longlong
     lib.gsr_tile_jobs_ints.restype = C.c_size_t
+    lib.gsr_project_backward_pose_workspace.restype = C.c_size_t
     lib.gsr_cumsum_workspace_bytes.restype = C.c_size_t
     lib.gsr_sort_workspace_bytes.restype = C.c_size_t
     lib.gsr_reach_record_bytes.restype = C.c_size_t

@@ -56,14 +56,28 @@ class _ProjectGaussians(Function):
             n, means3d, scales, glob_scale, quats, viewmat, projmat, fx, fy, cx, cy, img_height, img_width,
             cov3d, radii, conics, compensation, g_xys, g_depths, g_conics, g_compensation, trusted=True)
         g_means, g_scales, g_quats = grads[2:]  # (v_cov2d, v_cov3d) come first and stay internal
-        # slots: means3d, scales, glob_scale, quats, then the ten camera / image arguments
-        return (g_means, g_scales, None, g_quats) + (None,) * 10
+        g_viewmat = g_projmat = None
+        if ctx.needs_input_grad[4] or ctx.needs_input_grad[5]:
+            # the camera is being optimised: a pass of its own (two more launches), nothing above changes
+            v_viewmat, g_projmat = _C.project_gaussians_backward_pose(
+                n, means3d, viewmat, projmat, fx, fy, img_height, img_width, cov3d, radii, conics, compensation,
+                g_xys, g_depths, g_conics, g_compensation, trusted=True)
+            if ctx.needs_input_grad[4]:  # in the shape that was passed: [3,4], or [4,4] with a zero last row
+                g_viewmat = viewmat.new_zeros(viewmat.shape)
+                g_viewmat.view(-1)[:12] = v_viewmat.view(-1)
+            if not ctx.needs_input_grad[5]:
+                g_projmat = None
+        # slots: means3d, scales, glob_scale, quats, viewmat, projmat, then the eight scalar arguments
+        return (g_means, g_scales, None, g_quats, g_viewmat, g_projmat) + (None,) * 8
 
 
 def project_gaussians(means3d: Tensor, scales: Tensor, glob_scale: float, quats: Tensor, viewmat: Tensor,
                       projmat: Tensor, fx: float, fy: float, cx: float, cy: float, img_height: int,
                       img_width: int, block_width: int, clip_thresh: float = 0.01) -> _Out:
-    """Project N Gaussians; differentiable w.r.t. ``means3d``, ``scales`` and ``quats``.
+    """Project N Gaussians; differentiable w.r.t. ``means3d``, ``scales`` and ``quats``, and -- beyond the
+    reference, whose backward returns None for them -- w.r.t. ``viewmat`` and ``projmat`` where they require a
+    gradient (``rasterizer.cuda.project_gaussians_backward_pose``: the derivative of the projection alone; the SH
+    op has no gradient with respect to the view directions, so the colour's view dependence moves no camera).
 
     means3d [N,3]; scales [N,3] (already exponentiated) times ``glob_scale``; quats
     [N,4] as (w,x,y,z); viewmat world->camera (row-major, top 3x4 used); projmat the

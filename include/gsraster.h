@@ -84,6 +84,26 @@ int gsr_project_backward(int num_points, const float *means3d,
                          float *v_cov2d, float *v_cov3d, float *v_mean3d,
                          float *v_scale, float *v_quat, gsr_stream_t stream);
 
+/* Camera gradients of the projection (the reference has none: project_gaussians.py:156-232 returns None for both
+ * matrices): v_viewmat[12] (top 3x4) and v_projmat[16], the sums over the Gaussians with radii > 0 of the terms
+ * gsr_project_backward forms per Gaussian, under its conventions (no fov clamp; the compensation's cotangent scaled by
+ * 0.5 / (compensation + 1e-6); a NULL cotangent = all zeros).  Row 2 of v_projmat is exactly zero (the forward never
+ * reads that row).  Reads cov3d, never scales or quats: precomputed covariances need nothing else.  A pass of its
+ * own -- two launches, gsr_project_backward is not involved; float64 sums in a fixed order through `workspace`
+ * (8-byte aligned, gsr_project_backward_pose_workspace(num_points) bytes; GSR_ENOMEM when shorter), no atomics:
+ * the same inputs give the same bits.  num_points == 0 writes zeros to both outputs. */
+size_t gsr_project_backward_pose_workspace(int num_points);
+int gsr_project_backward_pose(int num_points, const float *means3d,
+                              const float *viewmat, const float *projmat,
+                              float fx, float fy, unsigned img_height,
+                              unsigned img_width, const float *cov3d,
+                              const int32_t *radii, const float *conics,
+                              const float *compensation, const float *v_xy,
+                              const float *v_depth, const float *v_conic,
+                              const float *v_compensation, void *workspace,
+                              size_t workspace_bytes, float *v_viewmat,
+                              float *v_projmat, gsr_stream_t stream);
+
 /* ---- spherical harmonics ----------------------------------------------
  * replaces compute_sh_forward_tensor / compute_sh_backward_tensor
  * (bindings.cu:58-103), kernels sh.cuh:188-224.  degree in 0..4 fixes the
