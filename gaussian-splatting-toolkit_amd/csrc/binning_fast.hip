@@ -53,6 +53,9 @@ int gsr_tile_scatter(int I, const int *cum, int n, const unsigned *keys, const i
 // tile_partition2.hip
 bool gsr_tile_partition2_supported(int tiles_x, int tiles_y);
 size_t gsr_tile_partition2_workspace_bytes(int n, int capacity, int tiles_x, int tiles_y);
+int gsr_tile_partition2_jobs(int n, int capacity, const int *order, const void *recs, int tiles_x, int tiles_y,
+                             int *ids_sorted, int *tile_bins, int *count_out, void *workspace, size_t workspace_bytes,
+                             int deep_first, int deep_second, int *jobs_built, hipStream_t s);
 int gsr_tile_partition2(int n, int capacity, const int *order, const void *recs, int tiles_x, int tiles_y,
                         int *ids_sorted, int *tile_bins, int *count_out, void *workspace, size_t workspace_bytes,
                         hipStream_t s);
@@ -520,7 +523,9 @@ int bin_sorted_impl(bool device_sized, int num_points, int num_intersects, const
                     const int32_t *cum_sorted, const float *xys, const int32_t *radii,
                     const void *reach_records, int tiles_x, int tiles_y, unsigned block_width, int num_bands,
                     int32_t *gaussian_ids_sorted, int32_t *tile_bins, int32_t *count_out, int32_t *slot_of_entry,
-                    void *workspace, size_t workspace_bytes, gsr_stream_t stream) {
+                    void *workspace, size_t workspace_bytes, gsr_stream_t stream, int deep_first = 0,
+                    int deep_second = 0, int *jobs_built = nullptr) {
+  if (jobs_built) *jobs_built = 0;
   GSR_REQUIRE(num_points >= 0 && num_intersects >= 0, "bin_sorted: negative size");
   GSR_REQUIRE(block_width >= 2 && block_width <= 16, "bin_sorted: block_width must be in [2,16]");
   GSR_REQUIRE(tiles_x > 0 && tiles_y > 0, "bin_sorted: empty tile grid");
@@ -561,8 +566,9 @@ int bin_sorted_impl(bool device_sized, int num_points, int num_intersects, const
     return GSR_ENOMEM;
   }
   if (mode == 't')  // large grid, one count per Gaussian: row-partitioned emission + per-row column partition
-    return gsr_tile_partition2(num_points, num_intersects, order, reach_records, tiles_x, tiles_y,
-                               gaussian_ids_sorted, tile_bins, count_out, workspace, workspace_bytes, s);
+    return gsr_tile_partition2_jobs(num_points, num_intersects, order, reach_records, tiles_x, tiles_y,
+                                    gaussian_ids_sorted, tile_bins, count_out, workspace, workspace_bytes, deep_first,
+                                    deep_second, jobs_built, s);
   char *ws = static_cast<char *>(workspace);
   const size_t ib = align_up(4 * (size_t)num_intersects);
   unsigned *tile_in = reinterpret_cast<unsigned *>(ws);
@@ -617,6 +623,30 @@ GSR_EXPORT int gsr_bin_sorted_dev(int num_points, int capacity, const int32_t *o
   return bin_sorted_impl(true, num_points, capacity, order, cum_sorted, xys, radii, reach_records, tiles_x,
                          tiles_y, block_width, num_bands, gaussian_ids_sorted, tile_bins, count_out, slot_of_entry,
                          workspace, workspace_bytes, stream);
+}
+
+// gsr_bin_sorted_dev that also leaves the compositing launches' job orders behind tile_bins where the list build can
+// carry them in its last launch (the two-level partition; include/gsraster.h): deep_first / deep_second as
+// gsr_tile_jobs_build takes them, *jobs_built (host) = 1 if they were written, 0 if the caller still has to.
+GSR_EXPORT int gsr_bin_sorted_dev_jobs(int num_points, int capacity, const int32_t *order, const int32_t *cum_sorted,
+                                       const float *xys, const int32_t *radii, const void *reach_records, int tiles_x,
+                                       int tiles_y, unsigned block_width, int num_bands, int32_t *gaussian_ids_sorted,
+                                       int32_t *tile_bins, int32_t *count_out, int32_t *slot_of_entry, void *workspace,
+                                       size_t workspace_bytes, int deep_first, int deep_second, int *jobs_built,
+                                       gsr_stream_t stream) {
+  if (jobs_built) *jobs_built = 0;
+  GSR_REQUIRE(capacity > 0 && num_points > 0, "bin_sorted_dev_jobs: capacity and num_points must be positive");
+  GSR_REQUIRE(jobs_built, "bin_sorted_dev_jobs: jobs_built is required");
+  if (deep_first > 0 && gsr_deep_ordered(deep_first)) {
+    GSR_REQUIRE(deep_second <= 0 || gsr_deep_ordered(deep_second), "bin_sorted_dev_jobs: second order without GSR_DEEP_ORDERED");
+    GSR_REQUIRE(deep_second <= 0 || gsr_deep_second(deep_first) != gsr_deep_second(deep_second),
+                "bin_sorted_dev_jobs: both orders name the same array");
+  } else {
+    deep_first = deep_second = 0;  // (no order asked for: the plain list build)
+  }
+  return bin_sorted_impl(true, num_points, capacity, order, cum_sorted, xys, radii, reach_records, tiles_x, tiles_y,
+                         block_width, num_bands, gaussian_ids_sorted, tile_bins, count_out, slot_of_entry, workspace,
+                         workspace_bytes, stream, deep_first, deep_second, jobs_built);
 }
 
 // ---- two-round lists ---------------------------------------------------

@@ -173,7 +173,7 @@ __device__ __forceinline__ TileJob tile_job(const unsigned b, const unsigned bas
 // (s_setprio tiers by estimated work were built and measured -- no gain: tools/exp/wave_prio.patch,
 //  profiles/r05_wave_priority_ab.txt)
 
-// The job order of one launch: one workgroup of 1024 lanes per XCD.  Items: every tile the static map gives this XCD
+// The job order of one launch: one workgroup per XCD (1024 lanes in a launch of its own, 256 inside the list build).  Items: every tile the static map gives this XCD
 // -- one job (tile, 15) keyed by its list length, or, above the threshold, four jobs (tile, 1 << p) keyed by
 // length x the measured cost ratio of a sub-tile wave (JobStats above).  Counting sort, descending, on HALF-OCTAVE buckets of the
 // key (bucket = floor(2 log2 key)): jobs inside a bucket differ by < 1.42 x in length and keep -- up to the order in
@@ -198,14 +198,27 @@ __device__ __forceinline__ int job_bucket(const int key) {  // larger keys -> sm
 // The sort is STABLE and deterministic: inside a bucket the jobs keep the static map's order (ranks by wave-wide key
 // matching, a per-(wave chunk, bucket) table, one prefix down the chunks) -- spatial neighbours stay neighbours in time.
 constexpr int kJobChunks = 64;  // wave chunks of 64 slots per XCD: up to 4 096 tile slots per XCD (32 768 in all: 3840 x 2160 is 32 400 tiles)
-static __global__ __launch_bounds__(1024) void tile_jobs_kernel(const int tiles_x, const int tiles_y,
-                                                                const unsigned base_grid,
-                                                                const int2 *__restrict__ tile_bins,
-                                                                const int deep_arg0, const int deep_arg1,
-                                                                int *__restrict__ jobs_base, float *stats,
-                                                                const float fixed_ratio) {
-  // workgroups 0-7: the order deep_arg0 describes (threshold, tail, which array); 8-15: deep_arg1's, if launched
-  const int deep_arg = blockIdx.x < 8 ? deep_arg0 : deep_arg1;
+// What the order's workgroup keeps in LDS besides its two [kJobBuckets][nchunks] tables
+struct JobScratch {
+  int tot[kJobBuckets], totw[kJobBuckets];
+  unsigned long long entries;
+  int total, whole, longest, filled;
+};
+// ints of LDS behind a JobScratch that an order over `base_grid` slots needs for its tables (sized by the grid's chunks)
+inline __host__ __device__ unsigned job_table_ints(const unsigned base_grid) {
+  return 2u * kJobBuckets * ((base_grid / 8u + 63u) >> 6);
+}
+// One XCD's order by a workgroup of NT threads (a multiple of 64: every wave takes whole 64-slot chunks, NT / 64 of
+// them per round): the stand-alone kernel below runs it with 1024, the list build's last launch
+// (tile_partition2.hip) with 256 beside its chunks.  The result does not depend on NT.
+// order_block: 0-7 the order deep_arg0 describes (threshold, tail, which array) for XCD order_block, 8-15 deep_arg1's.
+template <int NT>
+__device__ __forceinline__ void tile_jobs_order(const unsigned order_block, const int tiles_x, const int tiles_y,
+                                                const unsigned base_grid, const int2 *__restrict__ tile_bins,
+                                                const int deep_arg0, const int deep_arg1, int *__restrict__ jobs_base,
+                                                float *stats, const float fixed_ratio, JobScratch &S,
+                                                int *__restrict__ tables) {
+  const int deep_arg = order_block < 8 ? deep_arg0 : deep_arg1;
   int deep_threshold = gsr_deep_threshold(deep_arg);
   const int tail64 = gsr_deep_tail64(deep_arg);
   int *const jobs = jobs_base + (size_t)gsr_deep_second(deep_arg) * 4u * base_grid;
@@ -220,16 +233,15 @@ static __global__ __launch_bounds__(1024) void tile_jobs_kernel(const int tiles_
     if (l0 > 0.f && l1 > 0.f && d0 > 0.f && d1 > 0.f) ratio = fminf(0.5f, fmaxf(1.f / 64.f, (d1 / l1) / (d0 / l0)));
   }
   if (fixed_ratio > 0.f) ratio = fixed_ratio;
-  // bucket-major tables: a wave scans one bucket's chunks with its lanes (conflict-free rows)
-  __shared__ int cnt[kJobBuckets][kJobChunks];   // slots taken by chunk c's jobs of bucket q -> their offset in the bucket
-  __shared__ int cntw[kJobBuckets][kJobChunks];  // the same for whole-tile jobs only (their rank among themselves)
-  __shared__ int tot[kJobBuckets], totw[kJobBuckets];
-  __shared__ int total_s, whole_s;
-  __shared__ int longest_s, filled_s;
-  __shared__ unsigned long long entries_s;
-  const unsigned xcd = blockIdx.x & 7u, slots = base_grid / 8u;
+  const unsigned xcd = order_block & 7u, slots = base_grid / 8u;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nchunks = (int)((slots + 63u) >> 6);
+  // bucket-major tables [kJobBuckets][nchunks]: a wave scans one bucket's chunks with its lanes
+  int *const cnt = tables;                          // slots taken by chunk c's jobs of bucket q -> their offset in the bucket
+  int *const cntw = tables + kJobBuckets * nchunks;  // the same for whole-tile jobs only (their rank among themselves)
+  int *const tot = S.tot, *const totw = S.totw;
+  int &total_s = S.total, &whole_s = S.whole, &longest_s = S.longest, &filled_s = S.filled;
+  unsigned long long &entries_s = S.entries;
   const unsigned long long below = (1ull << lane) - 1ull;
   // Lists that are ALL ALIKE (the longest within 1.5 x the mean of the non-empty ones: a random cloud, never a trained
   // model) leave nothing to balance: their tiles keep the static map's order (one bucket) and the BACKWARD splits none
@@ -241,7 +253,7 @@ static __global__ __launch_bounds__(1024) void tile_jobs_kernel(const int tiles_
   {
     int longest = 0, filled = 0;
     unsigned long long entries = 0ull;
-    for (unsigned s = tid; s < slots; s += 1024u) {
+    for (unsigned s = tid; s < slots; s += (unsigned)NT) {
       const int tile = gsr_xcd_remap(s * 8u + xcd, tiles_x, tiles_y);
       if (tile < 0) continue;
       const int2 r = tile_bins[tile];
@@ -265,10 +277,7 @@ static __global__ __launch_bounds__(1024) void tile_jobs_kernel(const int tiles_
   __syncthreads();
   const bool alike = filled_s > 0 && 2ull * (unsigned long long)longest_s * (unsigned)filled_s <= 3ull * entries_s;
   if (alike && gsr_deep_second(deep_arg)) deep_threshold = max(deep_threshold, longest_s);
-  for (int i = tid; i < kJobBuckets * nchunks; i += 1024) {
-    cnt[i / nchunks][i % nchunks] = 0;
-    cntw[i / nchunks][i % nchunks] = 0;
-  }
+  for (int i = tid; i < 2 * kJobBuckets * nchunks; i += NT) tables[i] = 0;
   // one item per slot: bucket, weight (4 = a split tile's four jobs), and the lanes of its wave chunk that share its bucket
   auto item = [&](const unsigned s, int &tile, int &len, int &q, int &weight, unsigned long long &same,
                   unsigned long long &four) {
@@ -289,27 +298,27 @@ static __global__ __launch_bounds__(1024) void tile_jobs_kernel(const int tiles_
     }
     four = __ballot(weight == 4) & same;
   };
-  const unsigned rounds = (slots + 1023u) / 1024u;
-  int tile0, len0, q0, weight0;  // round 0's item stays in registers (the only round up to 8 192 tiles)
+  const unsigned rounds = (slots + (unsigned)NT - 1u) / (unsigned)NT;
+  int tile0, len0, q0, weight0;  // round 0's item stays in registers (with 1024 threads the only round up to 8 192 tiles)
   unsigned long long same0, four0;
   item(tid, tile0, len0, q0, weight0, same0, four0);
   __syncthreads();
   // pass 1: per (bucket, chunk) slot counts
   for (unsigned it = 0; it < rounds; ++it) {
-    const unsigned s = it * 1024u + tid;
+    const unsigned s = it * (unsigned)NT + tid;
     const int c = (int)(s >> 6);
     int tile = tile0, len = len0, q = q0, weight = weight0;
     unsigned long long same = same0, four = four0;
     if (it) item(s, tile, len, q, weight, same, four);
     if (tile >= 0 && (same & below) == 0) {  // the first lane of its bucket in this chunk
-      cnt[q][c] = __popcll(same) + 3 * __popcll(four);
-      cntw[q][c] = __popcll(same & ~four);
+      cnt[q * nchunks + c] = __popcll(same) + 3 * __popcll(four);
+      cntw[q * nchunks + c] = __popcll(same & ~four);
     }
   }
   __syncthreads();
-  // exclusive prefix down the chunks of every bucket: wave w takes buckets w, w + 16, ...; lane = chunk
-  for (int q = wave; q < kJobBuckets; q += 16) {
-    const int v = lane < nchunks ? cnt[q][lane] : 0, w = lane < nchunks ? cntw[q][lane] : 0;
+  // exclusive prefix down the chunks of every bucket: wave w takes buckets w, w + NT / 64, ...; lane = chunk
+  for (int q = wave; q < kJobBuckets; q += NT / 64) {
+    const int v = lane < nchunks ? cnt[q * nchunks + lane] : 0, w = lane < nchunks ? cntw[q * nchunks + lane] : 0;
     int incl = v, inclw = w;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
@@ -317,8 +326,8 @@ static __global__ __launch_bounds__(1024) void tile_jobs_kernel(const int tiles_
       if (lane >= o) incl += t, inclw += u;
     }
     if (lane < nchunks) {
-      cnt[q][lane] = incl - v;
-      cntw[q][lane] = inclw - w;
+      cnt[q * nchunks + lane] = incl - v;
+      cntw[q * nchunks + lane] = inclw - w;
     }
     if (lane == 63) tot[q] = incl, totw[q] = inclw;
   }
@@ -343,20 +352,20 @@ static __global__ __launch_bounds__(1024) void tile_jobs_kernel(const int tiles_
   const int tail_first = whole - n_tail;
   // pass 2: every job to its slot
   for (unsigned it = 0; it < rounds; ++it) {
-    const unsigned s = it * 1024u + tid;
+    const unsigned s = it * (unsigned)NT + tid;
     const int c = (int)(s >> 6);
     int tile = tile0, len = len0, q = q0, weight = weight0;
     unsigned long long same = same0, four = four0;
     if (it) item(s, tile, len, q, weight, same, four);
     if (tile < 0) continue;
     const unsigned long long before = same & below;
-    const int at = tot[q] + cnt[q][c] + __popcll(before) + 3 * __popcll(before & four);
+    const int at = tot[q] + cnt[q * nchunks + c] + __popcll(before) + 3 * __popcll(before & four);
     if (weight == 4) {
 #pragma unroll
       for (int p = 0; p < 4; ++p) jobs[(size_t)(at + p) * 8u + xcd] = tile | ((1 << p) << kJobTileBits);
       continue;
     }
-    const int rank = totw[q] + cntw[q][c] + __popcll(before & ~four);
+    const int rank = totw[q] + cntw[q * nchunks + c] + __popcll(before & ~four);
     const bool in_tail = n_tail > 0 && rank >= tail_first;
     if (in_tail && len > 0) {
       jobs[(size_t)at * 8u + xcd] = -1;
@@ -371,7 +380,7 @@ static __global__ __launch_bounds__(1024) void tile_jobs_kernel(const int tiles_
       }
     }
   }
-  for (unsigned s = total + 4 * n_tail + tid; s < 4u * slots; s += 1024) jobs[(size_t)s * 8u + xcd] = -1;
+  for (unsigned s = total + 4 * n_tail + tid; s < 4u * slots; s += NT) jobs[(size_t)s * 8u + xcd] = -1;
   if (xcd == 0 && tid == 0) {
     // where the compositing waves find the statistics (behind both job arrays), and the exponential average: what the
     // earlier launches of this direction measured counts half from now on (every workgroup of this launch has read
@@ -383,6 +392,18 @@ static __global__ __launch_bounds__(1024) void tile_jobs_kernel(const int tiles_
       for (int x = 0; x < 8; ++x) st[x].dur[0] *= 0.5f, st[x].dur[1] *= 0.5f, st[x].len[0] *= 0.5f, st[x].len[1] *= 0.5f;
     }
   }
+}
+
+static __global__ __launch_bounds__(1024) void tile_jobs_kernel(const int tiles_x, const int tiles_y,
+                                                                const unsigned base_grid,
+                                                                const int2 *__restrict__ tile_bins,
+                                                                const int deep_arg0, const int deep_arg1,
+                                                                int *__restrict__ jobs_base, float *stats,
+                                                                const float fixed_ratio) {
+  __shared__ JobScratch S;
+  __shared__ int tables[2 * kJobBuckets * kJobChunks];
+  tile_jobs_order<1024>(blockIdx.x, tiles_x, tiles_y, base_grid, tile_bins, deep_arg0, deep_arg1, jobs_base, stats,
+                        fixed_ratio, S, tables);
 }
 
 float *gsr_job_stats_buffer(hipStream_t s);  // capi.hip: this device's JobStats[2] (nullptr if it cannot be had)

@@ -27,6 +27,8 @@
 //     P6 bases      prefix over all tiles -> tile_bins (tile_scatter.hip's kernel)
 //     P7 colscatter per chunk: entries are ranked by column in stream order inside LDS
 //                   and leave as runs of ~17-34 ids per tile.
+//                   Its first workgroups also write the compositing launches' job orders behind tile_bins
+//                   (raster_common.h) when the caller gives their parameters: no launch of their own.
 //
 // HBM traffic per list entry: 8 B written by P3, 4 + 8 B read and 4 B written by P4 / P7
 // (24 B) against 8 + 4 + 8 + 4x8 (amplified) before.  The lists are the same, bit for bit,
@@ -61,9 +63,16 @@ struct SlabItems {
 };
 
 // P3's slab.  The records and row parameters are read only while a batch's items are derived (item_of); the batch's
-// item table, its sorted order and the start-mask block counts are first written after that, behind a barrier, so
-// they take the same 12 KB: 22 KB of LDS per workgroup instead of 34 KB, seven workgroups on a CU instead of four.
+// table of sorted items is first written after that, behind a barrier, so it takes the same 12 KB: 20 KB of LDS per
+// workgroup instead of 34 KB, seven workgroups on a CU instead of four.
 // A slab of more than kItems items reloads its records at the top of every batch after the first.
+// The table is in SORTED order (by row, then item order), three words per item.  At placement a thread puts its
+// items' two packed words (still in its registers) at their sorted slots; the thread that then owns sorted items
+// t kR .. t kR + kR - 1 knows their entry offsets `run` and turns them, in place, into what an entry needs:
+//   s_pos  the item's row's first global slot minus the row's first entry in the batch: entry j goes to s_pos + j
+//   s_gid  the Gaussian's id
+//   s_col  t0 - run: entry j is tile column s_col + j
+// Consecutive entries belong to the same item, so an entry's three reads are broadcasts.
 struct EmitSlab {
   int pref[kSlab];
   int gid[kSlab];
@@ -73,12 +82,21 @@ struct EmitSlab {
       RowParams par[kSlab];
     };
     struct {
-      unsigned it_a[kItems];             // row | t0 << 16
-      unsigned it_b[kItems];             // count | owner thread << 16
-      unsigned short sorted[kItems];
-      int blkfirst[kMaskBlocks];         // starts before the block
+      int s_pos[kItems];  // at placement: row | t0 << 16
+      int s_gid[kItems];  // at placement: count | owner thread << 16
+      int s_col[kItems];
     };
   };
+};
+// how an entry finds its sorted item: batches of up to 64 kMaskBlocks entries by start masks -- bit e & 63 of word
+// e >> 6 is set where a sorted item's first entry sits; the item that owns entry e is (#starts at or before e) - 1:
+// two popcounts -- larger ones by a binary search over the items' entry offsets
+union EmitFind {
+  struct {
+    unsigned long long smask[kMaskBlocks];
+    int blkfirst[kMaskBlocks];  // starts before the block
+  };
+  int sout[kItems];  // entry offset (within the batch) of sorted item s
 };
 
 // exclusive prefix of v over the 256 threads of the workgroup (and the total); two barriers
@@ -235,20 +253,19 @@ __device__ __forceinline__ int scan_rows(const int ny, F f, int *out, const bool
 // row) order), sorted stably by row in LDS, and every row's entries of the batch are written as
 // one run.  The sort ranks like P7 below: every wave ranks its own contiguous quarter of the
 // batch with wave-private row counters, one prefix over (row, wave) later every item has its slot.
-__global__ __launch_bounds__(kSlab) void emit_kernel(const Dims D, const int capacity, const int *__restrict__ order,
-                                                     const SplatRec *__restrict__ recs, const int *__restrict__ tableA,
-                                                     const int *__restrict__ rowtot, int *__restrict__ row_start,
-                                                     int *__restrict__ row_chunk_start, int *__restrict__ count_out,
-                                                     unsigned short *__restrict__ tx_out, int *__restrict__ gid_out) {
+// (waves_per_eu: seven waves per SIMD is what the LDS allows; left alone the scheduler takes 80 VGPRs for six)
+__global__ __launch_bounds__(kSlab) __attribute__((amdgpu_waves_per_eu(7)))
+void emit_kernel(const Dims D, const int capacity, const int *__restrict__ order, const SplatRec *__restrict__ recs,
+                 const int *__restrict__ tableA, const int *__restrict__ rowtot, int *__restrict__ row_start,
+                 int *__restrict__ row_chunk_start, int *__restrict__ count_out, unsigned short *__restrict__ tx_out,
+                 int *__restrict__ gid_out) {
   constexpr int kR = kItems / kSlab;     // items per thread and batch
   __shared__ EmitSlab W;
-  unsigned *it_a = W.it_a, *it_b = W.it_b;
-  unsigned short *sorted = W.sorted;
-  int *blkfirst = W.blkfirst;
-  __shared__ int sout[kItems + 1];       // entry offset (within the batch) of sorted item s
-  // start masks: bit e & 63 of word e >> 6 is set where a sorted item's first entry sits; the item
-  // that owns entry e is (#starts at or before e) - 1: two popcounts instead of a binary search
-  __shared__ unsigned long long smask[kMaskBlocks];
+  static_assert(kMaskBlocks == kSlab && kItems % kSlab == 0, "a thread clears one mask word and owns kR sorted items");
+  __shared__ EmitFind F;
+  int *s_pos = W.s_pos, *s_gid = W.s_gid, *s_col = W.s_col;
+  unsigned long long *smask = F.smask;
+  int *blkfirst = F.blkfirst, *sout = F.sout;
   __shared__ int wsum[4];
   __shared__ long long wsum64[4];
   extern __shared__ int rows_lds[];      // 7 arrays of tiles_y ints
@@ -296,6 +313,7 @@ __global__ __launch_bounds__(kSlab) void emit_kernel(const Dims D, const int cap
     }
     for (int r = tid; r < 4 * ny; r += kSlab) wcnt[r] = 0;
     for (int r = tid; r < ny; r += kSlab) bentc[r] = 0;
+    smask[tid] = 0ull;  // (kMaskBlocks == kSlab; the binary-search branch writes its offsets over them in step 4)
     __syncthreads();
     // 1. the batch's items; wave w ranks the w-th contiguous quarter of them (rounded up to whole
     //    rounds of 64: a short batch still keeps all four waves busy) by row, in item order
@@ -312,18 +330,13 @@ __global__ __launch_bounds__(kSlab) void emit_kernel(const Dims D, const int cap
       ib[r] = (unsigned)(t1 - t0) | ((unsigned)k << 16);
     }
     __syncthreads();  // (every record has been read: the item table goes where they were)
-    int rank[kR], myrow[kR];
+    int rank[kR];  // (-1: no item, or one without entries)
 #pragma unroll
     for (int r = 0; r < kR; ++r) {
-      myrow[r] = -1;
-      rank[r] = 0;
+      rank[r] = -1;
       if (r * 64 >= per) continue;  // (uniform)
       const int idx = w * per + r * 64 + lane;
       const int ty = (int)(ia[r] & 0xffffu), cnt = (int)(ib[r] & 0xffffu);
-      if (idx < nb) {
-        it_a[idx] = ia[r];
-        it_b[idx] = ib[r];
-      }
       const bool live = idx < nb && cnt > 0;
       unsigned long long peers = __ballot(live);
       for (int bit = 0; bit < row_bits; ++bit) {
@@ -333,11 +346,10 @@ __global__ __launch_bounds__(kSlab) void emit_kernel(const Dims D, const int cap
       }
       const int below = __popcll(peers & lt);
       const int prev = live ? wcnt[w * ny + ty] : 0;  // every peer reads before the group's first lane writes
-      rank[r] = prev + below;
+      rank[r] = live ? prev + below : -1;
       asm volatile("" : "+v"(rank[r]));  // (taken here, not where it is used: see colscatter_kernel)
       if (live && below == 0) wcnt[w * ny + ty] = prev + __popcll(peers);
       if (live) atomicAdd(&bentc[ty], cnt);
-      myrow[r] = live ? ty : -1;
     }
     __syncthreads();
     // 2. prefix over (row, wave) of the item counts -> first slots; over the rows of the entries
@@ -372,45 +384,54 @@ __global__ __launch_bounds__(kSlab) void emit_kernel(const Dims D, const int cap
       }
     }
     __syncthreads();
-    // 3. placement
+    // 3. placement: the items' packed words to their sorted slots
 #pragma unroll
     for (int r = 0; r < kR; ++r)
-      if (myrow[r] >= 0) sorted[wcnt[w * ny + myrow[r]] + rank[r]] = (unsigned short)(w * per + r * 64 + lane);
+      if (rank[r] >= 0) {
+        const int slot = wcnt[w * ny + (int)(ia[r] & 0xffffu)] + rank[r];
+        s_pos[slot] = (int)ia[r];
+        s_gid[slot] = (int)ib[r];
+      }
     __syncthreads();
-    // 4. entry offsets of the sorted items (thread t: sorted items t kR .. t kR + kR - 1)
+    // 4. entry offsets of the sorted items (thread t: sorted items t kR .. t kR + kR - 1) -> the table and the starts
+    const int nblk = (E + 63) >> 6;
+    const bool use_masks = nblk <= kMaskBlocks;
     {
-      int c[kR], sum = 0;
+      unsigned a[kR], b[kR];
+      int sum = 0;
 #pragma unroll
       for (int j = 0; j < kR; ++j) {
         const int sidx = tid * kR + j;
-        c[j] = sidx < nplaced ? (int)(it_b[sorted[sidx]] & 0xffffu) : 0;
-        sum += c[j];
+        a[j] = (unsigned)s_pos[sidx];
+        b[j] = sidx < nplaced ? (unsigned)s_gid[sidx] : 0u;  // (count 0 behind the last placed item)
+        sum += (int)(b[j] & 0xffffu);
       }
       int tot;
       int run = block_excl(sum, wsum, tot);
 #pragma unroll
       for (int j = 0; j < kR; ++j) {
         const int sidx = tid * kR + j;
-        if (sidx < nplaced) sout[sidx] = run;
-        run += c[j];
+        if (sidx < nplaced) {
+          const int row = (int)(a[j] & 0xffffu);
+          s_pos[sidx] = gcur[row] - bent[row];
+          s_gid[sidx] = W.gid[b[j] >> 16];
+          s_col[sidx] = (int)(a[j] >> 16) - run;
+          if (use_masks) atomicOr(&smask[run >> 6], 1ull << (run & 63));
+          else sout[sidx] = run;
+        }
+        run += (int)(b[j] & 0xffffu);
       }
-      if (tid == 0) sout[nplaced] = E;
     }
+    __syncthreads();
     // 5. output-driven, coalesced: entry j of the batch belongs to sorted item s(j)
-    const int nblk = (E + 63) >> 6;
-    const bool use_masks = nblk <= kMaskBlocks;
     if (use_masks) {
-      if (tid < nblk) smask[tid] = 0ull;
-      __syncthreads();
-      for (int sidx = tid; sidx < nplaced; sidx += kSlab) atomicOr(&smask[sout[sidx] >> 6], 1ull << (sout[sidx] & 63));
-      __syncthreads();
       const int c = tid < nblk ? __popcll(smask[tid]) : 0;
       int tot;
       const int ex = block_excl(c, wsum, tot);
       if (tid < nblk) blkfirst[tid] = ex;
       __syncthreads();
-      // four independent entries per thread and step: the LDS look-up chain (mask -> item -> row
-      // cursors) is latency, not bandwidth
+      // four independent entries per thread and step: the LDS look-up chain (mask -> item's three words) is latency,
+      // not bandwidth
       for (int j0 = 0; j0 < E; j0 += 4 * kSlab) {
         int jj[4], lo[4];
 #pragma unroll
@@ -419,32 +440,22 @@ __global__ __launch_bounds__(kSlab) void emit_kernel(const Dims D, const int cap
           const int jc = jj[u] < E ? jj[u] : E - 1;
           lo[u] = blkfirst[jc >> 6] + __popcll(smask[jc >> 6] & ((2ull << (jc & 63)) - 1ull)) - 1;
         }
-        unsigned a[4], b[4];
-        int so[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int si = sorted[lo[u]];
-          a[u] = it_a[si];
-          b[u] = it_b[si];
-          so[u] = sout[lo[u]];
-        }
         long long pos[4];
-        int gidv[4];
+        int gidv[4], col[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-          const int row = (int)(a[u] & 0xffffu);
-          pos[u] = (long long)gcur[row] + (jj[u] - bent[row]);
-          gidv[u] = W.gid[b[u] >> 16];
+          pos[u] = (long long)s_pos[lo[u]] + jj[u];
+          gidv[u] = s_gid[lo[u]];
+          col[u] = s_col[lo[u]] + jj[u];
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u)
           if (jj[u] < E && pos[u] < capacity) {
-            tx_out[pos[u]] = (unsigned short)((int)(a[u] >> 16) + (jj[u] - so[u]));
+            tx_out[pos[u]] = (unsigned short)col[u];
             gid_out[pos[u]] = gidv[u];
           }
       }
     } else {
-      __syncthreads();
       for (int j = tid; j < E; j += kSlab) {
         int lo = 0, hi = nplaced;  // last s with sout[s] <= j
         while (hi - lo > 1) {
@@ -452,12 +463,10 @@ __global__ __launch_bounds__(kSlab) void emit_kernel(const Dims D, const int cap
           if (sout[mid] <= j) lo = mid;
           else hi = mid;
         }
-        const unsigned a = it_a[sorted[lo]], b = it_b[sorted[lo]];
-        const int row = (int)(a & 0xffffu), t0 = (int)(a >> 16), k = (int)(b >> 16);
-        const long long pos = (long long)gcur[row] + (j - bent[row]);
+        const long long pos = (long long)s_pos[lo] + j;
         if (pos < capacity) {
-          tx_out[pos] = (unsigned short)(t0 + (j - sout[lo]));
-          gid_out[pos] = W.gid[k];
+          tx_out[pos] = (unsigned short)(s_col[lo] + j);
+          gid_out[pos] = s_gid[lo];
         }
       }
     }
@@ -609,6 +618,42 @@ __global__ __launch_bounds__(1024) void colscan_row_kernel(const Dims D, const i
 // wave-private counter per column carries the rank across rounds (no atomics, no barrier
 // inside the loop); one barrier later the four waves' counts are prefixed per column and
 // every entry knows its slot.  CMAX: column capacity of the LDS tables (256 or 1024).
+//
+// The launch also carries the compositing launches' JOB ORDERS (raster_common.h) when the caller of the list build
+// asks for them: tile_bins, all they read, is complete before this launch starts, so the `J.blocks` (8 or 16)
+// workgroups at the FRONT of the grid -- dispatched first -- build them beside the chunks instead of in a launch of
+// their own behind them; the chunks' workgroups follow, shifted by that many.  The orders' tables take the place of a
+// chunk's arrays in LDS (the kernel's footprint and its residency do not change).
+struct JobOrders {
+  int blocks;  // 0: none; 8: deep0's order; 16: deep0's and deep1's
+  unsigned base_grid;
+  const int2 *tile_bins;
+  int deep0, deep1;
+  int *jobs;
+  float *stats;
+  float ratio;
+};
+template <int CMAX>
+struct ScatterLds {
+  union {
+    struct {
+      unsigned short s_stx[kChunk];  // columns in ranked order
+      int s_gid[kChunk];             // ids in ranked order
+      int loff[CMAX];                // first ranked slot of a column
+      int wcnt[4][CMAX];             // per-wave column counts, then per-wave bases
+      int wsum[4];
+    };
+    struct {
+      gsr::JobScratch scratch;
+      int tables[1];  // [2][kJobBuckets][the grid's chunks]: as far as the chunk's arrays reach (job_orders_fit)
+    } jobs;
+  };
+};
+// do the tables of an order over `base_grid` slots fit into the LDS of colscatter_kernel<CMAX>?
+template <int CMAX>
+inline bool job_orders_fit(const unsigned base_grid) {
+  return sizeof(gsr::JobScratch) + 4 * (size_t)gsr::job_table_ints(base_grid) <= sizeof(ScatterLds<CMAX>);
+}
 template <int CMAX>
 __global__ __launch_bounds__(256) void colscatter_kernel(const Dims D, const int capacity,
                                                          const int *__restrict__ row_start,
@@ -617,15 +662,20 @@ __global__ __launch_bounds__(256) void colscatter_kernel(const Dims D, const int
                                                          const int *__restrict__ gid_in,
                                                          const int *__restrict__ tableB,
                                                          const unsigned *__restrict__ tile_base,
-                                                         int *__restrict__ ids_out) {
+                                                         int *__restrict__ ids_out, const JobOrders J) {
   constexpr int kRounds = kChunk / 256;     // 16 entries per lane
-  __shared__ unsigned short s_stx[kChunk];  // columns in ranked order
-  __shared__ int s_gid[kChunk];             // ids in ranked order
-  __shared__ int loff[CMAX];                // first ranked slot of a column
-  __shared__ int wcnt[4][CMAX];             // per-wave column counts, then per-wave bases
-  __shared__ int wsum[4];
+  __shared__ ScatterLds<CMAX> L;
+  if ((int)blockIdx.x < J.blocks) {  // (uniform over the workgroup)
+    gsr::tile_jobs_order<256>(blockIdx.x, D.tiles_x, D.tiles_y, J.base_grid, J.tile_bins, J.deep0, J.deep1, J.jobs,
+                              J.stats, J.ratio, L.jobs.scratch, L.jobs.tables);
+    return;
+  }
+  unsigned short *s_stx = L.s_stx;
+  int *s_gid = L.s_gid, *loff = L.loff, *wsum = L.wsum;
+  int (*wcnt)[CMAX] = L.wcnt;
+  const int chunk = (int)blockIdx.x - J.blocks;
   int row, beg, end;
-  if (!chunk_slice(D, capacity, blockIdx.x, row_start, row_chunk_start, row, beg, end)) return;
+  if (!chunk_slice(D, capacity, chunk, row_start, row_chunk_start, row, beg, end)) return;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, cnt = end - beg;
   const unsigned long long lt = (1ull << lane) - 1ull;
   for (int t = tid; t < 4 * CMAX; t += 256) (&wcnt[0][0])[t] = 0;
@@ -710,7 +760,7 @@ __global__ __launch_bounds__(256) void colscatter_kernel(const Dims D, const int
   // destination of ranked slot j of column t: tile base + the chunk's prefix + (j - loff[t]);
   // the first three are folded into loff (one coalesced load per table instead of two L2
   // look-ups per entry)
-  const int *pre = tableB + (size_t)blockIdx.x * D.txp;
+  const int *pre = tableB + (size_t)chunk * D.txp;
   const unsigned *tb = tile_base + (size_t)row * D.tiles_x;
   for (int t = tid; t < D.tiles_x; t += 256) loff[t] = (int)(tb[t] + (unsigned)pre[t] - (unsigned)loff[t]);
   __syncthreads();
@@ -770,10 +820,16 @@ size_t gsr_tile_partition2_workspace_bytes(int n, int capacity, int tiles_x, int
 // order[n]: Gaussians by depth; recs[n]: the records of gsr_count_reach (index order).
 // -> ids_sorted (cut at `capacity` entries), tile_bins[tiles][2], count_out (nullable,
 // device-accessible): the uncut number of list entries.
-int gsr_tile_partition2(int n, int capacity, const int *order, const void *recs, int tiles_x, int tiles_y,
-                        int *ids_sorted, int *tile_bins, int *count_out, void *workspace, size_t workspace_bytes,
-                        hipStream_t s) {
+//
+// deep_first / deep_second: the two `deep_tile_threshold` words gsr_tile_jobs_build takes (raster_fwd.hip), or 0.  With
+// GSR_DEEP_ORDERED in deep_first the last launch also writes the job orders behind tile_bins (colscatter_kernel) and
+// *jobs_built becomes 1 -- unless the grid is beyond the sort's tables or the orders' tables do not fit that kernel's
+// LDS: then nothing is written, *jobs_built stays 0 and the caller's gsr_tile_jobs_build does it as before.
+int gsr_tile_partition2_jobs(int n, int capacity, const int *order, const void *recs, int tiles_x, int tiles_y,
+                             int *ids_sorted, int *tile_bins, int *count_out, void *workspace, size_t workspace_bytes,
+                             int deep_first, int deep_second, int *jobs_built, hipStream_t s) {
   using namespace gsr_p2;
+  if (jobs_built) *jobs_built = 0;
   if (!gsr_tile_partition2_supported(tiles_x, tiles_y)) {
     gsr_set_error("tile_partition2: a %d x %d tile grid is not supported", tiles_x, tiles_y);
     return GSR_EINVAL;
@@ -807,14 +863,36 @@ int gsr_tile_partition2(int n, int capacity, const int *order, const void *recs,
     int rc = gsr_tile_bases(tiles_x * tiles_y, tile_cnt, tile_bins, s);
     if (rc != GSR_OK) return rc;
   }
+  JobOrders J{};
+  if (gsr_deep_ordered(deep_first)) {
+    const unsigned base = gsr_xcd_grid(tiles_x, tiles_y);
+    const bool fit = tiles_x <= 256 ? job_orders_fit<256>(base) : job_orders_fit<1024>(base);
+    if (base / 8u <= (unsigned)gsr::kJobChunks * 64u && fit) {
+      J.blocks = deep_second > 0 ? 16 : 8;
+      J.base_grid = base;
+      J.tile_bins = reinterpret_cast<const int2 *>(tile_bins);
+      J.deep0 = deep_first, J.deep1 = deep_second;
+      J.jobs = tile_bins + 2 * (size_t)tiles_x * tiles_y;
+      J.stats = gsr::gsr_job_stats_buffer(s);
+      J.ratio = gsr::gsr_job_split_ratio();
+      if (jobs_built) *jobs_built = 1;
+    }
+  }
   if (tiles_x <= 256)
-    hipLaunchKernelGGL(colscatter_kernel<256>, dim3(L.chunk_slots), dim3(256), 0, s, D, capacity,
+    hipLaunchKernelGGL(colscatter_kernel<256>, dim3(L.chunk_slots + J.blocks), dim3(256), 0, s, D, capacity,
                        (const int *)row_start, (const int *)row_chunk_start, (const unsigned short *)txs,
-                       (const int *)gids, (const int *)tableB, (const unsigned *)tile_cnt, ids_sorted);
+                       (const int *)gids, (const int *)tableB, (const unsigned *)tile_cnt, ids_sorted, J);
   else
-    hipLaunchKernelGGL(colscatter_kernel<1024>, dim3(L.chunk_slots), dim3(256), 0, s, D, capacity,
+    hipLaunchKernelGGL(colscatter_kernel<1024>, dim3(L.chunk_slots + J.blocks), dim3(256), 0, s, D, capacity,
                        (const int *)row_start, (const int *)row_chunk_start, (const unsigned short *)txs,
-                       (const int *)gids, (const int *)tableB, (const unsigned *)tile_cnt, ids_sorted);
+                       (const int *)gids, (const int *)tableB, (const unsigned *)tile_cnt, ids_sorted, J);
   GSR_CHECK_LAUNCH("tile_partition2");
   return GSR_OK;
+}
+
+int gsr_tile_partition2(int n, int capacity, const int *order, const void *recs, int tiles_x, int tiles_y,
+                        int *ids_sorted, int *tile_bins, int *count_out, void *workspace, size_t workspace_bytes,
+                        hipStream_t s) {
+  return gsr_tile_partition2_jobs(n, capacity, order, recs, tiles_x, tiles_y, ids_sorted, tile_bins, count_out,
+                                  workspace, workspace_bytes, 0, 0, nullptr, s);
 }

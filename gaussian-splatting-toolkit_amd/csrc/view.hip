@@ -83,15 +83,20 @@ GSR_EXPORT int gsr_rasterize_gaussians_forward(const gsr_raster_desc *v, gsr_str
                                           v->reach_records, v->order, v->sort_ws, v->sort_ws_bytes, stream));
     order = v->order;
   }
-  GSR_TRY(gsr_bin_sorted_dev(n, v->capacity, order, v->counts ? v->cum : nullptr, v->xys, v->radii, v->reach_records,
-                             tiles_x, tiles_y, 16, 1, v->ids, v->tile_bins, v->count_out, nullptr, v->bin_ws,
-                             v->bin_ws_bytes, stream));
   int deep = v->deep_tile_threshold;
-  if (deep > 0 && (deep & GSR_DEEP_ORDERED) && !(deep & GSR_DEEP_PREBUILT) && v->deep_tile_threshold_backward > 0) {
-    // both job orders in one launch, right behind the lists (also when only the lists were asked for: lists built
-    // ahead of time on a side stream come with their orders, and the compositing call that takes them later -- on
-    // the critical path behind the models' read-back -- launches nothing in front of its kernel)
-    GSR_TRY(gsr_tile_jobs_build(tiles_x, tiles_y, v->tile_bins, deep, v->deep_tile_threshold_backward, stream));
+  const bool orders = deep > 0 && (deep & GSR_DEEP_ORDERED) && !(deep & GSR_DEEP_PREBUILT) &&
+                      v->deep_tile_threshold_backward > 0;
+  // both job orders right behind the lists (also when only the lists were asked for: lists built ahead of time on a
+  // side stream come with their orders, and the compositing call that takes them later -- on the critical path behind
+  // the models' read-back -- launches nothing in front of its kernel): inside the list build's last launch where it
+  // can carry them (the two-level partition), else in one launch of their own
+  int built = 0;
+  GSR_TRY(gsr_bin_sorted_dev_jobs(n, v->capacity, order, v->counts ? v->cum : nullptr, v->xys, v->radii,
+                                  v->reach_records, tiles_x, tiles_y, 16, 1, v->ids, v->tile_bins, v->count_out, nullptr,
+                                  v->bin_ws, v->bin_ws_bytes, orders ? deep : 0,
+                                  orders ? v->deep_tile_threshold_backward : 0, &built, stream));
+  if (orders) {
+    if (!built) GSR_TRY(gsr_tile_jobs_build(tiles_x, tiles_y, v->tile_bins, deep, v->deep_tile_threshold_backward, stream));
     deep |= GSR_DEEP_PREBUILT;
   }
   if (v->out_img == nullptr) return GSR_OK;  // the lists only (built ahead of time, composited by a later call)

@@ -441,7 +441,7 @@ MAX_SCATTER_TILES = 16384  # tile grids the device-sized path supports without r
 def bin_sorted(num_points: int, num_intersects: int, order: Tensor, cum_sorted: Optional[Tensor], xys: Tensor,
                radii: Tensor, tile_bounds: Tuple[int, int, int], block_width: int,
                reach_records: Optional[Tensor] = None, device_sized: bool = False,
-               count_out: Optional[Tensor] = None, want_slots: bool = False):
+               count_out: Optional[Tensor] = None, want_slots: bool = False, job_orders=None):
     """Second half (``gsr_bin_sorted``): -> (gaussian_ids_sorted i32[I],
     tile_bins i32[T,2]), identical to what ``bin_and_sort_gaussians`` returns.
     With the records (and counts) of :func:`count_reach`: the same lists without
@@ -452,7 +452,10 @@ def bin_sorted(num_points: int, num_intersects: int, order: Tensor, cum_sorted: 
     later, off the critical path; ``count_out`` (int32[1], pinned host memory or
     device) receives that count.  ``cum_sorted=None``: only where :func:`lists_need_counts`
     is False.  ``want_slots``: also return ``slot_of_entry`` i32[I]
-    (the inverse of the scatter, for :func:`rasterize_backward_det`)."""
+    (the inverse of the scatter, for :func:`rasterize_backward_det`).
+    ``job_orders`` (device-sized lists with records): the (forward, backward) `deep_arg` words of the two job orders
+    the list build leaves behind ``tile_bins`` where its last launch can carry them (``gsr_bin_sorted_dev_jobs``);
+    default: the words :func:`forward_orders` will compute for these lists, ``(0, 0)``: none."""
     _check(order, "order", _i32)
     if cum_sorted is not None:
         _check(cum_sorted, "cum_sorted", _i32)
@@ -479,7 +482,19 @@ def bin_sorted(num_points: int, num_intersects: int, order: Tensor, cum_sorted: 
                 C.c_int(tile_bounds[1]), C.c_uint(block_width), C.c_int(bands), _ptr(ids), _ptr(tile_bins))
         tail = (_ptr(slots) if want_slots else None, _ptr(ws), C.c_size_t(nbytes), _stream(dev))
         if device_sized:
-            _call("gsr_bin_sorted_dev", *head, _ptr(count_out) if count_out is not None else None, *tail)
+            # the two job orders of the compositing launches that will walk these lists ride in the list build's last
+            # launch where it can carry them (the two-level partition): the words `forward_orders` would compute
+            fwd, second = (0, 0) if reach_records is None or want_slots else (
+                _list_build_orders(tile_bins, I, nt, tile_bounds) if job_orders is None else job_orders)
+            if fwd:
+                built = C.c_int(0)
+                _call("gsr_bin_sorted_dev_jobs", *head, _ptr(count_out) if count_out is not None else None, *tail[:-1],
+                      C.c_int(fwd), C.c_int(second), C.byref(built), tail[-1])
+                if built.value and second:  # (as view.hip and rasterize_gaussians_forward leave them)
+                    tile_bins._gsr_jobs_bwd, tile_bins._gsr_jobs_fwd = second, fwd
+                    tile_bins._gsr_jobs_by_list_build = True
+            else:
+                _call("gsr_bin_sorted_dev", *head, _ptr(count_out) if count_out is not None else None, *tail)
         else:
             _call("gsr_bin_sorted", *head, *tail)
     if want_slots:
@@ -745,6 +760,18 @@ def deep_arg(tile_bins: Optional[Tensor], list_entries: int, num_tiles: int, bac
             | (_order_cache["tail_bwd" if backward else "tail"] << _DEEP_TAIL_SHIFT))
 
 
+def _list_build_orders(tile_bins: Tensor, list_entries: int, num_tiles: int, tile_bounds):
+    """-> (fwd, bwd) `deep_arg` words for the call that builds these lists, as `forward_orders` will compute them for the
+    compositing forward over them; (0, 0) where it would build no pair of orders."""
+    fwd = deep_arg(tile_bins, list_entries, num_tiles, tile_bounds=tile_bounds)
+    if not (fwd & GSR_DEEP_ORDERED):
+        return 0, 0
+    bwd = deep_arg(tile_bins, list_entries, num_tiles, backward=True, tile_bounds=tile_bounds)
+    if not (bwd & GSR_DEEP_ORDERED):
+        return 0, 0
+    return fwd, bwd
+
+
 def forward_orders(tile_bins: Optional[Tensor], list_entries: int, num_tiles: int, tile_bounds, dev) -> int:
     """`deep_arg` for a compositing FORWARD, with both job orders -- this launch's and the coming backward's -- written
     by ONE small launch (`gsr_tile_jobs_build`) in front of it: the backward then finds its order ready
@@ -756,6 +783,10 @@ def forward_orders(tile_bins: Optional[Tensor], list_entries: int, num_tiles: in
     second = bwd if (bwd & GSR_DEEP_ORDERED) else 0
     if second and getattr(tile_bins, "_gsr_jobs_fwd", 0) == fwd and getattr(tile_bins, "_gsr_jobs_bwd", 0) == second:
         return fwd | GSR_DEEP_PREBUILT  # (the call that built these lists has written both orders behind them)
+    if getattr(tile_bins, "_gsr_jobs_by_list_build", False):
+        # the list build wrote orders for other words (another list count, a changed tuning row): build them again
+        order_counters["orders_prebuilt_fallbacks"] += 1
+        tile_bins._gsr_jobs_by_list_build = False
     _call("gsr_tile_jobs_build", C.c_int(int(tile_bounds[0])), C.c_int(int(tile_bounds[1])), _ptr(tile_bins), C.c_int(fwd),
           C.c_int(second), _stream(dev))
     try:
@@ -775,6 +806,7 @@ def backward_order(tile_bins: Optional[Tensor], list_entries: int, num_tiles: in
 
 
 _order_cache = {}
+order_counters = {"orders_prebuilt_fallbacks": 0}  # (rasterizer.rasterize puts its `counters` here)
 
 
 def _order_knob() -> bool:

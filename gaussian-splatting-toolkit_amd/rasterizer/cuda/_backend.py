@@ -41,6 +41,7 @@ SYMBOLS = (
     "gsr_bin_sorted_needs_counts",
     "gsr_bin_sorted",
     "gsr_bin_sorted_dev",
+    "gsr_bin_sorted_dev_jobs",
     "gsr_publish_int32",
     "gsr_rasterize_forward",
     "gsr_rasterize_backward",

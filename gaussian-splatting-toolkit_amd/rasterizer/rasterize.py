@@ -44,10 +44,13 @@ _tls = threading.local()
 #   ahead_hits / ahead_misses           ... and whether the rasterize call that followed could use them
 #   ahead_orders_used                   only the depth order of the side stream was used
 #   list_builds_two_round               lists built in two rounds (`_build_two_round`, deep scenes)
+#   orders_prebuilt_fallbacks           job orders the list build had written for other words than the forward then
+#                                       computed (another list count, a changed tuning row): built again by a launch
 #   ahead_recipes_off                   devices on which the recipe detection switched itself off (rasterizer/ahead.py)
 counters = {"list_rebuilds": 0, "list_builds_exact": 0, "list_builds_device_sized": 0, "list_builds_ahead": 0,
             "ahead_hits": 0, "ahead_misses": 0, "ahead_orders_used": 0, "ahead_recipes_off": 0,
-            "list_builds_two_round": 0}
+            "list_builds_two_round": 0, "orders_prebuilt_fallbacks": 0}
+_C.order_counters = counters  # (forward_orders counts the job orders it had to build again behind a list build's)
 
 
 def _cache_snapshot():

@@ -312,6 +312,25 @@ int gsr_bin_sorted_dev(int num_points, int capacity, const int32_t *order,
 size_t gsr_tile_jobs_ints(int tiles_x, int tiles_y);
 int gsr_tile_jobs_build(int tiles_x, int tiles_y, int32_t *tile_bins, int deep_arg_first,
                         int deep_arg_second, gsr_stream_t stream);
+/* gsr_bin_sorted_dev that also does gsr_tile_jobs_build's work: where the lists are built by
+ * the two-level partition, its last launch writes both job orders behind tile_bins beside
+ * the lists' last pass (tile_bins is complete by then), and no launch of its own is needed.
+ * deep_arg_first / deep_arg_second: as gsr_tile_jobs_build takes them (0 / without
+ * GSR_DEEP_ORDERED in the first: no order, plain gsr_bin_sorted_dev).  *jobs_built (host,
+ * required) = 1: the arrays are as gsr_tile_jobs_build would have left them, the compositing
+ * entries take GSR_DEEP_PREBUILT; 0 (another list builder, a grid whose tables do not fit
+ * that launch, a grid beyond the order's tables): nothing was written, call
+ * gsr_tile_jobs_build as before. */
+int gsr_bin_sorted_dev_jobs(int num_points, int capacity, const int32_t *order,
+                            const int32_t *cum_sorted, const float *xys,
+                            const int32_t *radii, const void *reach_records,
+                            int tiles_x, int tiles_y, unsigned block_width,
+                            int num_bands, int32_t *gaussian_ids_sorted,
+                            int32_t *tile_bins, int32_t *count_out,
+                            int32_t *slot_of_entry,
+                            void *workspace, size_t workspace_bytes,
+                            int deep_arg_first, int deep_arg_second, int *jobs_built,
+                            gsr_stream_t stream);
 /* The other mapping of the same compositing rule (measurement variant, 16x16 tiles, 3 channels):
  * lanes over the 64 staged splats, a wave-wide multiplicative prefix scan for the per-pixel
  * transmittance, ballot termination (forward.cu:349-385 is the serial loop it re-maps).  Same
