@@ -66,6 +66,13 @@ struct Cam {
   float p[16];  // full projection (P*V), row-major
 };
 
+// AA: also opacities_aa = opacities * compensation (the antialiased rasterize mode's opacity, vanilla_gs.py:815-816),
+// one float32 multiply on the compensation this lane holds anyway; everything else is the same text for both flags.
+struct FwdAA {
+  const float *opacities;
+  float *opacities_aa;
+};
+template <bool AA, typename... X>  // X: nothing, or FwdAA (an empty pack leaves the classic kernel's signature as it was)
 __global__ __launch_bounds__(256) void project_fwd_kernel(
     const int n, const float *__restrict__ means3d,
     const float *__restrict__ scales, const float glob_scale,
@@ -76,7 +83,8 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(
     float *__restrict__ cov3d, float *__restrict__ xys,
     float *__restrict__ depths, int *__restrict__ radii,
     float *__restrict__ conics, float *__restrict__ compensation,
-    int *__restrict__ num_tiles_hit) {
+    int *__restrict__ num_tiles_hit, const X... aa) {
+  static_assert(AA == (sizeof...(X) == 1), "project_fwd_kernel<true, FwdAA> or project_fwd_kernel<false>");
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
 
@@ -168,6 +176,10 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(
   conics[3 * i + 2] = o_k2;
   gsr_store_stream(compensation + i, o_comp);
   num_tiles_hit[i] = o_tiles;
+  if constexpr (AA) {
+    const FwdAA &a = (aa, ...);
+    gsr_store_stream(a.opacities_aa + i, a.opacities[i] * o_comp);  // (culled: x * 0)
+  }
 }
 
 // What the chain of project_bwd_kernel holds for one VISIBLE Gaussian between the cotangents and v_mean3d: shared
@@ -183,12 +195,15 @@ struct BwdChain {
   float g2[3], g3[6], gm[3];
 };
 
+// AA: `v_comp_aa` (= v_opacities_aa * opacities, the antialiased opacity's share) is added to the compensation's
+// cotangent in float32, in front of its scaling.
+template <bool AA = false>
 __device__ __forceinline__ void project_bwd_chain(
     const int i, const float *__restrict__ means3d, const float *__restrict__ viewmat,
     const float *__restrict__ projmat, const float fx, const float fy, const int img_w, const int img_h,
     const float *__restrict__ cov3d, const float *__restrict__ conics, const float *__restrict__ compensation,
     const float *__restrict__ v_xy, const float *__restrict__ v_depth, const float *__restrict__ v_conic,
-    const float *__restrict__ v_compensation, BwdChain &c) {
+    const float *__restrict__ v_compensation, BwdChain &c, const float v_comp_aa = 0.f) {
   float *const g2 = c.g2, *const g3 = c.g3, *const gm = c.gm;
   const float px = means3d[3 * i], py = means3d[3 * i + 1], pz = means3d[3 * i + 2];
   const float *P = projmat;
@@ -228,7 +243,8 @@ __device__ __forceinline__ void project_bwd_chain(
     const float comp = compensation[i];
     const float inv_det = X00 * X11 - X01 * X01;
     const float om2 = 1.f - comp * comp;
-    const float vsq = (v_compensation ? v_compensation[i] : 0.f) * 0.5f / (comp + 1e-6f);
+    const float vsq = (AA ? (v_compensation ? v_compensation[i] + v_comp_aa : v_comp_aa)
+                          : (v_compensation ? v_compensation[i] : 0.f)) * 0.5f / (comp + 1e-6f);
     g2[0] += vsq * (om2 * X00 - 0.3f * inv_det);
     g2[1] += 2.f * vsq * (om2 * X01);
     g2[2] += vsq * (om2 * X11 - 0.3f * inv_det);
@@ -275,6 +291,11 @@ __device__ __forceinline__ void project_bwd_chain(
   c.vT = vT;
 }
 
+struct BwdAA {  // (v_opacities may be v_opacities_aa itself: read before the write)
+  const float *opacities, *v_opacities_aa;
+  float *v_opacities, *v_compensation_out;
+};
+template <bool AA, typename... X>  // X: nothing, or BwdAA
 __global__ __launch_bounds__(256) void project_bwd_kernel(
     const int n, const float *__restrict__ means3d,
     const float *__restrict__ scales, const float glob_scale,
@@ -286,9 +307,17 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
     const float *__restrict__ v_depth, const float *__restrict__ v_conic,
     const float *__restrict__ v_compensation, float *__restrict__ v_cov2d,
     float *__restrict__ v_cov3d, float *__restrict__ v_mean3d,
-    float *__restrict__ v_scale, float *__restrict__ v_quat) {
+    float *__restrict__ v_scale, float *__restrict__ v_quat, const X... aa) {
+  static_assert(AA == (sizeof...(X) == 1), "project_bwd_kernel<true, BwdAA> or project_bwd_kernel<false>");
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+
+  float v_oaa = 0.f, v_comp_aa = 0.f;
+  if constexpr (AA) {
+    const BwdAA &a = (aa, ...);
+    v_oaa = a.v_opacities_aa[i];
+    v_comp_aa = v_oaa * a.opacities[i];
+  }
 
   BwdChain c;
   float *const g2 = c.g2, *const g3 = c.g3, *const gm = c.gm;
@@ -299,8 +328,8 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
   float gq[4] = {0.f, 0.f, 0.f, 0.f};
 
   if (radii[i] > 0) {
-    project_bwd_chain(i, means3d, viewmat, projmat, fx, fy, img_w, img_h, cov3d, conics, compensation, v_xy, v_depth,
-                      v_conic, v_compensation, c);
+    project_bwd_chain<AA>(i, means3d, viewmat, projmat, fx, fy, img_w, img_h, cov3d, conics, compensation, v_xy,
+                          v_depth, v_conic, v_compensation, c, v_comp_aa);
 
     // cov3d = M M^T, M = R S  (backward.cu:427-453)
     const M3 vS{g3[0], 0.5f * g3[1], 0.5f * g3[2], 0.5f * g3[1], g3[3],
@@ -344,6 +373,12 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
     for (int k = 0; k < 3; ++k) v_scale[3 * i + k] = gs[k];  // (read next by the activation backward)
 #pragma unroll
     for (int k = 0; k < 4; ++k) v_quat[4 * i + k] = gq[k];
+  }
+  if constexpr (AA) {
+    const BwdAA &a = (aa, ...);
+    a.v_opacities[i] = v_oaa * compensation[i];  // (read next by the activation backward; culled: x * 0)
+    if (a.v_compensation_out)  // the cotangent the chain took, for gsr_project_backward_pose
+      gsr_store_stream(a.v_compensation_out + i, v_compensation ? v_compensation[i] + v_comp_aa : v_comp_aa);
   }
 }
 
@@ -480,12 +515,39 @@ GSR_EXPORT int gsr_project_forward(
               "project_forward: pass both scales and quats, or neither (cov3d is then an input)");
   const int tiles_x = (int)gsr_cdiv(img_width, block_width);
   const int tiles_y = (int)gsr_cdiv(img_height, block_width);
-  hipLaunchKernelGGL(project_fwd_kernel, dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
+  hipLaunchKernelGGL((project_fwd_kernel<false>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
                      (hipStream_t)stream, num_points, means3d, scales, glob_scale, quats,
                      viewmat, projmat, fx, fy, cx, cy, (int)img_width, (int)img_height,
                      tiles_x, tiles_y, (int)block_width, clip_thresh, cov3d, xys, depths,
                      radii, conics, compensation, num_tiles_hit);
   GSR_CHECK_LAUNCH("project_forward");
+  return GSR_OK;
+}
+
+GSR_EXPORT int gsr_project_forward_aa(
+    int num_points, const float *means3d, const float *scales, float glob_scale,
+    const float *quats, const float *viewmat, const float *projmat, float fx,
+    float fy, float cx, float cy, unsigned img_height, unsigned img_width,
+    unsigned block_width, float clip_thresh, const float *opacities, float *cov3d, float *xys,
+    float *depths, int32_t *radii, float *conics, float *compensation,
+    int32_t *num_tiles_hit, float *opacities_aa, gsr_stream_t stream) {
+  GSR_REQUIRE(num_points >= 0, "project_forward_aa: num_points < 0");
+  GSR_REQUIRE(block_width >= 2 && block_width <= 16, "project_forward_aa: block_width must be in [2,16]");
+  GSR_REQUIRE(img_height > 0 && img_width > 0, "project_forward_aa: empty image");
+  if (num_points == 0) return GSR_OK;
+  GSR_REQUIRE(means3d && viewmat && projmat && cov3d && xys && depths &&
+                  radii && conics && compensation && num_tiles_hit && opacities && opacities_aa,
+              "project_forward_aa: null pointer");
+  GSR_REQUIRE((scales == nullptr) == (quats == nullptr),
+              "project_forward_aa: pass both scales and quats, or neither (cov3d is then an input)");
+  const int tiles_x = (int)gsr_cdiv(img_width, block_width);
+  const int tiles_y = (int)gsr_cdiv(img_height, block_width);
+  hipLaunchKernelGGL((project_fwd_kernel<true, FwdAA>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
+                     (hipStream_t)stream, num_points, means3d, scales, glob_scale, quats,
+                     viewmat, projmat, fx, fy, cx, cy, (int)img_width, (int)img_height,
+                     tiles_x, tiles_y, (int)block_width, clip_thresh, cov3d, xys, depths,
+                     radii, conics, compensation, num_tiles_hit, FwdAA{opacities, opacities_aa});
+  GSR_CHECK_LAUNCH("project_forward_aa");
   return GSR_OK;
 }
 
@@ -507,12 +569,43 @@ GSR_EXPORT int gsr_project_backward(
               "project_backward: null pointer");
   GSR_REQUIRE((scales == nullptr) == (quats == nullptr), "project_backward: pass both scales and quats, or neither");
   GSR_REQUIRE(scales == nullptr || (v_scale && v_quat), "project_backward: null pointer");
-  hipLaunchKernelGGL(project_bwd_kernel, dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
+  hipLaunchKernelGGL((project_bwd_kernel<false>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
                      (hipStream_t)stream, num_points, means3d, scales, glob_scale, quats,
                      viewmat, projmat, fx, fy, (int)img_width, (int)img_height, cov3d, radii,
                      conics, compensation, v_xy, v_depth, v_conic, v_compensation, v_cov2d,
                      v_cov3d, v_mean3d, v_scale, v_quat);
   GSR_CHECK_LAUNCH("project_backward");
+  return GSR_OK;
+}
+
+GSR_EXPORT int gsr_project_backward_aa(
+    int num_points, const float *means3d, const float *scales, float glob_scale,
+    const float *quats, const float *viewmat, const float *projmat, float fx,
+    float fy, float cx, float cy, unsigned img_height, unsigned img_width,
+    const float *cov3d, const int32_t *radii, const float *conics,
+    const float *compensation, const float *opacities, const float *v_xy, const float *v_depth,
+    const float *v_conic, const float *v_compensation, const float *v_opacities_aa, float *v_cov2d,
+    float *v_cov3d, float *v_mean3d, float *v_scale, float *v_quat, float *v_opacities,
+    float *v_compensation_out, gsr_stream_t stream) {
+  (void)cx;
+  (void)cy;
+  GSR_REQUIRE(num_points >= 0, "project_backward_aa: num_points < 0");
+  if (num_points == 0) return GSR_OK;
+  GSR_REQUIRE(means3d && viewmat && projmat && cov3d && radii && conics && compensation && opacities &&
+                  v_opacities_aa && v_cov2d && v_cov3d && v_mean3d && v_opacities,
+              "project_backward_aa: null pointer");
+  GSR_REQUIRE((scales == nullptr) == (quats == nullptr), "project_backward_aa: pass both scales and quats, or neither");
+  GSR_REQUIRE(scales == nullptr || (v_scale && v_quat), "project_backward_aa: null pointer");
+  // (v_opacities may be v_opacities_aa itself; nothing else may overlap what the kernel still reads)
+  GSR_REQUIRE(v_compensation_out == nullptr || v_compensation_out != v_compensation,
+              "project_backward_aa: v_compensation_out must not alias v_compensation");
+  hipLaunchKernelGGL((project_bwd_kernel<true, BwdAA>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
+                     (hipStream_t)stream, num_points, means3d, scales, glob_scale, quats,
+                     viewmat, projmat, fx, fy, (int)img_width, (int)img_height, cov3d, radii,
+                     conics, compensation, v_xy, v_depth, v_conic, v_compensation, v_cov2d,
+                     v_cov3d, v_mean3d, v_scale, v_quat,
+                     BwdAA{opacities, v_opacities_aa, v_opacities, v_compensation_out});
+  GSR_CHECK_LAUNCH("project_backward_aa");
   return GSR_OK;
 }
 

@@ -24,23 +24,33 @@ GSR_EXPORT int gsr_view_forward(const gsr_view_desc *v, gsr_stream_t stream) {
   const int n = v->num_points;
   GSR_REQUIRE(n >= 0 && v->capacity >= 1, "view_forward: bad sizes");
   GSR_REQUIRE(v->sh_degree >= 0 && v->sh_degree <= 3 && v->sh_degree_to_use <= v->sh_degree, "view_forward: SH degree");
+  GSR_REQUIRE(!v->antialiased || v->opac_aa != nullptr, "view_forward: antialiased without opac_aa");
   const int tiles_x = (v->img_width + 15) / 16, tiles_y = (v->img_height + 15) / 16;
   GSR_TRY(gsr_activate_forward(n, v->means, v->log_scales, v->raw_quats, v->logits, v->campos, v->scales, v->quats,
                                v->opac, v->dirs, stream));
-  GSR_TRY(gsr_project_forward(n, v->means, v->scales, v->glob_scale, v->quats, v->viewmat, v->projmat, v->fx, v->fy,
-                              v->cx, v->cy, (unsigned)v->img_height, (unsigned)v->img_width, 16, v->clip_thresh,
-                              v->cov3d, v->xys, v->depths, v->radii, v->conics, v->comp, v->tiles, stream));
+  // what the lists and the compositing take as the opacity: sigmoid(logits), times the compensation when antialiased
+  const float *opac = v->antialiased ? v->opac_aa : v->opac;
+  if (v->antialiased) {
+    GSR_TRY(gsr_project_forward_aa(n, v->means, v->scales, v->glob_scale, v->quats, v->viewmat, v->projmat, v->fx,
+                                   v->fy, v->cx, v->cy, (unsigned)v->img_height, (unsigned)v->img_width, 16,
+                                   v->clip_thresh, v->opac, v->cov3d, v->xys, v->depths, v->radii, v->conics, v->comp,
+                                   v->tiles, v->opac_aa, stream));
+  } else {
+    GSR_TRY(gsr_project_forward(n, v->means, v->scales, v->glob_scale, v->quats, v->viewmat, v->projmat, v->fx, v->fy,
+                                v->cx, v->cy, (unsigned)v->img_height, (unsigned)v->img_width, 16, v->clip_thresh,
+                                v->cov3d, v->xys, v->depths, v->radii, v->conics, v->comp, v->tiles, stream));
+  }
   GSR_TRY(gsr_sh_forward_split((unsigned)n, (unsigned)v->sh_degree, (unsigned)v->sh_degree_to_use, v->dirs,
                                v->features_dc, v->features_rest, v->colors, 0.5f, 1, stream));
   // lists: with counts (short lists: single-pass scatter) or without (two-level partition), as the caller
   // decided with gsr_bin_sorted_needs_counts when it sized the buffers
   if (v->counts) {
-    GSR_TRY(gsr_count_reach(n, v->xys, v->radii, v->conics, v->opac, tiles_x, tiles_y, 1, v->counts, v->reach_records,
+    GSR_TRY(gsr_count_reach(n, v->xys, v->radii, v->conics, opac, tiles_x, tiles_y, 1, v->counts, v->reach_records,
                             stream));
     GSR_TRY(gsr_depth_order(n, v->depths, v->radii, v->counts, 1, v->order, v->cum, v->sort_ws, v->sort_ws_bytes,
                             stream));
   } else {
-    GSR_TRY(gsr_reach_records_depth_order(n, v->xys, v->radii, v->conics, v->opac, v->depths, tiles_x, tiles_y,
+    GSR_TRY(gsr_reach_records_depth_order(n, v->xys, v->radii, v->conics, opac, v->depths, tiles_x, tiles_y,
                                           v->reach_records, v->order, v->sort_ws, v->sort_ws_bytes, stream));
   }
   GSR_TRY(gsr_bin_sorted_dev(n, v->capacity, v->order, v->counts ? v->cum : nullptr, v->xys, v->radii,
@@ -49,7 +59,7 @@ GSR_EXPORT int gsr_view_forward(const gsr_view_desc *v, gsr_stream_t stream) {
   GSR_REQUIRE(!v->render_depth || v->out_depth != nullptr, "view_forward: render_depth without out_depth");
   GSR_TRY(gsr_rasterize_forward_seg(tiles_x, tiles_y, (unsigned)v->img_width, (unsigned)v->img_height, v->ids,
                                     v->tile_bins, v->xys, v->conics, v->colors, v->render_depth ? v->depths : nullptr,
-                                    v->opac, v->background, 0.f, v->out_img, v->render_depth ? v->out_depth : nullptr,
+                                    opac, v->background, 0.f, v->out_img, v->render_depth ? v->out_depth : nullptr,
                                     v->final_Ts, v->final_idx, v->deep_tile_threshold, v->out_alpha, v->zero_ptr,
                                     v->zero_bytes, v->segments, v->segment_min_entries, v->seg_ws, v->seg_ws_bytes,
                                     stream));
@@ -115,16 +125,20 @@ GSR_EXPORT int gsr_view_backward(const gsr_view_desc *v, const gsr_view_grads *g
   const size_t N = (size_t)n;
   // accumulators laid out as the Python binding lays them out: v_xy | v_conic | v_colors | v_opacity [| v_extra]
   float *acc = g->accumulators;
-  GSR_REQUIRE(acc != nullptr && g->v_img != nullptr, "view_backward: null pointer");
+  GSR_REQUIRE(acc != nullptr && (g->v_img != nullptr || g->accumulators_final), "view_backward: null pointer");
   float *v_xy = acc, *v_conic = acc + 2 * N, *v_colors = acc + 5 * N, *v_opac = acc + 8 * N, *v_extra = acc + 9 * N;
   GSR_REQUIRE(!v->render_depth || g->v_depth != nullptr, "view_backward: render_depth without its cotangent");
-  GSR_TRY(gsr_rasterize_backward_seg((unsigned)v->img_height, (unsigned)v->img_width, n, v->ids, v->tile_bins, v->xys,
-                                     v->conics, v->colors, v->render_depth ? v->depths : nullptr, v->opac,
+  GSR_REQUIRE(!v->antialiased || v->opac_aa != nullptr, "view_backward: antialiased without opac_aa");
+  if (!g->accumulators_final) {  // (else: the caller's deterministic compositing backward has filled them)
+    GSR_TRY(gsr_rasterize_backward_seg((unsigned)v->img_height, (unsigned)v->img_width, n, v->ids, v->tile_bins, v->xys,
+                                     v->conics, v->colors, v->render_depth ? v->depths : nullptr,
+                                     v->antialiased ? v->opac_aa : v->opac,
                                      v->background, 0.f, v->final_Ts, v->final_idx, g->v_img,
                                      v->render_depth ? g->v_depth : nullptr, g->v_alpha, v_xy, v_conic, v_colors,
                                      v->render_depth ? v_extra : nullptr, v_opac, v->deep_tile_threshold,
                                      g->accumulators_zeroed, v->segments, v->segment_min_entries, v->seg_ws,
                                      v->seg_ws_bytes, stream));
+  }
   if (g->stats_first != nullptr)
     GSR_TRY(gsr_densify_stats_dev(n, v_xy, v->radii, g->stats_inv_size, g->stats_first, g->xys_grad_norm,
                                   g->vis_counts, g->max_2dsize, stream));
@@ -133,10 +147,18 @@ GSR_EXPORT int gsr_view_backward(const gsr_view_desc *v, const gsr_view_grads *g
   if (g->v_dc != nullptr)
     GSR_TRY(gsr_sh_backward_split((unsigned)n, (unsigned)v->sh_degree, (unsigned)v->sh_degree_to_use, v->dirs,
                                   v_colors, v->colors, g->v_dc, g->v_rest, stream));
-  GSR_TRY(gsr_project_backward(n, v->means, v->scales, v->glob_scale, v->quats, v->viewmat, v->projmat, v->fx, v->fy,
-                               v->cx, v->cy, (unsigned)v->img_height, (unsigned)v->img_width, v->cov3d, v->radii,
-                               v->conics, v->comp, v_xy, v->render_depth ? v_extra : nullptr, v_conic, nullptr,
-                               g->tmp_v_cov2d, g->tmp_v_cov3d, g->v_means, g->tmp_v_scales, g->tmp_v_quats, stream));
+  if (v->antialiased) {  // v_opac holds the cotangent of opac_aa: turned into opac's in place, its other half joins the chain
+    GSR_TRY(gsr_project_backward_aa(n, v->means, v->scales, v->glob_scale, v->quats, v->viewmat, v->projmat, v->fx,
+                                    v->fy, v->cx, v->cy, (unsigned)v->img_height, (unsigned)v->img_width, v->cov3d,
+                                    v->radii, v->conics, v->comp, v->opac, v_xy, v->render_depth ? v_extra : nullptr,
+                                    v_conic, nullptr, v_opac, g->tmp_v_cov2d, g->tmp_v_cov3d, g->v_means,
+                                    g->tmp_v_scales, g->tmp_v_quats, v_opac, nullptr, stream));
+  } else {
+    GSR_TRY(gsr_project_backward(n, v->means, v->scales, v->glob_scale, v->quats, v->viewmat, v->projmat, v->fx, v->fy,
+                                 v->cx, v->cy, (unsigned)v->img_height, (unsigned)v->img_width, v->cov3d, v->radii,
+                                 v->conics, v->comp, v_xy, v->render_depth ? v_extra : nullptr, v_conic, nullptr,
+                                 g->tmp_v_cov2d, g->tmp_v_cov3d, g->v_means, g->tmp_v_scales, g->tmp_v_quats, stream));
+  }
   GSR_TRY(gsr_activate_backward(n, v->raw_quats, v->scales, v->quats, v->opac, g->tmp_v_scales, g->tmp_v_quats, v_opac,
                                 g->v_log_scales, g->v_raw_quats, g->v_logits, stream));
   return GSR_OK;

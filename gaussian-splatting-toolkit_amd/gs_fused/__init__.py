@@ -11,4 +11,5 @@ from .activations import activate_gaussians, densify_stats_  # noqa: F401
 from .rgbd import rasterize_gaussians_rgbd  # noqa: F401
 from .refine import RefineConfig, adam_moments, refine_gaussians, refinement_branch, swap_parameters  # noqa: F401
 from .render import DensifyStats, ListCapacity, ViewSpec, render_gaussians  # noqa: F401
+from rasterizer.project_gaussians import project_gaussians_antialiased  # noqa: F401
 from .knn import KNN, initial_log_scales, k_nearest, knn, knn_mean_distance  # noqa: F401

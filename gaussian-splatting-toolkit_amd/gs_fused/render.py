@@ -8,7 +8,7 @@ features, ``project_gaussians``, ``spherical_harmonics``, ``clamp(+0.5)``,
 autograd nodes, each with its own saved-tensor bookkeeping.  ``render_gaussians`` chains
 the same native calls (include/gsraster.h) inside ONE ``torch.autograd.Function``:
 
-  forward : gsr_activate_forward -> gsr_project_forward -> gsr_sh_forward_split (+0.5,
+  forward : gsr_activate_forward -> gsr_project_forward (_aa: `ViewSpec.rasterize_mode`) -> gsr_sh_forward_split (+0.5,
             clamp) -> count_reach / depth_order / bin_sorted_dev -> gsr_rasterize_forward
             (or _rgbd: RGB + depth from one compositing pass)
   backward: gsr_rasterize_backward(_rgbd) -> gsr_sh_backward_split -> gsr_project_backward
@@ -18,7 +18,9 @@ the same native calls (include/gsraster.h) inside ONE ``torch.autograd.Function`
 Nothing in it reads device memory back: the tile lists are sized by ``capacity`` (the
 caller's job: `ListCapacity` below keeps a running estimate and checks the real count one
 view later), which makes the whole view -- forward, loss, backward -- capturable in a HIP
-graph (`ViewGraph`).  Same values as the separate ops (tests/test_gpu_render.py): images
+graph (`ViewGraph`).  Under ``rasterizer.rasterize.set_deterministic(True)`` the compositing backward is
+``gsr_rasterize_backward_det`` (a fixed summation order instead of float atomics: bit-identical gradients from run to
+run, about 1.4x its time, one more list build per view), still without a read-back.  Same values as the separate ops (tests/test_gpu_render.py): images
 bit-identical, gradients equal up to the order of the float atomics.
 fp32 CUDA tensors; 16x16 tiles; SH degree 0-3 storage (K = 1, 4, 9, 16).
 """
@@ -37,6 +39,12 @@ _f32, _i32 = torch.float32, torch.int32
 BLOCK = 16
 
 
+def _deterministic() -> bool:
+    from rasterizer.rasterize import is_deterministic  # (imported late: rasterizer.rasterize imports its siblings)
+
+    return is_deterministic()
+
+
 class _ViewDesc(C.Structure):  # gsr_view_desc (include/gsraster.h)
     _fields_ = ([(k, C.c_int) for k in ("num_points", "sh_degree", "sh_degree_to_use", "render_depth", "img_height",
                                         "img_width")]
@@ -50,7 +58,8 @@ class _ViewDesc(C.Structure):  # gsr_view_desc (include/gsraster.h)
                 + [("sort_ws_bytes", C.c_size_t), ("bin_ws", C.c_void_p), ("bin_ws_bytes", C.c_size_t)]
                 + [(k, C.c_void_p) for k in ("out_img", "out_depth", "final_Ts", "final_idx", "out_alpha", "zero_ptr")]
                 + [("zero_bytes", C.c_size_t), ("segments", C.c_int), ("segment_min_entries", C.c_int),
-                   ("seg_ws", C.c_void_p), ("seg_ws_bytes", C.c_size_t)])
+                   ("seg_ws", C.c_void_p), ("seg_ws_bytes", C.c_size_t)]
+                + [("antialiased", C.c_int), ("opac_aa", C.c_void_p)])
 
 
 class _ViewGrads(C.Structure):  # gsr_view_grads
@@ -58,7 +67,8 @@ class _ViewGrads(C.Structure):  # gsr_view_grads
                 + [("accumulators_zeroed", C.c_int), ("stats_first", C.c_void_p), ("stats_inv_size", C.c_float)]
                 + [(k, C.c_void_p) for k in ("xys_grad_norm", "vis_counts", "max_2dsize", "tmp_v_cov2d", "tmp_v_cov3d",
                                              "tmp_v_scales", "tmp_v_quats", "v_means", "v_log_scales", "v_raw_quats",
-                                             "v_logits", "v_dc", "v_rest")])
+                                             "v_logits", "v_dc", "v_rest")]
+                + [("accumulators_final", C.c_int)])
 
 
 def _segments(spec, capacity, dev):
@@ -116,6 +126,17 @@ class ViewSpec:
     render_depth: bool = False
     clip_thresh: float = 0.01
     glob_scale: float = 1.0
+    # "classic", or "antialiased": the view composites sigmoid(logits) * compensation (vanilla_gs.py:96-104,815-816),
+    # formed and differentiated inside the projection kernels (gsr_project_forward_aa / _backward_aa)
+    rasterize_mode: str = "classic"
+
+    def __post_init__(self):
+        if self.rasterize_mode not in ("classic", "antialiased"):
+            raise ValueError("Unknown rasterize_mode: %s" % self.rasterize_mode)
+
+    @property
+    def antialiased(self) -> bool:
+        return self.rasterize_mode == "antialiased"
 
     @property
     def tile_bounds(self):
@@ -158,6 +179,7 @@ class _Render(Function):
             scales, quats, opac, dirs = e((n, 3)), e((n, 4)), torch.empty_like(logits), e((n, 3))
             cov3d, xys, depths, radii = e((n, 6)), e((n, 2)), e((n,)), e((n,), _i32)
             conics, comp, tiles, colors = e((n, 3)), e((n,)), e((n,), _i32), e((n, 3))
+            opac_aa = torch.empty_like(opac) if spec.antialiased else None
             sort_b, bin_b, rec_b, lean = _workspace_bytes(n, capacity, tb)
             recs = e((n, rec_b), torch.uint8)
             counts = None if lean else e((n,), _i32)
@@ -167,7 +189,11 @@ class _Render(Function):
             img, Ts, idx, alpha = e((H, W, 3)), e((H, W)), e((H, W), _i32), e((H, W))
             dep = e((H, W)) if spec.render_depth else None
             # alpha = 1 - T and the backward's cleared accumulators come out of the compositing launch
-            acc = _C.backward_accumulators(n, 4 if spec.render_depth else 3, dev) if any(ctx.needs_input_grad[:6]) else None
+            wants_grad = any(ctx.needs_input_grad[:6])
+            # rasterizer.rasterize.set_deterministic(True): the compositing backward sums in a fixed order
+            # (gsr_rasterize_backward_det) instead of with float atomics -- see below
+            det = wants_grad and _deterministic()
+            acc = _C.backward_accumulators(n, 4 if spec.render_depth else 3, dev) if wants_grad and not det else None
             p = lambda t: None if t is None else t.data_ptr()
             seg = _segments(spec, capacity, dev)
             desc = _ViewDesc(n, degree, spec.sh_degree_to_use, int(spec.render_depth), H, W, spec.fx, spec.fy, spec.cx,
@@ -178,14 +204,29 @@ class _Render(Function):
                              p(cov3d), p(xys), p(depths), p(radii), p(conics), p(comp), p(tiles), p(colors), p(recs),
                              p(counts), p(order), p(cum), p(ids), p(bins), p(count_out), p(sort_ws), sort_b,
                              p(bin_ws), bin_b, p(img), p(dep), p(Ts), p(idx), p(alpha), p(acc),
-                             0 if acc is None else acc.numel() * 4, *_seg_fields(seg))
+                             0 if acc is None else acc.numel() * 4, *_seg_fields(seg), int(spec.antialiased),
+                             p(opac_aa))
             _call("gsr_view_forward", C.byref(desc), _stream(dev))
             del seg
+            ctx.det = None
+            if det:
+                # what gsr_rasterize_backward_det reduces along: the depth order, the scan of the per-band counts and
+                # the inverse of the scatter, from the list builder that returns it (the banded single-pass scatter;
+                # no read-back: capturable).  Its lists are the view's lists -- every builder emits a tile's entries
+                # in depth order (tests/test_gpu_kernels.py::test_list_builders_agree_on_random_shapes) -- and the
+                # backward walks them with the forward's final_Ts / final_idx.
+                op = (opac_aa if opac_aa is not None else opac).view(n, 1)
+                counts_b, recs_b = _C.count_reach(xys, radii, conics, op, tb, bands=_C.tile_bands(tb))
+                d_order, d_cum = _C.depth_order(depths, radii, counts_b)
+                d_ids, d_bins, d_slots = _C.bin_sorted(n, capacity, d_order, d_cum, xys, radii, tb, BLOCK, recs_b,
+                                                       device_sized=True, want_slots=True)
+                ctx.det = (d_order, d_cum, d_ids, d_bins, d_slots)
         ctx.spec, ctx.stats, ctx.degree = spec, stats, degree
         ctx.sh_collector = sh_collector
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(means, raw_quats, features_dc, features_rest, viewmat, projmat, background, scales, quats,
-                              opac, dirs, cov3d, xys, depths, radii, conics, comp, colors, ids, bins, Ts, idx)
+                              opac, dirs, cov3d, xys, depths, radii, conics, comp, colors, ids, bins, Ts, idx,
+                              *(() if opac_aa is None else (opac_aa,)))
         ctx.mark_non_differentiable(radii)
         ctx.accumulators = acc
         ctx.capacity = capacity
@@ -196,8 +237,9 @@ class _Render(Function):
     @staticmethod
     def backward(ctx, v_img, v_alpha, _v_radii, v_dep=None):
         (means, raw_quats, features_dc, features_rest, viewmat, projmat, background, scales, quats, opac, dirs, cov3d,
-         xys, depths, radii, conics, comp, colors, ids, bins, Ts, idx) = ctx.saved_tensors
+         xys, depths, radii, conics, comp, colors, ids, bins, Ts, idx) = ctx.saved_tensors[:22]
         spec, stats = ctx.spec, ctx.stats
+        opac_aa = ctx.saved_tensors[22] if spec.antialiased else None
         n = means.shape[0]
         dev = means.device
         H, W = spec.height, spec.width
@@ -211,7 +253,19 @@ class _Render(Function):
                 v_dep = torch.zeros(H, W, device=dev) if v_dep is None else v_dep.contiguous()
             acc, ctx.accumulators = ctx.accumulators, None
             zeroed = acc is not None
-            if acc is None:  # a second backward (retain_graph): the kernels clear their own
+            if ctx.det is not None:
+                # fixed summation order: the compositing backward from Python, its sums laid out as the accumulators,
+                # and gsr_view_backward for everything behind it
+                d_order, d_cum, d_ids, d_bins, d_slots = ctx.det
+                op = (opac_aa if opac_aa is not None else opac).view(n, 1)
+                sums = _C.rasterize_backward_det(
+                    H, W, d_ids, d_bins, xys, conics, colors, op, background, Ts, idx, v_img, v_a, d_order, d_cum,
+                    d_slots, extra=depths if spec.render_depth else None,
+                    v_output_extra=v_dep if spec.render_depth else None)
+                if spec.render_depth:  # (v_xy, v_conic, v_colors, v_extra, v_opacity) -> ... v_opacity | v_extra
+                    sums = sums[:3] + (sums[4], sums[3])
+                acc = torch.cat([t.reshape(-1) for t in sums])
+            elif acc is None:  # a second backward (retain_graph): the kernels clear their own
                 acc = _C.backward_accumulators(n, 4 if spec.render_depth else 3, dev)
             e = lambda shape: torch.empty(shape, dtype=_f32, device=dev)
             t_cov2d, t_cov3d, t_vs, t_vq = e((n, 3)), e((n, 6)), e((n, 3)), e((n, 4))
@@ -231,12 +285,12 @@ class _Render(Function):
                              p(projmat), None, p(background), p(scales), p(quats), p(opac), p(dirs), p(cov3d), p(xys),
                              p(depths), p(radii), p(conics), p(comp), None, p(colors), None, None, None, None, p(ids),
                              p(bins), None, None, 0, None, 0, None, None, p(Ts), p(idx), None, None, 0,
-                             *_seg_fields(seg))
+                             *_seg_fields(seg), int(spec.antialiased), p(opac_aa))
             grads = _ViewGrads(p(v_img), p(v_a), p(v_dep) if spec.render_depth else None, p(acc), int(zeroed),
                                p(stats.first) if use_stats else None, (1.0 / stats.max_dim) if use_stats else 0.0,
                                p(stats.xys_grad_norm) if use_stats else None, p(stats.vis_counts) if use_stats else None,
                                p(stats.max_2dsize) if use_stats else None, p(t_cov2d), p(t_cov3d), p(t_vs), p(t_vq),
-                               p(v_means), p(g_s), p(g_q), p(g_o), p(v_dc), p(v_rest))
+                               p(v_means), p(g_s), p(g_q), p(g_o), p(v_dc), p(v_rest), int(ctx.det is not None))
             _call("gsr_view_backward", C.byref(desc), C.byref(grads), _stream(dev))
             del seg
             if use_stats:

@@ -66,7 +66,7 @@ def export_mask(mask, bounding_box: bool = False, margin: int = 5) -> Tensor:
 
 def fuse_views(volume: TSDFVolume, params: Dict[str, Tensor], cameras: Sequence[Camera], background: Tensor,
                sh_degree: int, alpha_min: float = 0.5, depth_trunc: float = 10.0, masks: Optional[Sequence] = None,
-               bounding_box: bool = False, mask_margin: int = 5) -> None:
+               bounding_box: bool = False, mask_margin: int = 5, rasterize_mode: str = "classic") -> None:
     """Render RGB + depth from every camera (`render_view(render_depth=True, fused_depth=True)`: one compositing
     pass) and integrate it into `volume`.  `params`: activated `means3d`, `scales`, `quats`, `opacities`,
     `sh_coeffs` on the volume's device; `cameras`: `harness.scene.Camera` (host arrays).
@@ -75,10 +75,15 @@ def fuse_views(volume: TSDFVolume, params: Dict[str, Tensor], cameras: Sequence[
     depth is integrated only where `export_mask(mask, bounding_box, mask_margin)` keeps it.  A mask that is not its
     camera's height x width raises ValueError.  All masks are converted before the first view is rendered.
 
+    `rasterize_mode`: the mode the model was trained in (`render_view`'s; "antialiased" composites opacities *
+    compensation) -- depth and alpha of a model trained antialiased are wrong in classic mode, and so is its mesh.
+
     Everything stays on the device as float32: there is NO round trip through 8-bit colour PNG and 16-bit millimetre
     depth PNG files as in the toolkit's file-based route, hence none of their quantisation -- a deliberate difference;
     and the host is not synchronised between views."""
     dev = volume.device
+    if rasterize_mode not in ("classic", "antialiased"):
+        raise ValueError("Unknown rasterize_mode: %s" % rasterize_mode)
     keeps = None
     if masks is not None:
         if len(masks) != len(cameras):
@@ -93,7 +98,8 @@ def fuse_views(volume: TSDFVolume, params: Dict[str, Tensor], cameras: Sequence[
         for i, cam in enumerate(cameras):
             out = render_view(params["means3d"], params["scales"], params["quats"], params["opacities"],
                               params["sh_coeffs"], CameraTensors.from_numpy(cam, dev), background, sh_degree,
-                              render_depth=True, fused_depth=True, normalise_depth=False)
+                              rasterize_mode=rasterize_mode, render_depth=True, fused_depth=True,
+                              normalise_depth=False)
             depth, valid = view_depth(out["depth_acc"], out["alpha"], alpha_min)
             if keeps is not None:
                 valid = valid & keeps[i]

@@ -298,7 +298,7 @@ class GaussianParams(torch.nn.Module):
 
     def render(self, cam: CameraTensors, background, sh_degree_to_use: int, render_depth=False,
                retain_xys_grad=False, clamp_rgb=True, sh_exchange=None, caller_syncs=False, fused_depth=False,
-               normalise_depth=True):
+               normalise_depth=True, rasterize_mode="classic"):
         g = self.gauss
         if self.split_sh and g["features_dc"].is_cuda and g["features_rest"].shape[1] in (3, 8, 15):
             coeffs = (g["features_dc"], g["features_rest"])  # gs_fused.spherical_harmonics_split
@@ -316,7 +316,7 @@ class GaussianParams(torch.nn.Module):
         return render_view(g["means"], scales, quats, opac, coeffs, cam, background, sh_degree_to_use,
                            render_depth=render_depth, retain_xys_grad=retain_xys_grad, viewdirs=dirs,
                            clamp_rgb=clamp_rgb, caller_syncs=caller_syncs, fused_depth=fused_depth,
-                           normalise_depth=normalise_depth,
+                           normalise_depth=normalise_depth, rasterize_mode=rasterize_mode,
                            sh_exchange=None if sh_exchange is None else (
                                sh_exchange, ("features_dc", "features_rest"), (g["features_dc"], g["features_rest"])))
 
@@ -399,6 +399,12 @@ class TrainConfig:
     # call sequence of the models; use_graph: render -> loss -> backward replayed as one HIP graph
     fused_render: bool = False
     use_graph: bool = False
+    # `rasterize_mode` of the toolkit's models (vanilla_gs.py:96-104): "classic", or "antialiased" -- the view
+    # composites sigmoid(opacities) * compensation (:815-816).  Training views and `evaluate` alike, on all three step
+    # bodies: the separate ops through pipeline.render_view, the one-node view and its graph through
+    # `ViewSpec.rasterize_mode` (the product inside the projection kernels).  A model trained in one mode renders
+    # wrongly in the other.
+    rasterize_mode: str = "classic"
     # checkpoints in the toolkit's layout (harness/checkpoint.py; trainer.py:404-476)
     checkpoint_dir: Optional[str] = None
     save_every: int = 0                   # steps_per_save; 0 = never
@@ -561,6 +567,8 @@ def _check_config(cfg: TrainConfig) -> None:
         raise ValueError("co-gs runs through the separate ops (fused_depth = one RGB + depth compositing pass)")
     if cfg.mask not in ("none", "alpha", "box"):
         raise ValueError(f"unknown mask {cfg.mask!r}")
+    if cfg.rasterize_mode not in ("classic", "antialiased"):
+        raise ValueError("Unknown rasterize_mode: %s" % cfg.rasterize_mode)
     if cfg.camera_optimizer not in ("off", "SO3xR3", "SE3"):
         raise ValueError(f"unknown camera_optimizer {cfg.camera_optimizer!r}")
     if cfg.camera_optimizer != "off":
@@ -669,9 +677,10 @@ def evaluate(model: GaussianParams, data: TrainData, cfg: TrainConfig, cams=None
     with torch.no_grad():
         for i in np.linspace(0, cfg.num_views - 1, cfg.eval_views).astype(int):
             if cogs:
-                o = model.render(cams[i], bg, cfg.sh_degree, render_depth=True, fused_depth=bg.is_cuda)
+                o = model.render(cams[i], bg, cfg.sh_degree, render_depth=True, fused_depth=bg.is_cuda,
+                                 rasterize_mode=cfg.rasterize_mode)
             else:
-                o = model.render(cams[i], bg, cfg.sh_degree)
+                o = model.render(cams[i], bg, cfg.sh_degree, rasterize_mode=cfg.rasterize_mode)
             ps.append(psnr(o["rgb"], gt[i]))
             if masked:
                 sel = data.masks[i][..., 0] > 0.5
@@ -922,7 +931,8 @@ class FusedStep:
             while True:
                 probe = render_gaussians(g_["means"], g_["scales"], g_["quats"], g_["opacities"], g_["features_dc"],
                                          g_["features_rest"], cam.viewmat, cam.projmat, cam.campos, data.bg,
-                                         ViewSpec(cfg.height, cfg.width, cam.fx, cam.fy, cam.cx, cam.cy, cfg.sh_degree),
+                                         ViewSpec(cfg.height, cfg.width, cam.fx, cam.fy, cam.cx, cam.cy, cfg.sh_degree,
+                                                  rasterize_mode=cfg.rasterize_mode),
                                          self.caps.capacity)
                 need = int(probe["count"].item())
                 if need <= self.caps.capacity:
@@ -932,7 +942,8 @@ class FusedStep:
 
     def __call__(self, step, v, d, cam, deg, bg, target, mask):
         cfg, caps, fstats, g_ = self.cfg, self.caps, self.stats.native, self.model.gauss
-        spec = self.ViewSpec(cam.height, cam.width, cam.fx, cam.fy, cam.cx, cam.cy, deg)
+        spec = self.ViewSpec(cam.height, cam.width, cam.fx, cam.fy, cam.cx, cam.cy, deg,
+                             rasterize_mode=cfg.rasterize_mode)
         fstats.enabled = step < self.stats.stop_at
         fstats.max_dim = max(cam.width, cam.height)  # `max(self.last_size)` of after_train
         if not cfg.use_graph:
@@ -1012,6 +1023,7 @@ class SeparateStep:
         self.render_kw = dict(
             retain_xys_grad=True, clamp_rgb=not fused_clamp, sh_exchange=exchange if sh_views else None,
             caller_syncs=cfg.caller_syncs, render_depth=cogs, fused_depth=cogs and cfg.fused_depth and cuda,
+            rasterize_mode=cfg.rasterize_mode,
             normalise_depth=not (cogs and cfg.fused_depth and cfg.fused_loss and cuda and not cfg.use_est_depth))
         self.depth_after = cfg.depth_loss_start_iteration if cogs and cfg.use_depth_loss else math.inf
         self.phase_every = cfg.phase_every if cuda else 0
@@ -1181,6 +1193,8 @@ def result_record(cfg: TrainConfig, device, world: int, model, run: Dict, eval0:
                          "background_color": cfg.background_color, "caller_syncs": cfg.caller_syncs},
             "update": run["update"], "init": cfg.init, "model": cfg.model, "mask": cfg.mask,
             **({"psnr_masked_start": eval0["psnr_masked"], "psnr_masked_end": eval1["psnr_masked"]} if masked else {}),
+            # (only where it was asked for: a classic run's record stays what it was, to the byte)
+            **({"rasterize_mode": cfg.rasterize_mode} if cfg.rasterize_mode != "classic" else {}),
             "depth": ({"loss_from_step": cfg.depth_loss_start_iteration + 1 if cfg.use_depth_loss else None,
                        "one_compositing_pass": bool(cfg.fused_depth and device.type == "cuda"),
                        "mean_abs_error_start_end": [eval0["depth_err"], eval1["depth_err"]]} if cogs else None),

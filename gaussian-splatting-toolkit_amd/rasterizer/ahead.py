@@ -47,12 +47,17 @@ def _R():
 # it runs through both read-backs and next to the SH evaluation; `rasterize_gaussians` then finds its lists ready
 # (checked by provenance, the same rule the list cache uses: same storage at the same version, or the same pure op
 # on the same leaf at the same version -- never by hoping) and goes straight to compositing.  Where the opacities
-# cannot be predicted (another recipe, no previous view) only the depth order is built ahead.
+# cannot be predicted (another recipe, no previous view) only the depth order is built ahead.  One more recipe: the
+# antialiased mode's `unary(leaf) * comp[:, None]` with the compensation of the projection that queues the lists
+# (`_product_signature` below).
 # WHEN: only while the caller is seen to block.  A caller without read-backs keeps the GPU's queue full; there is no
 # idle time to fill, and lists on a second stream merely compete with the SH kernel (bench default: +-0; 200 k
 # Gaussians / dense scales, where nothing is left to overlap with: +3 %).  The signal is the caller's stream itself: if
 # it is IDLE when `rasterize_gaussians` is entered, the host was blocked (or is the bottleneck) and the GPU had
-# nothing to do -- an exponential average of that observation above 1/2 switches the side stream on.
+# nothing to do -- an exponential average of that observation above 1/2 switches the side stream on.  (A caller whose
+# opacity is the product recipe has its own multiply in flight at that moment: there the observation is whether the
+# projection, and all that was queued before it, had finished -- a weaker sign of a blocked host than an idle stream,
+# measured at one size only: 1 M Gaussians at 1080p, 0 -> 196 lists built ahead in 200 views)
 # GSR_SPECULATE=auto (default) | lists (always) | sort (depth order only, always) | 0 (never).
 _spec = {}
 _UNARY_FN = {"SigmoidBackward0": torch.sigmoid, "ExpBackward0": torch.exp, "TanhBackward0": torch.tanh,
@@ -91,7 +96,11 @@ def _note_opacity_recipe(device, opacity) -> None:
             if _producer_signature(opacity) is not None:
                 recipe = ("unary", type(fn).__name__, weakref.ref(fn.next_functions[0][0].variable), tuple(opacity.shape))
             else:
-                unknown = True
+                prod = _product_signature(opacity)
+                if prod is not None:  # the antialiased mode's line: unary(leaf) * compensation of the projection
+                    recipe = ("product", prod[1], weakref.ref(_product_leaf(opacity)), tuple(opacity.shape))
+                else:
+                    unknown = True
         except (AttributeError, IndexError, TypeError, RuntimeError) as e:  # the graph no longer looks as it did
             unknown = "raised: %r" % (e,)
     with _R()._state_lock:
@@ -122,12 +131,15 @@ def announce_opacity(opacity) -> None:
             st["recipe"] = ("same", weakref.ref(opacity))
 
 
-def speculate_lists(xys, depths, radii, conics, num_tiles_hit, img_height, img_width, block_width) -> None:
+def speculate_lists(xys, depths, radii, conics, num_tiles_hit, img_height, img_width, block_width, compensation=None,
+                    node=None) -> None:
     """(called by `project_gaussians` once the projection is queued) start this view's depth order -- and, where the
-    opacities are predictable, its tile lists -- on the side stream."""
+    opacities are predictable, its tile lists -- on the side stream.  `compensation` / `node`: that projection's
+    compensation output and its autograd node, for callers whose opacity is `unary(leaf) * compensation` (the
+    antialiased rasterize mode, vanilla_gs.py:815-816)."""
     mode = _speculation_mode()
     n = xys.size(0)
-    if mode == "0" or block_width != 16 or not xys.is_cuda or n < _spec_knobs["min_points"] or _R()._deterministic["on"] \
+    if mode == "0" or block_width != 16 or not xys.is_cuda or n < _spec_knobs["min_points"] \
             or not _R()._speculation_enabled() or os.environ.get("GSR_TILE_SORT", "")[:1] == "b":
         return
     dev = xys.device
@@ -137,6 +149,15 @@ def speculate_lists(xys, depths, radii, conics, num_tiles_hit, img_height, img_w
     with _R()._state_lock:
         st = _spec.setdefault(dev, {"stream": None, "recipe": None, "entry": None})
         recipe = st["recipe"]
+        # The product recipe's caller queues its two small kernels (the unary op, the multiply) right in front of
+        # `rasterize_gaussians`: its stream is never idle there, blocked or not.  For that caller the signal is whether
+        # the stream had drained THIS projection by then (rasterize.py, where `idle` is averaged).
+        st["projected"] = None
+        if recipe is not None and recipe[0] == "product":
+            if st.get("projected_event") is None:
+                st["projected_event"] = torch.cuda.Event()  # (one per device, recorded again every view)
+            st["projected"] = st["projected_event"]
+            st["projected"].record(torch.cuda.current_stream(dev))
         if mode == "auto":
             if st.get("idle", 1.0) <= 0.5:  # the caller keeps the queue full: nothing to hide work behind
                 stale, st["entry"], st["retired"] = st["entry"], None, None  # (an entry nobody took: let go of its tensors)
@@ -153,10 +174,18 @@ def speculate_lists(xys, depths, radii, conics, num_tiles_hit, img_height, img_w
     if st["stream"] is None:
         st["stream"] = torch.cuda.Stream(dev)
     side, main = st["stream"], torch.cuda.current_stream(dev)
-    opacity_src = osig = None
+    opacity_src = osig = product = None
     capacity = None
     if mode == "lists" and recipe is not None:
-        if recipe[0] == "same":
+        if recipe[0] == "product":
+            leaf = recipe[2]()
+            if leaf is not None and node is not None and compensation is not None and leaf.is_cuda \
+                    and leaf.numel() == n and leaf.dtype == torch.float32 and compensation.numel() == n:
+                opacity_src = ("product", leaf, recipe[1], recipe[3])
+                product = (compensation, compensation._version,
+                           ("product", recipe[1], id(leaf), leaf._version, leaf.data_ptr(), tuple(leaf.shape), id(node),
+                            COMPENSATION_OUTPUT, recipe[3]), node)
+        elif recipe[0] == "same":
             t = recipe[1]()
             if t is not None and t.is_cuda and t.numel() == n and t.dtype == torch.float32 and t.is_contiguous():
                 opacity_src = ("same", t)
@@ -167,6 +196,11 @@ def speculate_lists(xys, depths, radii, conics, num_tiles_hit, img_height, img_w
                 osig = (recipe[1], id(leaf), leaf._version, leaf.data_ptr(), tuple(leaf.shape))
         if opacity_src is not None:
             capacity = _R()._speculative_capacity(dev, n, tile_bounds, True)
+    # deterministic mode (rasterize.set_deterministic): the lists come from the builder that also returns what the
+    # fixed-order backward reduces along (below); a depth order alone is of no use to it
+    det = _R()._deterministic["on"]
+    if det and (opacity_src is None or capacity is None):
+        return
     key = _R()._geometry_key(xys, depths, radii, num_tiles_hit, img_height, img_width, block_width)
     entry = {"key": key, "keep": (xys, depths, radii, num_tiles_hit, conics)}
     if opacity_src is not None and capacity is not None:
@@ -181,12 +215,27 @@ def speculate_lists(xys, depths, radii, conics, num_tiles_hit, img_height, img_w
             if opacity_src[0] == "same":
                 opac = opacity_src[1].detach()
                 oversion = opacity_src[1]._version
+            elif opacity_src[0] == "product":  # the same float32 product of the same two tensors, element by element
+                opac = (_UNARY_FN[opacity_src[2]](opacity_src[1].detach()).reshape(-1)
+                        * compensation.detach().reshape(-1)).reshape(opacity_src[3]).contiguous()
+                oversion = opac._version
+                entry["product"] = product  # (holds the node: its identity cannot be handed to another one meanwhile)
             else:
                 opac = _UNARY_FN[opacity_src[2]](opacity_src[1].detach()).reshape(opacity_src[3]).contiguous()
                 oversion = opac._version
             pending = _R()._PendingCount(dev)
-            ids, bins = _C.rasterize_gaussians_forward(xys, depths, radii, conics, None, opac.view(n, 1), None, img_height,
-                                                       img_width, capacity, pending.buf, composite=False, checked=True)
+            if det:  # as rasterize._build_fresh builds them in this mode: per-band counts, their scan, the slots
+                counts, records = _C.count_reach(xys, radii, conics, opac.view(n, 1), tile_bounds,
+                                                 bands=_C.tile_bands(tile_bounds))
+                order, cum = _C.depth_order(depths, radii, counts)
+                _C.publish_int32(cum[-1:], pending.buf)
+                ids, bins, slots = _C.bin_sorted(n, capacity, order, cum, xys, radii, tile_bounds, block_width, records,
+                                                 device_sized=True, want_slots=True)
+                entry["aux"] = (order, cum, slots)
+            else:
+                ids, bins = _C.rasterize_gaussians_forward(xys, depths, radii, conics, None, opac.view(n, 1), None,
+                                                           img_height, img_width, capacity, pending.buf, composite=False,
+                                                           checked=True)
             entry.update(ids=ids, bins=bins, pending=pending, capacity=capacity,
                          reach=(conics.detach(), opac, conics._version, oversion, None, osig))
             _R().counters["list_builds_ahead"] += 1
@@ -202,6 +251,7 @@ def speculate_lists(xys, depths, radii, conics, num_tiles_hit, img_height, img_w
     # the NEXT view's call, and by then the caller's stream has waited for `done` (when the entry was taken, or
     # below): memory handed back after that point cannot be reused ahead of the side stream's reads.
     entry["keep"] += (opacity_src[1],) if opacity_src is not None else ()
+    entry["keep"] += (compensation,) if product is not None else ()
     with _R()._state_lock:
         old, st["entry"] = st["entry"], entry
         st["retired"] = None
@@ -217,6 +267,84 @@ def _take_speculation(device, key):
         entry, st["entry"] = st["entry"], None
         st["retired"] = entry["keep"]
     return entry
+
+
+# ---- unary(leaf) * compensation: the opacity of the antialiased rasterize mode ------------------------------------
+# `torch.sigmoid(self.opacities) * comp[:, None]` (vanilla_gs.py:815-816) is a MulBackward0 over a pure unary op on a
+# leaf and a chain of value-preserving views (`[:, None]`: an unsqueeze) of output COMPENSATION_OUTPUT of the
+# projection's node.  Same op on the same leaf at the same version, the very node of the projection that queued the
+# lists (its identity: the entry holds it), that projection's compensation at the version it had, and no broadcast --
+# the leaf, the compensation and the product have n elements each, the views in between cannot change a count, and
+# where the multiply saved its operands both of them have n elements -- = the same float32 product, element by element.
+COMPENSATION_OUTPUT = 4  # position of `compensation` among project_gaussians' outputs
+# ops that hand every element on, in order, and cannot change how many there are (no slice, no expand, no index:
+# `comp[:1][:, None]` broadcasts against the other factor and is NOT this product)
+_VALUE_VIEWS = ("UnsqueezeBackward0", "AliasBackward0", "ViewBackward0", "ReshapeAliasBackward0",
+                "UnsafeViewBackward0", "SqueezeBackward1")
+
+
+def _product_parts(t):
+    """-> (unary node, leaf, projection node, its output index) of `t = unary(leaf) * views(projection output)`, in
+    either order of the factors; None for anything else."""
+    fn = t.grad_fn
+    if fn is None or type(fn).__name__ != "MulBackward0" or t.dtype != torch.float32:
+        return None
+    nxt = fn.next_functions
+    if len(nxt) != 2 or nxt[0][0] is None or nxt[1][0] is None:
+        return None
+    for a, b in ((0, 1), (1, 0)):
+        un, (node, idx) = nxt[a][0], nxt[b]
+        if type(un).__name__ not in _PURE_UNARY:
+            continue
+        src = un.next_functions
+        if len(src) != 1 or src[0][0] is None or not hasattr(src[0][0], "variable"):
+            continue
+        leaf = src[0][0].variable
+        for _ in range(4):
+            if type(node).__name__ not in _VALUE_VIEWS:
+                break
+            if len(node.next_functions) != 1 or node.next_functions[0][0] is None:
+                return None
+            node, idx = node.next_functions[0]
+        if getattr(node, "gsr_compensation_output", None) != idx or leaf.numel() != t.numel() \
+                or leaf.dtype != torch.float32:
+            continue
+        # the operands autograd kept for the multiply's backward, where it kept them: n elements each (no broadcast)
+        if any(op is not None and op.numel() != t.numel()
+               for op in (getattr(fn, "_saved_self", None), getattr(fn, "_saved_other", None))):
+            continue
+        return un, leaf, node, idx
+    return None
+
+
+def _product_signature(t):
+    """What pins down the values of `t = unary(leaf) * compensation` (see above), or None -- also when the installed
+    torch does not expose what the proof needs: the entry is then dropped, as for any unknown producer."""
+    try:
+        parts = _product_parts(t)
+    except (AttributeError, IndexError, TypeError, RuntimeError):
+        return None
+    if parts is None:
+        return None
+    un, leaf, node, idx = parts
+    return ("product", type(un).__name__, id(leaf), leaf._version, leaf.data_ptr(), tuple(leaf.shape), id(node), idx,
+            tuple(t.shape))
+
+
+def _product_leaf(t):
+    return _product_parts(t)[1]
+
+
+def _ahead_matches(conics, opacity, ahead) -> bool:
+    """(`rasterize_gaussians`, on arrival) may the lists of `ahead` be used for these conics and this opacity?"""
+    product = ahead.get("product")
+    if product is None:
+        return _R()._same_reach_inputs(conics, opacity, ahead["reach"]) is True
+    c0, o0, cv, _, _, _ = ahead["reach"]
+    if conics.data_ptr() != c0.data_ptr() or conics._version != cv or opacity.shape != o0.shape:
+        return False
+    comp, comp_version, sig, _node = product
+    return comp._version == comp_version and comp.numel() == opacity.numel() and _product_signature(opacity) == sig
 
 
 # unary, parameter-free ops: the same op on the same leaf at the same version = the same values

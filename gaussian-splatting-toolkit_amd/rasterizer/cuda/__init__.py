@@ -170,6 +170,92 @@ def project_gaussians_backward(
     return v_cov2d, v_cov3d, v_mean3d, v_scale, v_quat
 
 
+def project_gaussians_forward_aa(
+    num_points: int, means3d: Tensor, scales: Tensor, glob_scale: float, quats: Tensor,
+    viewmat: Tensor, projmat: Tensor, fx: float, fy: float, cx: float, cy: float,
+    img_height: int, img_width: int, block_width: int, clip_thresh: float, opacities: Tensor,
+) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """-> (cov3d, xys, depths, radii, conics, compensation, num_tiles_hit, opacities_aa): ``project_gaussians_forward``
+    plus ``opacities_aa = opacities * compensation`` (one float32 multiply in the projection kernel: the opacity the
+    antialiased rasterize mode composites, vanilla_gs.py:815-816), in the shape of ``opacities`` ([N] or [N,1])."""
+    for t, nm in ((means3d, "means3d"), (scales, "scales"), (quats, "quats"), (viewmat, "viewmat"),
+                  (projmat, "projmat"), (opacities, "opacities")):
+        _check(t, nm, _f32)
+    n = int(num_points)
+    if viewmat.numel() < 12 or projmat.numel() != 16:
+        raise RuntimeError("viewmat must hold at least 3x4 and projmat 4x4 values")
+    if means3d.numel() != 3 * n or scales.numel() != 3 * n or quats.numel() != 4 * n or opacities.numel() != n:
+        raise RuntimeError("means3d/scales/quats/opacities do not match num_points")
+    dev = means3d.device
+    with _on(dev):
+        e = lambda shape, dt=_f32: torch.empty(shape, dtype=dt, device=dev)  # noqa: E731
+        xys, depths, conics, compensation, cov3d = e((n, 2)), e((n,)), e((n, 3)), e((n,)), e((n, 6))
+        radii, num_tiles_hit = e((n,), _i32), e((n,), _i32)
+        opacities_aa = e(tuple(opacities.shape))
+        _call(
+            "gsr_project_forward_aa", C.c_int(n), _ptr(means3d), _ptr(scales), _cf(glob_scale),
+            _ptr(quats), _ptr(viewmat), _ptr(projmat), _cf(fx), _cf(fy), _cf(cx), _cf(cy),
+            C.c_uint(img_height), C.c_uint(img_width), C.c_uint(block_width), _cf(clip_thresh), _ptr(opacities),
+            _ptr(cov3d), _ptr(xys), _ptr(depths), _ptr(radii), _ptr(conics), _ptr(compensation),
+            _ptr(num_tiles_hit), _ptr(opacities_aa), _stream(dev),
+        )
+    return cov3d, xys, depths, radii, conics, compensation, num_tiles_hit, opacities_aa
+
+
+def project_gaussians_backward_aa(
+    num_points: int, means3d: Tensor, scales: Tensor, glob_scale: float, quats: Tensor,
+    viewmat: Tensor, projmat: Tensor, fx: float, fy: float, cx: float, cy: float,
+    img_height: int, img_width: int, cov3d: Tensor, radii: Tensor, conics: Tensor,
+    compensation: Tensor, opacities: Tensor, v_xy: Optional[Tensor], v_depth: Optional[Tensor],
+    v_conic: Optional[Tensor], v_compensation: Optional[Tensor], v_opacities_aa: Optional[Tensor],
+    in_place: bool = False, want_v_compensation: bool = False, trusted: bool = False,
+):
+    """-> (v_cov2d, v_cov3d, v_mean3d, v_scale, v_quat, v_opacities, v_compensation_out or None):
+    ``project_gaussians_backward`` plus the product's two cotangents.  ``v_opacities = v_opacities_aa * compensation``
+    (``in_place``: written over ``v_opacities_aa``, which is returned); the compensation's cotangent inside the chain
+    is ``v_compensation + v_opacities_aa * opacities`` (float32), returned when ``want_v_compensation`` -- what
+    ``project_gaussians_backward_pose`` takes as its ``v_compensation``.  A cotangent that is None is zero."""
+    n = int(num_points)
+    dev = means3d.device
+    if not trusted:
+        for t, nm in ((means3d, "means3d"), (scales, "scales"), (quats, "quats"), (viewmat, "viewmat"),
+                      (projmat, "projmat"), (cov3d, "cov3d"), (conics, "conics"), (compensation, "compensation"),
+                      (opacities, "opacities")):
+            _check(t, nm, _f32)
+        _check(radii, "radii", _i32)
+        if opacities.numel() != n or compensation.numel() != n:
+            raise RuntimeError("opacities/compensation do not match num_points")
+    v_xy, v_depth, v_conic, v_compensation = (
+        None if t is None else _check(t.contiguous(), nm, _f32)
+        for t, nm in ((v_xy, "v_xy"), (v_depth, "v_depth"), (v_conic, "v_conic"),
+                      (v_compensation, "v_compensation"))
+    )
+    _opt = lambda t: None if t is None else _ptr(t)
+    with _on(dev):
+        e = lambda shape: torch.empty(shape, dtype=_f32, device=dev)  # noqa: E731
+        if v_opacities_aa is None:
+            v_opacities_aa = torch.zeros(tuple(opacities.shape), dtype=_f32, device=dev)
+            in_place = True
+        elif in_place:
+            _check(v_opacities_aa, "v_opacities_aa", _f32)
+        else:
+            v_opacities_aa = _check(v_opacities_aa.contiguous(), "v_opacities_aa", _f32)
+        if v_opacities_aa.numel() != n:
+            raise RuntimeError("v_opacities_aa does not match num_points")
+        v_cov2d, v_cov3d, v_mean3d, v_scale, v_quat = e((n, 3)), e((n, 6)), e((n, 3)), e((n, 3)), e((n, 4))
+        v_opacities = v_opacities_aa if in_place else e(tuple(opacities.shape))
+        v_comp_out = e((n,)) if want_v_compensation else None
+        _call(
+            "gsr_project_backward_aa", C.c_int(n), _ptr(means3d), _ptr(scales), _cf(glob_scale),
+            _ptr(quats), _ptr(viewmat), _ptr(projmat), _cf(fx), _cf(fy), _cf(cx), _cf(cy),
+            C.c_uint(img_height), C.c_uint(img_width), _ptr(cov3d), _ptr(radii), _ptr(conics),
+            _ptr(compensation), _ptr(opacities), _opt(v_xy), _opt(v_depth), _opt(v_conic), _opt(v_compensation),
+            _ptr(v_opacities_aa), _ptr(v_cov2d), _ptr(v_cov3d), _ptr(v_mean3d), _ptr(v_scale), _ptr(v_quat),
+            _ptr(v_opacities), _opt(v_comp_out), _stream(dev),
+        )
+    return v_cov2d, v_cov3d, v_mean3d, v_scale, v_quat, v_opacities, v_comp_out
+
+
 def project_gaussians_backward_pose(
     num_points: int, means3d: Tensor, viewmat: Tensor, projmat: Tensor, fx: float, fy: float,
     img_height: int, img_width: int, cov3d: Tensor, radii: Tensor, conics: Tensor, compensation: Tensor,

@@ -21,6 +21,8 @@ SYMBOLS = (
     "gsr_last_error",
     "gsr_project_forward",
     "gsr_project_backward",
+    "gsr_project_forward_aa",
+    "gsr_project_backward_aa",
     "gsr_project_backward_pose_workspace",
     "gsr_project_backward_pose",
     "gsr_sh_forward",

@@ -25,6 +25,8 @@ Conventions of the Inria API that are translated here
   * forks of the Inria rasterizer also return a depth and an alpha image:
     `forward(..., return_depth=True, return_alpha=True)` appends `depth` [1,H,W]
     (sum_i z_i alpha_i T_i, from the same compositing pass) and `alpha` [1,H,W].
+  * `antialiasing` (the settings' last field, as upstream): the opacities are multiplied by the
+    projection's compensation, inside the projection kernels (`project_gaussians_antialiased`).
 Not translated (documented differences from the Inria kernels): the Inria
 near-plane cull is z <= 0.2 (here: `clip_thresh`, default 0.01, as in the
 reference toolkit); the Inria forward clamps alpha at 0.99 (here 0.999 forward /
@@ -37,7 +39,7 @@ from torch import Tensor
 
 import rasterizer.cuda as _C
 
-from .project_gaussians import project_gaussians
+from .project_gaussians import project_gaussians, project_gaussians_antialiased
 from .rasterize import rasterize_gaussians
 from .sh import deg_from_sh, spherical_harmonics
 
@@ -55,6 +57,9 @@ class GaussianRasterizationSettings(NamedTuple):
     campos: Tensor
     prefiltered: bool = False
     debug: bool = False
+    # (last, where upstream put it: positional constructions of the older tuple keep working) the opacities are
+    # multiplied by the projection's compensation sqrt(det(cov2d - 0.3 I) / det(cov2d)) in front of the compositing
+    antialiasing: bool = False
 
 
 class _ScreenGrad(torch.autograd.Function):
@@ -121,10 +126,18 @@ class GaussianRasterizer(torch.nn.Module):
         fy = H / (2.0 * rs.tanfovy)
         viewmat = rs.viewmatrix.t().contiguous()   # back to row-major world->camera
         projmat = rs.projmatrix.t().contiguous()   # row-major P @ V
+        opac = opacities if opacities.dim() == 2 else opacities[:, None]
         if cov3D_precomp is not None:
             xys, depths, radii, conics, comp, num_tiles_hit = _ProjectPrecomputed.apply(
                 means3D.contiguous(), cov3D_precomp.contiguous(), viewmat[:3, :].contiguous(), projmat, fx, fy,
                 W / 2.0, H / 2.0, H, W, self.BLOCK_WIDTH, self.clip_thresh)
+            if rs.antialiasing:
+                opac = opac * comp[:, None]
+        elif rs.antialiasing:  # the product and its cotangents inside the projection kernels
+            quats = rotations / rotations.norm(dim=-1, keepdim=True)
+            xys, depths, radii, conics, opac, num_tiles_hit, _ = project_gaussians_antialiased(
+                means3D, scales, rs.scale_modifier, quats, viewmat[:3, :], projmat, fx, fy, W / 2.0, H / 2.0,
+                H, W, self.BLOCK_WIDTH, opac, self.clip_thresh)
         else:
             quats = rotations / rotations.norm(dim=-1, keepdim=True)
             xys, depths, radii, conics, comp, num_tiles_hit, _ = project_gaussians(
@@ -139,7 +152,6 @@ class GaussianRasterizer(torch.nn.Module):
             colors = torch.clamp_min(spherical_harmonics(use, dirs, shs) + 0.5, 0.0)
         else:
             colors = colors_precomp
-        opac = opacities if opacities.dim() == 2 else opacities[:, None]
         if return_depth:
             from gs_fused import rasterize_gaussians_rgbd  # RGB + depth from one compositing pass
 

@@ -38,7 +38,9 @@ class _ProjectGaussians(Function):
             n, means3d, scales, glob_scale, quats, *camera, block_width, clip_thresh)
         # everything this view's tile lists depend on exists now: start building them on the side stream, next to
         # whatever the caller does before it calls rasterize_gaussians (rasterize.py, "lists built ahead of time")
-        _ahead(xys, depths, radii, conics, num_tiles_hit, img_height, img_width, block_width)
+        # (the compensation and this node go along: the antialiased mode's opacity is a product with it, ahead.py)
+        ctx.gsr_compensation_output = 4
+        _ahead(xys, depths, radii, conics, num_tiles_hit, img_height, img_width, block_width, compensation, ctx)
         ctx.static = (n, glob_scale) + camera[2:]
         # Outputs nobody differentiates through (depths, compensation, cov3d in an RGB
         # pass) reach backward() as None rather than as N-sized zero tensors; the
@@ -91,3 +93,74 @@ def project_gaussians(means3d: Tensor, scales: Tensor, glob_scale: float, quats:
     tensors = [t.contiguous() for t in (means3d, scales, quats, viewmat, projmat)]
     return _ProjectGaussians.apply(tensors[0], tensors[1], glob_scale, tensors[2], tensors[3], tensors[4],
                                    fx, fy, cx, cy, img_height, img_width, block_width, clip_thresh)
+
+
+class _ProjectGaussiansAntialiased(Function):
+    """forward(means3d, scales, glob_scale, quats, viewmat, projmat, fx, fy, cx, cy, H, W, block_width, opacities,
+    clip_thresh) -> (xys, depths, radii, conics, opacities_aa, num_tiles_hit, cov3d)"""
+
+    @staticmethod
+    def forward(ctx, means3d, scales, glob_scale, quats, viewmat, projmat, fx, fy, cx, cy,
+                img_height, img_width, block_width, opacities, clip_thresh=0.01):
+        n = means3d.shape[-2]
+        if n < 1 or means3d.shape[-1] != 3:
+            raise ValueError(f"Invalid shape for means3d: {means3d.shape}")
+        camera = (viewmat, projmat, fx, fy, cx, cy, img_height, img_width)
+        cov3d, xys, depths, radii, conics, compensation, num_tiles_hit, opacities_aa = _C.project_gaussians_forward_aa(
+            n, means3d, scales, glob_scale, quats, *camera, block_width, clip_thresh, opacities)
+        # the opacity the coming rasterize_gaussians receives exists already: the lists built ahead of time are built
+        # for it (autograd provenance cannot show it -- it is this node's output)
+        from rasterizer.ahead import announce_opacity
+
+        announce_opacity(opacities_aa)
+        _ahead(xys, depths, radii, conics, num_tiles_hit, img_height, img_width, block_width)
+        ctx.static = (n, glob_scale) + camera[2:]
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(radii, num_tiles_hit)
+        ctx.save_for_backward(means3d, scales, quats, viewmat, projmat, cov3d, radii, conics, compensation, opacities)
+        return xys, depths, radii, conics, opacities_aa, num_tiles_hit, cov3d
+
+    @staticmethod
+    def backward(ctx, g_xys, g_depths, _g_radii, g_conics, g_opacities_aa, _g_tiles, _g_cov3d):
+        means3d, scales, quats, viewmat, projmat, cov3d, radii, conics, compensation, opacities = ctx.saved_tensors
+        n, glob_scale, fx, fy, cx, cy, img_height, img_width = ctx.static
+        pose = ctx.needs_input_grad[4] or ctx.needs_input_grad[5]
+        grads = _C.project_gaussians_backward_aa(
+            n, means3d, scales, glob_scale, quats, viewmat, projmat, fx, fy, cx, cy, img_height, img_width,
+            cov3d, radii, conics, compensation, opacities, g_xys, g_depths, g_conics, None, g_opacities_aa,
+            want_v_compensation=pose, trusted=True)
+        g_means, g_scales, g_quats, g_opacities, g_compensation = grads[2:]
+        g_viewmat = g_projmat = None
+        if pose:  # the pose pass takes the compensation's cotangent the chain above took
+            v_viewmat, g_projmat = _C.project_gaussians_backward_pose(
+                n, means3d, viewmat, projmat, fx, fy, img_height, img_width, cov3d, radii, conics, compensation,
+                g_xys, g_depths, g_conics, g_compensation, trusted=True)
+            if ctx.needs_input_grad[4]:
+                g_viewmat = viewmat.new_zeros(viewmat.shape)
+                g_viewmat.view(-1)[:12] = v_viewmat.view(-1)
+            if not ctx.needs_input_grad[5]:
+                g_projmat = None
+        # slots: means3d, scales, glob_scale, quats, viewmat, projmat, seven scalars, opacities, clip_thresh
+        return (g_means, g_scales, None, g_quats, g_viewmat, g_projmat) + (None,) * 7 + (g_opacities, None)
+
+
+def project_gaussians_antialiased(means3d: Tensor, scales: Tensor, glob_scale: float, quats: Tensor, viewmat: Tensor,
+                                  projmat: Tensor, fx: float, fy: float, cx: float, cy: float, img_height: int,
+                                  img_width: int, block_width: int, opacities: Tensor,
+                                  clip_thresh: float = 0.01) -> _Out:
+    """`project_gaussians` for the antialiased rasterize mode: one autograd node in place of the model's projection
+    call plus its ``opacities * comp[:, None]`` line (vanilla_gs.py:815-816).
+
+    Arguments as `project_gaussians`, plus ``opacities`` [N] or [N,1] (already sigmoid()'d).  Returns ``(xys, depths,
+    radii, conics, opacities_aa, num_tiles_hit, cov3d)``: where `project_gaussians` returns the compensation, this
+    returns ``opacities * compensation`` in the shape of ``opacities`` -- the product and both of its cotangents are
+    formed inside the projection kernels.  Differentiable w.r.t. ``means3d``, ``scales``, ``quats``, ``opacities``
+    and, where they require a gradient, ``viewmat`` and ``projmat``.  The output is announced to
+    ``rasterize_gaussians`` (`rasterizer.rasterize.announce_opacity`): tile lists built ahead of time are built for it."""
+    assert block_width > 1 and block_width <= 16, "block_width must be between 2 and 16"
+    if opacities.dim() not in (1, 2) or opacities.numel() != means3d.shape[-2]:
+        raise ValueError(f"opacities [N] or [N,1] expected, got {tuple(opacities.shape)}")
+    tensors = [t.contiguous() for t in (means3d, scales, quats, viewmat, projmat, opacities)]
+    return _ProjectGaussiansAntialiased.apply(tensors[0], tensors[1], glob_scale, tensors[2], tensors[3], tensors[4],
+                                              fx, fy, cx, cy, img_height, img_width, block_width, tensors[5],
+                                              clip_thresh)

@@ -431,8 +431,8 @@ class _PendingCount:
 
 
 # lists built ahead of time (the prediction of the caller's next opacities, the side stream): rasterizer/ahead.py
-from .ahead import (_PURE_UNARY, _UNARY_FN, _note_opacity_recipe, _producer_signature, _spec, _spec_knobs,  # noqa: E402,F401
-                    _speculation_mode, _take_speculation, announce_opacity, speculate_lists)
+from .ahead import (_PURE_UNARY, _UNARY_FN, _ahead_matches, _note_opacity_recipe, _producer_signature, _spec,  # noqa: E402,F401
+                    _spec_knobs, _speculation_mode, _take_speculation, announce_opacity, speculate_lists)
 
 def _same_reach_inputs(conics, opacity, reach):
     """Are `conics` / `opacity` the tensors the cached lists were built from?  True: the same
@@ -570,12 +570,16 @@ def build_tile_lists(xys, depths, radii, conics, num_tiles_hit, opacity, img_hei
             idle = 1.0 if torch.cuda.current_stream(xys.device).query() else 0.0
             with _state_lock:
                 st = _spec.setdefault(xys.device, {"stream": None, "recipe": None, "entry": None})
+                if idle == 0.0 and st["recipe"] is not None and st["recipe"][0] == "product" \
+                        and st.get("projected") is not None and st["projected"].query():
+                    idle = 1.0  # only this opacity's own product is in flight: the projection finished long ago
                 st["idle"] = 0.75 * st.get("idle", 1.0) + 0.25 * idle
         ahead = _take_speculation(xys.device, key)
         if ahead is not None:
             main = torch.cuda.current_stream(xys.device)
             main.wait_event(ahead["done"])
-            if "ids" in ahead and not _deterministic["on"] and _same_reach_inputs(conics, opacity, ahead["reach"]) is True:
+            # (deterministic mode takes lists that came with their `aux`, and no others)
+            if "ids" in ahead and ("aux" in ahead) == _deterministic["on"] and _ahead_matches(conics, opacity, ahead):
                 # this view's lists were built on the side stream while the caller was busy (or blocked)
                 counters["ahead_hits"] += 1
                 ids, bins, pending, capacity = ahead["ids"], ahead["bins"], ahead["pending"], ahead["capacity"]
@@ -593,7 +597,7 @@ def build_tile_lists(xys, depths, radii, conics, num_tiles_hit, opacity, img_hei
                         n, i2, b2, _ = _build_fresh(xys, depths, radii, conics, num_tiles_hit, opacity, tile_bounds,
                                                     block_width, exact, remember, speculate=False)
                         return n, i2, b2, True
-                    remember(num_intersects, ids, bins, None)
+                    remember(num_intersects, ids, bins, ahead.get("aux"))
                     return num_intersects, ids, bins, False
 
                 return None, ids, bins, finish_ahead

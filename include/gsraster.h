@@ -84,6 +84,42 @@ int gsr_project_backward(int num_points, const float *means3d,
                          float *v_cov2d, float *v_cov3d, float *v_mean3d,
                          float *v_scale, float *v_quat, gsr_stream_t stream);
 
+/* The antialiased rasterize mode (`rasterize_mode="antialiased"`, vanilla_gs.py:96-104,815-816: the model composites
+ * opacities * compensation) inside the projection: the same kernels behind a template flag, one more 4-byte stream
+ * per Gaussian each way.
+ * gsr_project_forward_aa = gsr_project_forward (same seven outputs, bit for bit) plus
+ *   opacities_aa[i] = opacities[i] * compensation[i]   one float32 multiply; a culled Gaussian gets x * 0.
+ * gsr_project_backward_aa = gsr_project_backward plus the product's two cotangents:
+ *   v_opacities[i] = v_opacities_aa[i] * compensation[i]          (may be v_opacities_aa itself: written after the read)
+ *   the compensation's cotangent inside the chain is v_compensation[i] + v_opacities_aa[i] * opacities[i] (float32;
+ *   the second term alone when v_compensation == NULL), in front of the 0.5 / (compensation + 1e-6) scaling;
+ *   v_compensation_out [n], nullable, receives that cotangent: what gsr_project_backward_pose takes as its
+ *   v_compensation when a camera requires a gradient.  It must not be v_compensation itself. */
+int gsr_project_forward_aa(int num_points, const float *means3d,
+                           const float *scales, float glob_scale,
+                           const float *quats, const float *viewmat,
+                           const float *projmat, float fx, float fy, float cx,
+                           float cy, unsigned img_height, unsigned img_width,
+                           unsigned block_width, float clip_thresh,
+                           const float *opacities, float *cov3d, float *xys,
+                           float *depths, int32_t *radii, float *conics,
+                           float *compensation, int32_t *num_tiles_hit,
+                           float *opacities_aa, gsr_stream_t stream);
+int gsr_project_backward_aa(int num_points, const float *means3d,
+                            const float *scales, float glob_scale,
+                            const float *quats, const float *viewmat,
+                            const float *projmat, float fx, float fy, float cx,
+                            float cy, unsigned img_height, unsigned img_width,
+                            const float *cov3d, const int32_t *radii,
+                            const float *conics, const float *compensation,
+                            const float *opacities, const float *v_xy,
+                            const float *v_depth, const float *v_conic,
+                            const float *v_compensation,
+                            const float *v_opacities_aa, float *v_cov2d,
+                            float *v_cov3d, float *v_mean3d, float *v_scale,
+                            float *v_quat, float *v_opacities,
+                            float *v_compensation_out, gsr_stream_t stream);
+
 /* Camera gradients of the projection (the reference has none: project_gaussians.py:156-232 returns None for both
  * matrices): v_viewmat[12] (top 3x4) and v_projmat[16], the sums over the Gaussians with radii > 0 of the terms
  * gsr_project_backward forms per Gaussian, under its conventions (no fov clamp; the compensation's cotangent scaled by
@@ -747,6 +783,11 @@ typedef struct gsr_view_desc {
   int segments, segment_min_entries;
   void *seg_ws;
   size_t seg_ws_bytes;
+  /* antialiased != 0: the view composites opac_aa [n] = opac * comp (gsr_project_forward_aa writes it; the lists,
+   * the compositing and its backward read it where they read opac, gsr_project_backward_aa turns the accumulated
+   * cotangent into opac's in place).  0: every call is the classic sequence and opac_aa may be NULL. */
+  int antialiased;
+  float *opac_aa;
 } gsr_view_desc;
 
 /* cotangents in, parameter gradients out.  accumulators: (9 + render_depth) n floats laid out
@@ -766,6 +807,10 @@ typedef struct gsr_view_grads {
   float *max_2dsize;
   float *tmp_v_cov2d, *tmp_v_cov3d, *tmp_v_scales, *tmp_v_quats;
   float *v_means, *v_log_scales, *v_raw_quats, *v_logits, *v_dc, *v_rest;
+  /* != 0: `accumulators` already hold the compositing backward's sums -- a caller that ran
+   * gsr_rasterize_backward_det on the view's lists for a fixed summation order: that launch is skipped here
+   * (v_img may then be NULL) and everything behind it runs as usual */
+  int accumulators_final;
 } gsr_view_grads;
 
 int gsr_view_forward(const gsr_view_desc *view, gsr_stream_t stream);

@@ -87,6 +87,9 @@ def parse_args(argv=None):
                          "non-zero (PNG masks must be decoded by the caller: no image library here)")
     ap.add_argument("--bounding-box", action="store_true",
                     help="with --masks: fuse inside each mask's bounding rectangle grown by 5 pixels")
+    ap.add_argument("--rasterize-mode", default="classic", choices=["classic", "antialiased"],
+                    help="the mode the model was trained in: antialiased composites opacities * compensation "
+                         "(a model trained that way gives wrong depth and alpha in classic mode)")
     a = ap.parse_args(argv)
     if a.min_component_faces < 0:
         ap.error("--min-component-faces must not be negative")
@@ -125,7 +128,7 @@ def main(argv=None):
     K = params["sh_coeffs"].shape[1]
     bg = torch.tensor(a.background, dtype=torch.float32, device=vol.device)
     fuse_views(vol, params, cams, bg, {1: 0, 4: 1, 9: 2, 16: 3}.get(K, 4), alpha_min=a.alpha_min,
-               depth_trunc=a.depth_trunc, masks=masks, bounding_box=a.bounding_box)
+               depth_trunc=a.depth_trunc, masks=masks, bounding_box=a.bounding_box, rasterize_mode=a.rasterize_mode)
     points, colors, normals = vol.extract_point_cloud()
     vertices, vcolors, triangles = vol.extract_mesh()
     os.makedirs(a.out, exist_ok=True)

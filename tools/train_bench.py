@@ -52,6 +52,10 @@ def main():
     ap.add_argument("--torch-activations", action="store_true", help="A/B: torch ops for exp/normalise/sigmoid/viewdirs")
     ap.add_argument("--cat-sh", action="store_true", help="A/B: torch.cat + spherical_harmonics instead of the split op")
     ap.add_argument("--torch-fused-adam", action="store_true", help="A/B: torch's fused Adam instead of gs_fused.FusedAdam")
+    ap.add_argument("--rasterize-mode", default="classic", choices=["classic", "antialiased"],
+                    help="TrainConfig.rasterize_mode: antialiased composites sigmoid(opacities) * compensation")
+    ap.add_argument("--caller-syncs", action="store_true",
+                    help="block the host where the unchanged models do (separate ops only)")
     args = ap.parse_args()
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -80,7 +84,8 @@ def main():
                       init_gaussians=args.init_gaussians, refine=rcfg, log_every=args.log_every,
                       fused_render=args.fused_render, use_graph=args.graph,
                       scene=args.scene, scene_scale=tuple(args.scene_scale), init=args.init, seed_knn=args.seed_knn, tex_cell=args.tex_cell, scene_objects=tuple(args.objects), cam_radius=args.cam_radius, scene_extent=args.extent,
-                      means_lr_schedule=args.means_lr_schedule, phase_every=args.phase_every)
+                      means_lr_schedule=args.means_lr_schedule, phase_every=args.phase_every,
+                      rasterize_mode=args.rasterize_mode, caller_syncs=args.caller_syncs)
     res = train(cfg, dev, rank, world)
     if world > 1:
         cs = torch.tensor([res["param_checksum"]], dtype=torch.float64, device=dev)
