@@ -106,6 +106,25 @@ __device__ __forceinline__ bool gsr_cov2d_bounds(float c0, float c1, float c2,
   return true;
 }
 
+// The oriented crop box (OrientedBox.within, gs_toolkit/data/scene_box.py:83-96).  `crop` is
+// float32[16]: [0,12) the world->box matrix A (3x4, row-major), [12,15) the half extents h, [15] unused.
+//   q_k = ((A_k0 x + A_k1 y) + A_k2 z) + A_k3,   inside <=> -h_k < q_k < h_k for k = 0, 1, 2   (strict)
+// Every product and sum is rounded on its own (no contraction, whatever flags the including file is built with), so
+// numpy.float32 arithmetic restates the rule bit for bit.  A NaN coordinate compares false: outside.  h_k = 0 keeps
+// nothing.  The 16 words are wave-uniform: read through the scalar cache.
+__device__ __forceinline__ bool gsr_crop_inside(const float *__restrict__ crop, const float x, const float y,
+                                                const float z) {
+  bool in = true;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float *a = crop + 4 * k;
+    const float q = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(a[0], x), __fmul_rn(a[1], y)), __fmul_rn(a[2], z)), a[3]);
+    const float h = crop[12 + k];
+    in = in && (q > -h) && (q < h);
+  }
+  return in;
+}
+
 // deep_tile_threshold carries one flag bit besides the threshold (include/gsraster.h, GSR_DEEP_ORDERED): the buffer
 // behind tile_bins holds the launch's JOB ORDER (raster_common.h), built by the entry point itself.
 // deep_tile_threshold's bits (include/gsraster.h): 0-21 the threshold; 22-27 GSR_DEEP_TAIL_64THS; 28 GSR_DEEP_SECOND

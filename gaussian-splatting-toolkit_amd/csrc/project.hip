@@ -68,11 +68,21 @@ struct Cam {
 
 // AA: also opacities_aa = opacities * compensation (the antialiased rasterize mode's opacity, vanilla_gs.py:815-816),
 // one float32 multiply on the compensation this lane holds anyway; everything else is the same text for both flags.
+// CROP: a Gaussian whose centre is outside the oriented crop box (gsr_crop_inside, gsr_common.h) leaves through the
+// exit of a clipped one -- radii = num_tiles_hit = 0, zeros elsewhere -- before anything but its centre was read.
 struct FwdAA {
   const float *opacities;
   float *opacities_aa;
 };
-template <bool AA, typename... X>  // X: nothing, or FwdAA (an empty pack leaves the classic kernel's signature as it was)
+struct FwdCrop {
+  const float *crop;  // float32[16], gsr_common.h
+};
+template <typename T, typename... R>
+__device__ __forceinline__ const T &fwd_first(const T &t, const R &...) {
+  return t;
+}
+// X: nothing, FwdAA, FwdCrop, or FwdAA then FwdCrop (an empty pack leaves the classic kernel's signature as it was)
+template <bool AA, bool CROP, typename... X>
 __global__ __launch_bounds__(256) void project_fwd_kernel(
     const int n, const float *__restrict__ means3d,
     const float *__restrict__ scales, const float glob_scale,
@@ -84,7 +94,8 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(
     float *__restrict__ depths, int *__restrict__ radii,
     float *__restrict__ conics, float *__restrict__ compensation,
     int *__restrict__ num_tiles_hit, const X... aa) {
-  static_assert(AA == (sizeof...(X) == 1), "project_fwd_kernel<true, FwdAA> or project_fwd_kernel<false>");
+  static_assert(sizeof...(X) == (AA ? 1 : 0) + (CROP ? 1 : 0),
+                "project_fwd_kernel<AA, CROP, [FwdAA,] [FwdCrop]>: one argument per flag, in that order");
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
 
@@ -99,7 +110,13 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(
   const float ty = V[4] * px + V[5] * py + V[6] * pz + V[7];
   const float tz = V[8] * px + V[9] * py + V[10] * pz + V[11];
 
-  if (tz > clip) {  // near-plane cull is `z <= clip` (helpers.cuh:212-219)
+  bool keep = true;
+  if constexpr (CROP) {
+    const FwdCrop &c = (aa, ...);  // (the last argument)
+    keep = gsr_crop_inside(c.crop, px, py, pz);
+  }
+
+  if (keep && tz > clip) {  // near-plane cull is `z <= clip` (helpers.cuh:212-219)
     M3 S;
     if (scales) {
       float w, x, y, z;
@@ -177,8 +194,8 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(
   gsr_store_stream(compensation + i, o_comp);
   num_tiles_hit[i] = o_tiles;
   if constexpr (AA) {
-    const FwdAA &a = (aa, ...);
-    gsr_store_stream(a.opacities_aa + i, a.opacities[i] * o_comp);  // (culled: x * 0)
+    const FwdAA &a = fwd_first(aa...);
+    gsr_store_stream(a.opacities_aa + i, a.opacities[i] * o_comp);  // (culled or cropped: x * 0)
   }
 }
 
@@ -495,6 +512,29 @@ __global__ __launch_bounds__(256) void cov2d_bounds_kernel(
   radii[i] = r;
 }
 
+// mask[i] = centre i is inside the crop box, by the projection's own rule.  count (nullable, zeroed by the entry
+// point): one ballot + popcount per wave, the four waves' counts through LDS, one integer atomic per workgroup.
+__global__ __launch_bounds__(256) void crop_mask_kernel(const int n, const float *__restrict__ means3d,
+                                                        const float *__restrict__ crop, uint8_t *__restrict__ mask,
+                                                        int *__restrict__ count) {
+  __shared__ int wave_counts[256 / GSR_WAVE];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool in = false;
+  if (i < n) {
+    const size_t o = 3 * (size_t)i;
+    in = gsr_crop_inside(crop, means3d[o], means3d[o + 1], means3d[o + 2]);
+    mask[i] = in ? 1 : 0;
+  }
+  if (count == nullptr) return;  // (uniform over the grid)
+  const unsigned long long inside = __ballot(in);
+  if (threadIdx.x % GSR_WAVE == 0) wave_counts[threadIdx.x / GSR_WAVE] = __popcll(inside);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int c = (wave_counts[0] + wave_counts[1]) + (wave_counts[2] + wave_counts[3]);
+    if (c > 0) atomicAdd(count, c);
+  }
+}
+
 }  // namespace
 
 GSR_EXPORT int gsr_project_forward(
@@ -515,7 +555,7 @@ GSR_EXPORT int gsr_project_forward(
               "project_forward: pass both scales and quats, or neither (cov3d is then an input)");
   const int tiles_x = (int)gsr_cdiv(img_width, block_width);
   const int tiles_y = (int)gsr_cdiv(img_height, block_width);
-  hipLaunchKernelGGL((project_fwd_kernel<false>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
+  hipLaunchKernelGGL((project_fwd_kernel<false, false>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
                      (hipStream_t)stream, num_points, means3d, scales, glob_scale, quats,
                      viewmat, projmat, fx, fy, cx, cy, (int)img_width, (int)img_height,
                      tiles_x, tiles_y, (int)block_width, clip_thresh, cov3d, xys, depths,
@@ -542,12 +582,62 @@ GSR_EXPORT int gsr_project_forward_aa(
               "project_forward_aa: pass both scales and quats, or neither (cov3d is then an input)");
   const int tiles_x = (int)gsr_cdiv(img_width, block_width);
   const int tiles_y = (int)gsr_cdiv(img_height, block_width);
-  hipLaunchKernelGGL((project_fwd_kernel<true, FwdAA>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
+  hipLaunchKernelGGL((project_fwd_kernel<true, false, FwdAA>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
                      (hipStream_t)stream, num_points, means3d, scales, glob_scale, quats,
                      viewmat, projmat, fx, fy, cx, cy, (int)img_width, (int)img_height,
                      tiles_x, tiles_y, (int)block_width, clip_thresh, cov3d, xys, depths,
                      radii, conics, compensation, num_tiles_hit, FwdAA{opacities, opacities_aa});
   GSR_CHECK_LAUNCH("project_forward_aa");
+  return GSR_OK;
+}
+
+GSR_EXPORT int gsr_project_forward_crop(
+    int num_points, const float *means3d, const float *scales, float glob_scale,
+    const float *quats, const float *viewmat, const float *projmat, float fx,
+    float fy, float cx, float cy, unsigned img_height, unsigned img_width,
+    unsigned block_width, float clip_thresh, const float *crop, const float *opacities, float *cov3d,
+    float *xys, float *depths, int32_t *radii, float *conics, float *compensation,
+    int32_t *num_tiles_hit, float *opacities_aa, gsr_stream_t stream) {
+  GSR_REQUIRE(num_points >= 0, "project_forward_crop: num_points < 0");
+  GSR_REQUIRE(block_width >= 2 && block_width <= 16, "project_forward_crop: block_width must be in [2,16]");
+  GSR_REQUIRE(img_height > 0 && img_width > 0, "project_forward_crop: empty image");
+  if (num_points == 0) return GSR_OK;
+  GSR_REQUIRE(means3d && viewmat && projmat && cov3d && xys && depths &&
+                  radii && conics && compensation && num_tiles_hit && crop,
+              "project_forward_crop: null pointer");
+  GSR_REQUIRE((opacities == nullptr) == (opacities_aa == nullptr),
+              "project_forward_crop: pass both opacities and opacities_aa, or neither");
+  GSR_REQUIRE((scales == nullptr) == (quats == nullptr),
+              "project_forward_crop: pass both scales and quats, or neither (cov3d is then an input)");
+  const int tiles_x = (int)gsr_cdiv(img_width, block_width);
+  const int tiles_y = (int)gsr_cdiv(img_height, block_width);
+  if (opacities) {
+    hipLaunchKernelGGL((project_fwd_kernel<true, true, FwdAA, FwdCrop>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
+                       (hipStream_t)stream, num_points, means3d, scales, glob_scale, quats,
+                       viewmat, projmat, fx, fy, cx, cy, (int)img_width, (int)img_height,
+                       tiles_x, tiles_y, (int)block_width, clip_thresh, cov3d, xys, depths,
+                       radii, conics, compensation, num_tiles_hit, FwdAA{opacities, opacities_aa}, FwdCrop{crop});
+  } else {
+    hipLaunchKernelGGL((project_fwd_kernel<false, true, FwdCrop>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
+                       (hipStream_t)stream, num_points, means3d, scales, glob_scale, quats,
+                       viewmat, projmat, fx, fy, cx, cy, (int)img_width, (int)img_height,
+                       tiles_x, tiles_y, (int)block_width, clip_thresh, cov3d, xys, depths,
+                       radii, conics, compensation, num_tiles_hit, FwdCrop{crop});
+  }
+  GSR_CHECK_LAUNCH("project_forward_crop");
+  return GSR_OK;
+}
+
+GSR_EXPORT int gsr_crop_mask(int num_points, const float *means3d, const float *crop, uint8_t *mask,
+                             int32_t *count, gsr_stream_t stream) {
+  GSR_REQUIRE(num_points >= 0, "crop_mask: num_points < 0");
+  if (count != nullptr)
+    if (int rc = gsr_zero_async(count, sizeof(int32_t), (hipStream_t)stream)) return rc;
+  if (num_points == 0) return GSR_OK;
+  GSR_REQUIRE(means3d && crop && mask, "crop_mask: null pointer");
+  hipLaunchKernelGGL(crop_mask_kernel, dim3(gsr_cdiv(num_points, 256)), dim3(256), 0, (hipStream_t)stream,
+                     num_points, means3d, crop, mask, count);
+  GSR_CHECK_LAUNCH("crop_mask");
   return GSR_OK;
 }
 

@@ -17,9 +17,9 @@ namespace {
     const int rc_ = (expr);    \
     if (rc_ != GSR_OK) return rc_; \
   } while (0)
-}  // namespace
 
-GSR_EXPORT int gsr_view_forward(const gsr_view_desc *v, gsr_stream_t stream) {
+// the body of gsr_view_forward and gsr_view_forward_crop (crop == nullptr: the sequence without a crop)
+int view_forward(const gsr_view_desc *v, const float *crop, gsr_stream_t stream) {
   GSR_REQUIRE(v != nullptr, "view_forward: null descriptor");
   const int n = v->num_points;
   GSR_REQUIRE(n >= 0 && v->capacity >= 1, "view_forward: bad sizes");
@@ -30,7 +30,13 @@ GSR_EXPORT int gsr_view_forward(const gsr_view_desc *v, gsr_stream_t stream) {
                                v->opac, v->dirs, stream));
   // what the lists and the compositing take as the opacity: sigmoid(logits), times the compensation when antialiased
   const float *opac = v->antialiased ? v->opac_aa : v->opac;
-  if (v->antialiased) {
+  if (crop) {  // the oriented crop box: outside = culled, here and in everything behind
+    GSR_TRY(gsr_project_forward_crop(n, v->means, v->scales, v->glob_scale, v->quats, v->viewmat, v->projmat, v->fx,
+                                     v->fy, v->cx, v->cy, (unsigned)v->img_height, (unsigned)v->img_width, 16,
+                                     v->clip_thresh, crop, v->antialiased ? v->opac : nullptr, v->cov3d, v->xys,
+                                     v->depths, v->radii, v->conics, v->comp, v->tiles,
+                                     v->antialiased ? v->opac_aa : nullptr, stream));
+  } else if (v->antialiased) {
     GSR_TRY(gsr_project_forward_aa(n, v->means, v->scales, v->glob_scale, v->quats, v->viewmat, v->projmat, v->fx,
                                    v->fy, v->cx, v->cy, (unsigned)v->img_height, (unsigned)v->img_width, 16,
                                    v->clip_thresh, v->opac, v->cov3d, v->xys, v->depths, v->radii, v->conics, v->comp,
@@ -64,6 +70,13 @@ GSR_EXPORT int gsr_view_forward(const gsr_view_desc *v, gsr_stream_t stream) {
                                     v->zero_bytes, v->segments, v->segment_min_entries, v->seg_ws, v->seg_ws_bytes,
                                     stream));
   return GSR_OK;
+}
+}  // namespace
+
+GSR_EXPORT int gsr_view_forward(const gsr_view_desc *v, gsr_stream_t stream) { return view_forward(v, nullptr, stream); }
+
+GSR_EXPORT int gsr_view_forward_crop(const gsr_view_desc *v, const float *crop, gsr_stream_t stream) {
+  return view_forward(v, crop, stream);
 }
 
 // gsr_rasterize_gaussians_forward -- everything `_RasterizeGaussians.forward` does on the device

@@ -12,4 +12,5 @@ from .rgbd import rasterize_gaussians_rgbd  # noqa: F401
 from .refine import RefineConfig, adam_moments, refine_gaussians, refinement_branch, swap_parameters  # noqa: F401
 from .render import DensifyStats, ListCapacity, ViewSpec, render_gaussians  # noqa: F401
 from rasterizer.project_gaussians import project_gaussians_antialiased  # noqa: F401
+from .crop import CropBox, crop_gaussians, project_gaussians_cropped  # noqa: F401
 from .knn import KNN, initial_log_scales, k_nearest, knn, knn_mean_distance  # noqa: F401

@@ -8,7 +8,7 @@ features, ``project_gaussians``, ``spherical_harmonics``, ``clamp(+0.5)``,
 autograd nodes, each with its own saved-tensor bookkeeping.  ``render_gaussians`` chains
 the same native calls (include/gsraster.h) inside ONE ``torch.autograd.Function``:
 
-  forward : gsr_activate_forward -> gsr_project_forward (_aa: `ViewSpec.rasterize_mode`) -> gsr_sh_forward_split (+0.5,
+  forward : gsr_activate_forward -> gsr_project_forward (_aa: `ViewSpec.rasterize_mode`; _crop: `crop=`) -> gsr_sh_forward_split (+0.5,
             clamp) -> count_reach / depth_order / bin_sorted_dev -> gsr_rasterize_forward
             (or _rgbd: RGB + depth from one compositing pass)
   backward: gsr_rasterize_backward(_rgbd) -> gsr_sh_backward_split -> gsr_project_backward
@@ -168,7 +168,7 @@ class _Render(Function):
     @staticmethod
     def forward(ctx, means, log_scales, raw_quats, logits, features_dc, features_rest, viewmat, projmat, campos,
                 background, spec: ViewSpec, capacity: int, count_out: Tensor, stats: Optional[DensifyStats],
-                sh_collector=None):
+                sh_collector=None, crop: Optional[Tensor] = None):
         n = means.shape[0]
         dev = means.device
         H, W = spec.height, spec.width
@@ -206,7 +206,10 @@ class _Render(Function):
                              p(bin_ws), bin_b, p(img), p(dep), p(Ts), p(idx), p(alpha), p(acc),
                              0 if acc is None else acc.numel() * 4, *_seg_fields(seg), int(spec.antialiased),
                              p(opac_aa))
-            _call("gsr_view_forward", C.byref(desc), _stream(dev))
+            if crop is None:
+                _call("gsr_view_forward", C.byref(desc), _stream(dev))
+            else:  # the crop box rides next to the descriptor (whose layout is unchanged)
+                _call("gsr_view_forward_crop", C.byref(desc), _ptr(crop), _stream(dev))
             del seg
             ctx.det = None
             if det:
@@ -301,13 +304,14 @@ class _Render(Function):
                 v_col = acc[5 * n:8 * n].view(n, 3)
                 cut = colors.view(torch.int32) == -2147483648
                 collector.offer(torch.where(cut, torch.zeros((), dtype=_f32, device=dev), v_col).contiguous())
-        return (v_means, g_s, g_q, g_o, v_dc, v_rest) + (None,) * 9
+        return (v_means, g_s, g_q, g_o, v_dc, v_rest) + (None,) * 10
 
 
 def render_gaussians(means: Tensor, log_scales: Tensor, raw_quats: Tensor, opacity_logits: Tensor,
                      features_dc: Tensor, features_rest: Tensor, viewmat: Tensor, projmat: Tensor, campos: Tensor,
                      background: Tensor, spec: ViewSpec, capacity: int, count_out: Optional[Tensor] = None,
-                     stats: Optional[DensifyStats] = None, sh_collector=None) -> Dict[str, Optional[Tensor]]:
+                     stats: Optional[DensifyStats] = None, sh_collector=None,
+                     crop: Optional[Tensor] = None) -> Dict[str, Optional[Tensor]]:
     """The raw parameters of a Gaussian model -> ``{"rgb" [H,W,3] (not clamped at 1), "alpha"
     [H,W], "depth" [H,W] or None (accumulated, not divided by alpha), "radii" [N] i32,
     "count" int32[1]}``.
@@ -319,6 +323,10 @@ def render_gaussians(means: Tensor, log_scales: Tensor, raw_quats: Tensor, opaci
     ``count_out`` may be a caller-owned int32[1] (device, or pinned host memory).    ``sh_collector`` (data parallel, `harness.parallel.GradientExchange.begin_sh_views`): the backward skips its SH
     backward, hands the colour cotangents [N,3] to ``sh_collector.offer`` and returns no gradient for
     ``features_dc`` / ``features_rest`` -- the exchange forms it from all ranks' cotangents.
+    ``crop``: float32[16] on the device (`gs_fused.CropBox.tensor`), the oriented crop box of the toolkit's
+    ``get_outputs`` (vanilla_gs.py:703-757) without its gathers: a Gaussian whose centre is outside the box is culled
+    inside the projection kernel (``radii == 0``; its gradients are zero in all six groups), N stays what it is.  An
+    empty box gives the background with alpha 0 (the reference's depth-10 image needs a read-back: `render_view`).
     """
     n = means.shape[0]
     if features_dc.shape != (n, 3) or features_rest.dim() != 3 or features_rest.shape[1] + 1 not in (1, 4, 9, 16):
@@ -329,11 +337,13 @@ def render_gaussians(means: Tensor, log_scales: Tensor, raw_quats: Tensor, opaci
         raise ValueError("capacity must be positive")
     if count_out is None:
         count_out = torch.empty(1, dtype=_i32, device=means.device)
+    if crop is not None:
+        _C._check_crop(crop, means.device)
     vm = viewmat[:3, :] if viewmat.shape[0] == 4 else viewmat
     out = _Render.apply(means.contiguous(), log_scales.contiguous(), raw_quats.contiguous(),
                         opacity_logits.contiguous(), features_dc.contiguous(), features_rest.contiguous(),
                         vm.contiguous(), projmat.contiguous(), campos.contiguous(), background.contiguous(), spec,
-                        int(capacity), count_out, stats, sh_collector)
+                        int(capacity), count_out, stats, sh_collector, crop)
     return {"rgb": out[0], "alpha": out[1], "radii": out[2], "depth": out[3] if spec.render_depth else None,
             "count": count_out}
 
@@ -381,8 +391,8 @@ class ViewGraph:
     """One HIP graph per view: render -> loss -> backward of a Gaussian model captured once
     (``torch.cuda.CUDAGraph`` = hipGraph on ROCm) and replayed for every view with the same
     `ViewSpec`, number of Gaussians and list capacity.  What varies per view -- the camera
-    matrices and position, the target image(s) -- is copied into static buffers before
-    the replay; the parameter gradients land in static ``.grad`` tensors that the optimizer
+    matrices and position, the target image(s), the crop box of a graph built with one (`set_crop`) -- is copied into
+    static buffers before the replay; the parameter gradients land in static ``.grad`` tensors that the optimizer
     then reads as usual.  The graph holds ~45 kernel nodes that are otherwise ~45 launches
     from Python through ctypes / autograd.
 
@@ -393,7 +403,7 @@ class ViewGraph:
     owner re-captures with a larger capacity (`ListCapacity`)."""
 
     def __init__(self, params: Dict[str, Tensor], spec: ViewSpec, capacity: int, loss_fn, background: Tensor,
-                 target_shapes, stats: Optional[DensifyStats] = None):
+                 target_shapes, stats: Optional[DensifyStats] = None, crop: Optional[Tensor] = None):
         self.params, self.spec, self.capacity, self.loss_fn, self.stats = params, spec, int(capacity), loss_fn, stats
         dev = params["means"].device
         self.device = dev
@@ -402,6 +412,8 @@ class ViewGraph:
         self.projmat = torch.zeros(4, 4, device=dev)
         self.campos = torch.zeros(3, device=dev)
         self.targets = tuple(torch.zeros(s, device=dev) for s in target_shapes)
+        # the crop box the captured view reads (None: the graph has no such node); `set_crop` moves it between replays
+        self.crop = None if crop is None else self._crop_values(crop).to(dev).clone()
         self.count_dev = torch.zeros(1, dtype=_i32, device=dev)
         self.count_host = torch.zeros(1, dtype=_i32).pin_memory()
         self.graph = None
@@ -415,11 +427,26 @@ class ViewGraph:
         for dst, src in zip(self.targets, targets):
             dst.copy_(src)
 
+    @staticmethod
+    def _crop_values(box) -> Tensor:
+        t = box if isinstance(box, Tensor) else box.tensor("cpu")
+        if t.dtype != _f32 or t.numel() != 16:
+            raise ValueError("a crop box is a gs_fused.CropBox or its float32[16] tensor")
+        return t.reshape(16)
+
+    def set_crop(self, box) -> None:
+        """Move the crop box (a `gs_fused.CropBox` or its float32[16]): copied into the static buffer the captured
+        view reads, ahead of the next replay -- as `_set_inputs` copies the camera; nothing is captured again.  A
+        graph built without a crop has no node that reads one: ValueError."""
+        if self.crop is None:
+            raise ValueError("this ViewGraph was built without a crop box: build one with crop= to move it later")
+        self.crop.copy_(self._crop_values(box))
+
     def _step(self):
         p = self.params
         out = render_gaussians(p["means"], p["scales"], p["quats"], p["opacities"], p["features_dc"],
                                p["features_rest"], self.viewmat, self.projmat, self.campos, self.background, self.spec,
-                               self.capacity, count_out=self.count_dev, stats=self.stats)
+                               self.capacity, count_out=self.count_dev, stats=self.stats, crop=self.crop)
         loss = self.loss_fn(out, self.targets)
         loss.backward()
         _C.publish_int32(self.count_dev, self.count_host)

@@ -8,6 +8,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
+from gs_fused.crop import CropBox
 from harness.pipeline import CameraTensors, render_view
 from harness.scene import Camera, projection_matrix
 
@@ -66,7 +67,8 @@ def export_mask(mask, bounding_box: bool = False, margin: int = 5) -> Tensor:
 
 def fuse_views(volume: TSDFVolume, params: Dict[str, Tensor], cameras: Sequence[Camera], background: Tensor,
                sh_degree: int, alpha_min: float = 0.5, depth_trunc: float = 10.0, masks: Optional[Sequence] = None,
-               bounding_box: bool = False, mask_margin: int = 5, rasterize_mode: str = "classic") -> None:
+               bounding_box: bool = False, mask_margin: int = 5, rasterize_mode: str = "classic",
+               crop_box=None) -> None:
     """Render RGB + depth from every camera (`render_view(render_depth=True, fused_depth=True)`: one compositing
     pass) and integrate it into `volume`.  `params`: activated `means3d`, `scales`, `quats`, `opacities`,
     `sh_coeffs` on the volume's device; `cameras`: `harness.scene.Camera` (host arrays).
@@ -78,12 +80,19 @@ def fuse_views(volume: TSDFVolume, params: Dict[str, Tensor], cameras: Sequence[
     `rasterize_mode`: the mode the model was trained in (`render_view`'s; "antialiased" composites opacities *
     compensation) -- depth and alpha of a model trained antialiased are wrong in classic mode, and so is its mesh.
 
+    `crop_box`: a `gs_fused.CropBox` (or its float32[16]): every view is rendered with the Gaussians whose centre the
+    box keeps (`render_view(crop=...)`: a test inside the projection kernel, nothing is gathered) -- the cut in 3-D
+    that separates an object from what stands behind it, which 2-D masks cannot.  A box that keeps nothing fuses
+    nothing.
+
     Everything stays on the device as float32: there is NO round trip through 8-bit colour PNG and 16-bit millimetre
     depth PNG files as in the toolkit's file-based route, hence none of their quantisation -- a deliberate difference;
     and the host is not synchronised between views."""
     dev = volume.device
     if rasterize_mode not in ("classic", "antialiased"):
         raise ValueError("Unknown rasterize_mode: %s" % rasterize_mode)
+    # (a CropBox goes to the device once, not once per view; anything else is `render_view`'s to check)
+    crop = crop_box.tensor(dev) if isinstance(crop_box, CropBox) else crop_box
     keeps = None
     if masks is not None:
         if len(masks) != len(cameras):
@@ -99,7 +108,7 @@ def fuse_views(volume: TSDFVolume, params: Dict[str, Tensor], cameras: Sequence[
             out = render_view(params["means3d"], params["scales"], params["quats"], params["opacities"],
                               params["sh_coeffs"], CameraTensors.from_numpy(cam, dev), background, sh_degree,
                               rasterize_mode=rasterize_mode, render_depth=True, fused_depth=True,
-                              normalise_depth=False)
+                              normalise_depth=False, crop=crop)
             depth, valid = view_depth(out["depth_acc"], out["alpha"], alpha_min)
             if keeps is not None:
                 valid = valid & keeps[i]

@@ -70,6 +70,11 @@ def render_view(
                          # (vanilla_gs.py:784) and `assert (num_tiles_hit > 0).any()` (:811); "camera": also the
                          # intrinsics read back from the device ahead of the projection (:736-740, :772-773).
                          # False: the same ops with no read-back -- what a caller that WAS changed could do
+    crop=None,  # a gs_fused.CropBox or its float32[16]: the model's crop box (vanilla_gs.py:703-757) as a test inside
+                # the projection (gs_fused.project_gaussians_cropped) instead of six gathers.  A box that keeps nothing:
+                # with `caller_syncs` the branch below returns what the reference returns for `crop_ids.sum() == 0`
+                # (:750-757: background, depth 10, accumulation 0); without a read-back nobody can know, and the image
+                # is what compositing nothing gives -- the background with alpha 0, depth 0
 ) -> Dict[str, Optional[torch.Tensor]]:
     H, W = cam.height, cam.width
     if caller_syncs == "camera" and cam.scalars is not None:
@@ -79,10 +84,23 @@ def render_view(
         sc = cam.scalars
         _ = (sc[2].item(), sc[3].item(), float(sc[4] / (2 * sc[0])), float(sc[5] / (2 * sc[1])), sc[4].item(),
              sc[5].item(), sc[0].item(), sc[1].item())
-    xys, depths, radii, conics, comp, num_tiles_hit, cov3d = project_gaussians(
-        means3d, scales, 1, quats, cam.viewmat[:3, :], cam.projmat, cam.fx, cam.fy, cam.cx, cam.cy,
-        H, W, BLOCK_WIDTH,
-    )
+    opac_aa = None
+    if crop is None:
+        xys, depths, radii, conics, comp, num_tiles_hit, cov3d = project_gaussians(
+            means3d, scales, 1, quats, cam.viewmat[:3, :], cam.projmat, cam.fx, cam.fy, cam.cx, cam.cy,
+            H, W, BLOCK_WIDTH,
+        )
+    else:
+        from gs_fused import project_gaussians_cropped
+
+        if rasterize_mode not in ("classic", "antialiased"):
+            raise ValueError("Unknown rasterize_mode: %s" % rasterize_mode)
+        res = project_gaussians_cropped(
+            means3d, scales, 1, quats, cam.viewmat[:3, :], cam.projmat, cam.fx, cam.fy, cam.cx, cam.cy,
+            H, W, BLOCK_WIDTH, crop, opacities=opacities if rasterize_mode == "antialiased" else None,
+        )
+        xys, depths, radii, conics, comp, num_tiles_hit, cov3d = res[:7]
+        opac_aa = res[7] if len(res) == 8 else None
     if caller_syncs and (radii).sum() == 0:  # vanilla_gs.py:784-794: nothing on screen, the background
         rgb = background.repeat(H, W, 1)
         # (`depth_acc`: the accumulated, un-normalised depth the fused depth loss takes together with the alpha -- zeros
@@ -121,7 +139,7 @@ def render_view(
         assert (num_tiles_hit > 0).any()  # vanilla_gs.py:811 (a second blocking read-back)
 
     if rasterize_mode == "antialiased":
-        opac = opacities * comp[:, None]
+        opac = opacities * comp[:, None] if opac_aa is None else opac_aa  # (cropped: the product left the kernel)
     elif rasterize_mode == "classic":
         opac = opacities
     else:
@@ -139,6 +157,13 @@ def render_view(
             background=background, return_alpha=True,
         )
     alpha = alpha[..., None]
+    if crop is not None:
+        # `rasterize_gaussians(return_alpha=True)` answers a view with nothing on screen with alpha = 1 (the quirk of
+        # the reference's op, rasterize.py:119-127, which its models never meet: they return before it).  With a crop
+        # the rule here is "anything on screen": alpha times 1.0 or 0.0, formed on the device (no read-back; times 1.0
+        # changes no bit).  That covers the box that keeps nothing -- accumulation 0, as the reference's models give
+        # -- and equally a box whose Gaussians are all off screen, where the route without a crop keeps the quirk
+        alpha = alpha * (num_tiles_hit > 0).any().to(alpha.dtype)
     if clamp_rgb:
         rgb = torch.clamp(rgb, max=1.0)
     if render_depth:

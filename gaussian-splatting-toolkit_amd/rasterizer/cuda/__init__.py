@@ -202,6 +202,67 @@ def project_gaussians_forward_aa(
     return cov3d, xys, depths, radii, conics, compensation, num_tiles_hit, opacities_aa
 
 
+def _check_crop(crop: Tensor, dev) -> Tensor:
+    _check(crop, "crop", _f32)
+    if crop.numel() != 16 or crop.device != dev:
+        raise RuntimeError("crop must hold 16 float32 values (gs_fused.CropBox.tensor) on the device of means3d")
+    return crop
+
+
+def project_gaussians_forward_crop(
+    num_points: int, means3d: Tensor, scales: Tensor, glob_scale: float, quats: Tensor,
+    viewmat: Tensor, projmat: Tensor, fx: float, fy: float, cx: float, cy: float,
+    img_height: int, img_width: int, block_width: int, clip_thresh: float, crop: Tensor,
+    opacities: Optional[Tensor] = None,
+):
+    """-> (cov3d, xys, depths, radii, conics, compensation, num_tiles_hit, opacities_aa or None):
+    ``project_gaussians_forward`` (with ``opacities``: ``project_gaussians_forward_aa``) for the Gaussians whose
+    centre is inside the oriented crop box ``crop`` (float32[16] on the device: the world->box matrix 3x4 and the
+    half extents, include/gsraster.h); a Gaussian outside it comes back as a culled one, zeros everywhere."""
+    for t, nm in ((means3d, "means3d"), (scales, "scales"), (quats, "quats"), (viewmat, "viewmat"),
+                  (projmat, "projmat")) + (() if opacities is None else ((opacities, "opacities"),)):
+        _check(t, nm, _f32)
+    n = int(num_points)
+    dev = means3d.device
+    _check_crop(crop, dev)
+    if viewmat.numel() < 12 or projmat.numel() != 16:
+        raise RuntimeError("viewmat must hold at least 3x4 and projmat 4x4 values")
+    if means3d.numel() != 3 * n or scales.numel() != 3 * n or quats.numel() != 4 * n \
+            or (opacities is not None and opacities.numel() != n):
+        raise RuntimeError("means3d/scales/quats/opacities do not match num_points")
+    with _on(dev):
+        e = lambda shape, dt=_f32: torch.empty(shape, dtype=dt, device=dev)  # noqa: E731
+        xys, depths, conics, compensation, cov3d = e((n, 2)), e((n,)), e((n, 3)), e((n,)), e((n, 6))
+        radii, num_tiles_hit = e((n,), _i32), e((n,), _i32)
+        opacities_aa = None if opacities is None else e(tuple(opacities.shape))
+        _call(
+            "gsr_project_forward_crop", C.c_int(n), _ptr(means3d), _ptr(scales), _cf(glob_scale),
+            _ptr(quats), _ptr(viewmat), _ptr(projmat), _cf(fx), _cf(fy), _cf(cx), _cf(cy),
+            C.c_uint(img_height), C.c_uint(img_width), C.c_uint(block_width), _cf(clip_thresh), _ptr(crop),
+            None if opacities is None else _ptr(opacities), _ptr(cov3d), _ptr(xys), _ptr(depths), _ptr(radii),
+            _ptr(conics), _ptr(compensation), _ptr(num_tiles_hit),
+            None if opacities_aa is None else _ptr(opacities_aa), _stream(dev),
+        )
+    return cov3d, xys, depths, radii, conics, compensation, num_tiles_hit, opacities_aa
+
+
+def crop_mask(means3d: Tensor, crop: Tensor, want_count: bool = True) -> Tuple[Tensor, Optional[Tensor]]:
+    """-> (mask uint8[N], count int32[1] on the device or None): which centres the crop box keeps, by the device
+    function the cropped projection uses (``gsr_crop_mask``).  Nothing is read back."""
+    _check(means3d, "means3d", _f32)
+    if means3d.dim() != 2 or means3d.shape[1] != 3:
+        raise RuntimeError("means3d [N,3] expected")
+    dev = means3d.device
+    _check_crop(crop, dev)
+    n = means3d.shape[0]
+    with _on(dev):
+        mask = torch.empty((n,), dtype=torch.uint8, device=dev)
+        count = torch.empty((1,), dtype=_i32, device=dev) if want_count else None
+        _call("gsr_crop_mask", C.c_int(n), _ptr(means3d), _ptr(crop), _ptr(mask),
+              None if count is None else _ptr(count), _stream(dev))
+    return mask, count
+
+
 def project_gaussians_backward_aa(
     num_points: int, means3d: Tensor, scales: Tensor, glob_scale: float, quats: Tensor,
     viewmat: Tensor, projmat: Tensor, fx: float, fy: float, cx: float, cy: float,

@@ -23,6 +23,8 @@ SYMBOLS = (
     "gsr_project_backward",
     "gsr_project_forward_aa",
     "gsr_project_backward_aa",
+    "gsr_project_forward_crop",
+    "gsr_crop_mask",
     "gsr_project_backward_pose_workspace",
     "gsr_project_backward_pose",
     "gsr_sh_forward",
@@ -80,6 +82,7 @@ SYMBOLS = (
     "gsr_rasterize_forward_round",
     "gsr_rasterize_backward_two",
     "gsr_view_forward",
+    "gsr_view_forward_crop",
     "gsr_rasterize_gaussians_forward",
     "gsr_view_backward",
     "gsr_rasterize_backward_rgbd",

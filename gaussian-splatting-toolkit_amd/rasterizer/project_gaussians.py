@@ -22,6 +22,43 @@ def _ahead(*args):
 _Out = Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]
 
 
+def backward_chain(static, saved, needs_viewmat, needs_projmat, g_xys, g_depths, g_conics, g_compensation,
+                    opacities=None, g_opacities_aa=None):
+    """The backward of every projection node of the package (this module's two, gs_fused.project_gaussians_cropped):
+    -> (g_means, g_scales, g_quats, g_viewmat, g_projmat, g_opacities).  `saved`: (means3d, scales, quats, viewmat,
+    projmat, cov3d, radii, conics, compensation) of the forward; `static`: (n, glob_scale, fx, fy, cx, cy, H, W).
+    With `opacities` the node also returned ``opacities * compensation``: its cotangent `g_opacities_aa` joins the
+    chain (gsr_project_backward_aa) and `g_opacities` comes back; else `g_opacities` is None.  The camera gradients
+    are a pass of their own (two more launches), run only where one of the matrices requires a gradient, on the
+    compensation's cotangent the chain took."""
+    means3d, scales, quats, viewmat, projmat, cov3d, radii, conics, compensation = saved
+    n, glob_scale, fx, fy, cx, cy, img_height, img_width = static
+    pose = needs_viewmat or needs_projmat
+    g_opacities = None
+    if opacities is None:
+        grads = _C.project_gaussians_backward(
+            n, means3d, scales, glob_scale, quats, viewmat, projmat, fx, fy, cx, cy, img_height, img_width,
+            cov3d, radii, conics, compensation, g_xys, g_depths, g_conics, g_compensation, trusted=True)
+        g_means, g_scales, g_quats = grads[2:]  # (v_cov2d, v_cov3d) come first and stay internal
+    else:
+        grads = _C.project_gaussians_backward_aa(
+            n, means3d, scales, glob_scale, quats, viewmat, projmat, fx, fy, cx, cy, img_height, img_width,
+            cov3d, radii, conics, compensation, opacities, g_xys, g_depths, g_conics, g_compensation, g_opacities_aa,
+            want_v_compensation=pose, trusted=True)
+        g_means, g_scales, g_quats, g_opacities, g_compensation = grads[2:]
+    g_viewmat = g_projmat = None
+    if pose:
+        v_viewmat, g_projmat = _C.project_gaussians_backward_pose(
+            n, means3d, viewmat, projmat, fx, fy, img_height, img_width, cov3d, radii, conics, compensation,
+            g_xys, g_depths, g_conics, g_compensation, trusted=True)
+        if needs_viewmat:  # in the shape that was passed: [3,4], or [4,4] with a zero last row
+            g_viewmat = viewmat.new_zeros(viewmat.shape)
+            g_viewmat.view(-1)[:12] = v_viewmat.view(-1)
+        if not needs_projmat:
+            g_projmat = None
+    return g_means, g_scales, g_quats, g_viewmat, g_projmat, g_opacities
+
+
 class _ProjectGaussians(Function):
     """forward(means3d, scales, glob_scale, quats, viewmat, projmat, fx, fy, cx, cy, H, W,
     block_width, clip_thresh) -> (xys, depths, radii, conics, compensation, num_tiles_hit, cov3d)"""
@@ -52,23 +89,9 @@ class _ProjectGaussians(Function):
 
     @staticmethod
     def backward(ctx, g_xys, g_depths, _g_radii, g_conics, g_compensation, _g_tiles, _g_cov3d):
-        means3d, scales, quats, viewmat, projmat, cov3d, radii, conics, compensation = ctx.saved_tensors
-        n, glob_scale, fx, fy, cx, cy, img_height, img_width = ctx.static
-        grads = _C.project_gaussians_backward(
-            n, means3d, scales, glob_scale, quats, viewmat, projmat, fx, fy, cx, cy, img_height, img_width,
-            cov3d, radii, conics, compensation, g_xys, g_depths, g_conics, g_compensation, trusted=True)
-        g_means, g_scales, g_quats = grads[2:]  # (v_cov2d, v_cov3d) come first and stay internal
-        g_viewmat = g_projmat = None
-        if ctx.needs_input_grad[4] or ctx.needs_input_grad[5]:
-            # the camera is being optimised: a pass of its own (two more launches), nothing above changes
-            v_viewmat, g_projmat = _C.project_gaussians_backward_pose(
-                n, means3d, viewmat, projmat, fx, fy, img_height, img_width, cov3d, radii, conics, compensation,
-                g_xys, g_depths, g_conics, g_compensation, trusted=True)
-            if ctx.needs_input_grad[4]:  # in the shape that was passed: [3,4], or [4,4] with a zero last row
-                g_viewmat = viewmat.new_zeros(viewmat.shape)
-                g_viewmat.view(-1)[:12] = v_viewmat.view(-1)
-            if not ctx.needs_input_grad[5]:
-                g_projmat = None
+        g_means, g_scales, g_quats, g_viewmat, g_projmat, _ = backward_chain(
+            ctx.static, ctx.saved_tensors, ctx.needs_input_grad[4], ctx.needs_input_grad[5], g_xys, g_depths, g_conics,
+            g_compensation)
         # slots: means3d, scales, glob_scale, quats, viewmat, projmat, then the eight scalar arguments
         return (g_means, g_scales, None, g_quats, g_viewmat, g_projmat) + (None,) * 8
 
@@ -122,24 +145,9 @@ class _ProjectGaussiansAntialiased(Function):
 
     @staticmethod
     def backward(ctx, g_xys, g_depths, _g_radii, g_conics, g_opacities_aa, _g_tiles, _g_cov3d):
-        means3d, scales, quats, viewmat, projmat, cov3d, radii, conics, compensation, opacities = ctx.saved_tensors
-        n, glob_scale, fx, fy, cx, cy, img_height, img_width = ctx.static
-        pose = ctx.needs_input_grad[4] or ctx.needs_input_grad[5]
-        grads = _C.project_gaussians_backward_aa(
-            n, means3d, scales, glob_scale, quats, viewmat, projmat, fx, fy, cx, cy, img_height, img_width,
-            cov3d, radii, conics, compensation, opacities, g_xys, g_depths, g_conics, None, g_opacities_aa,
-            want_v_compensation=pose, trusted=True)
-        g_means, g_scales, g_quats, g_opacities, g_compensation = grads[2:]
-        g_viewmat = g_projmat = None
-        if pose:  # the pose pass takes the compensation's cotangent the chain above took
-            v_viewmat, g_projmat = _C.project_gaussians_backward_pose(
-                n, means3d, viewmat, projmat, fx, fy, img_height, img_width, cov3d, radii, conics, compensation,
-                g_xys, g_depths, g_conics, g_compensation, trusted=True)
-            if ctx.needs_input_grad[4]:
-                g_viewmat = viewmat.new_zeros(viewmat.shape)
-                g_viewmat.view(-1)[:12] = v_viewmat.view(-1)
-            if not ctx.needs_input_grad[5]:
-                g_projmat = None
+        g_means, g_scales, g_quats, g_viewmat, g_projmat, g_opacities = backward_chain(
+            ctx.static, ctx.saved_tensors[:9], ctx.needs_input_grad[4], ctx.needs_input_grad[5], g_xys, g_depths,
+            g_conics, None, opacities=ctx.saved_tensors[9], g_opacities_aa=g_opacities_aa)
         # slots: means3d, scales, glob_scale, quats, viewmat, projmat, seven scalars, opacities, clip_thresh
         return (g_means, g_scales, None, g_quats, g_viewmat, g_projmat) + (None,) * 7 + (g_opacities, None)
 

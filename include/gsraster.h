@@ -120,6 +120,33 @@ int gsr_project_backward_aa(int num_points, const float *means3d,
                             float *v_quat, float *v_opacities,
                             float *v_compensation_out, gsr_stream_t stream);
 
+/* The oriented crop box (`OrientedBox`, gs_toolkit/data/scene_box.py:74-108; `get_outputs` gathers the Gaussians
+ * inside it before it projects, vanilla_gs.py:703-757) inside the projection: a Gaussian whose centre is outside the
+ * box is a culled Gaussian -- radii = num_tiles_hit = 0 and zeros in every other output, opacities_aa included -- so
+ * the count never changes, nothing is gathered, and gsr_project_backward(_aa) returns zeros for it as for any
+ * radii <= 0.  `crop` is float32[16] on the device:
+ *   crop[0:12]   A, the world->box matrix (the inverse of [[R, T], [0, 1]]), top 3x4, row-major
+ *   crop[12:15]  h = S / 2, the half extents;  crop[15] is not read
+ *   q_k = ((A_k0 x + A_k1 y) + A_k2 z) + A_k3, every product and sum rounded to float32 on its own;
+ *   inside <=> -h_k < q_k < h_k for k = 0, 1, 2 (strict).  A NaN coordinate is outside; h_k = 0 keeps nothing.
+ * gsr_project_forward_crop = gsr_project_forward with that test; opacities / opacities_aa both NULL, or both given:
+ *   then it is gsr_project_forward_aa with that test.  Inside Gaussians get the uncropped entry's bits.
+ * gsr_crop_mask: mask[i] = 1 / 0 by the same device function; count (nullable, int32[1] on the device) receives the
+ *   number of ones (zeroed and summed on `stream`: one integer atomic per workgroup). */
+int gsr_project_forward_crop(int num_points, const float *means3d,
+                             const float *scales, float glob_scale,
+                             const float *quats, const float *viewmat,
+                             const float *projmat, float fx, float fy, float cx,
+                             float cy, unsigned img_height, unsigned img_width,
+                             unsigned block_width, float clip_thresh,
+                             const float *crop, const float *opacities,
+                             float *cov3d, float *xys, float *depths,
+                             int32_t *radii, float *conics, float *compensation,
+                             int32_t *num_tiles_hit, float *opacities_aa,
+                             gsr_stream_t stream);
+int gsr_crop_mask(int num_points, const float *means3d, const float *crop,
+                  uint8_t *mask, int32_t *count, gsr_stream_t stream);
+
 /* Camera gradients of the projection (the reference has none: project_gaussians.py:156-232 returns None for both
  * matrices): v_viewmat[12] (top 3x4) and v_projmat[16], the sums over the Gaussians with radii > 0 of the terms
  * gsr_project_backward forms per Gaussian, under its conventions (no fov clamp; the compensation's cotangent scaled by
@@ -814,6 +841,11 @@ typedef struct gsr_view_grads {
 } gsr_view_grads;
 
 int gsr_view_forward(const gsr_view_desc *view, gsr_stream_t stream);
+/* gsr_view_forward with the oriented crop box of gsr_project_forward_crop: `crop` != NULL is float32[16] on the
+ * device, the projection is that entry and a Gaussian outside the box is culled (gsr_view_backward, unchanged, then
+ * returns zero gradients for it in every group).  crop == NULL: gsr_view_forward, call for call.  The pointer rides
+ * next to the descriptor, not in it: gsr_view_desc keeps its layout and its size. */
+int gsr_view_forward_crop(const gsr_view_desc *view, const float *crop, gsr_stream_t stream);
 
 /* ---- the forward of rasterize_gaussians as ONE call ------------------------------------------
  * What `_RasterizeGaussians.forward` runs on the device (gs_toolkit/gs_components/rasterizer/rasterize.py:89-170:

@@ -4,6 +4,7 @@
         [--voxel-length 0.01171875] [--sdf-trunc 0.06] [--depth-trunc 10] [--bounds x0 y0 z0 x1 y1 z1]
         [--capacity BLOCKS] [--alpha-min 0.5] [--background r g b] [--no-clean] [--min-component-faces 20000]
         [--gt GT.{stl,ply}] [--gt-threshold T] [--masks MASKS.npy [--bounding-box]]
+        [--obb-pos X Y Z --obb-rpy R P Y --obb-scale SX SY SZ]
 
 Renders RGB + depth from every camera of `poses.json` (the trajectory file `TSDFFusion.read_trajectory` reads), fuses
 the views into a block-sparse TSDF volume (gs_fusion) and writes `point_cloud.ply` and `mesh.ply` to DIR.  File names
@@ -21,6 +22,11 @@ non-zero (for three channels: where 0.21 R + 0.72 G + 0.07 B, truncated to 8 bit
 --bounding-box fuses inside the rectangle around each mask's non-zero pixels, grown by 5 pixels, instead (`bounding_box`).
 The toolkit reads the masks as PNG files (`Annotations/frame_%05d.png`); this project depends on no image library, so
 decoding them into the .npy array stays with the caller.
+
+--obb-pos / --obb-rpy / --obb-scale (all three, or none) cut the object out in 3-D instead: the oriented crop box of
+the toolkit's viewer (`OrientedBox.from_params`: position, roll-pitch-yaw in radians, extents).  Every view is rendered
+with the Gaussians whose centre lies inside it (gs_fused.CropBox, a test inside the projection kernel), and without
+--bounds the volume is sized by those Gaussians alone.
 """
 import argparse
 import json
@@ -32,6 +38,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "gaussian-splatting-toolkit_amd")]
 import numpy as np
 import torch
 
+from gs_fused.crop import CropBox
 from gs_fusion import TSDFVolume, clean_mesh, fuse_views, read_poses_json
 from gs_io import read_gaussian_ply, write_mesh_ply, write_point_cloud_ply
 
@@ -62,6 +69,29 @@ def load_masks(path, num_views):
     return masks
 
 
+def add_obb_arguments(ap):
+    """--obb-pos / --obb-rpy / --obb-scale, shared with tools/export_gaussians.py."""
+    ap.add_argument("--obb-pos", type=float, nargs=3, metavar=("X", "Y", "Z"), help="crop box: centre")
+    ap.add_argument("--obb-rpy", type=float, nargs=3, metavar=("R", "P", "Y"),
+                    help="crop box: roll, pitch, yaw in radians (R = Rz(yaw) Ry(pitch) Rx(roll))")
+    ap.add_argument("--obb-scale", type=float, nargs=3, metavar=("SX", "SY", "SZ"), help="crop box: extents")
+
+
+def obb_from_args(ap, a):
+    """-> CropBox or None; the three options come together, extents must not be negative."""
+    given = [v is not None for v in (a.obb_pos, a.obb_rpy, a.obb_scale)]
+    if not any(given):
+        return None
+    if not all(given):
+        ap.error("--obb-pos, --obb-rpy and --obb-scale go together")
+    if min(a.obb_scale) < 0:
+        ap.error("--obb-scale must not be negative")
+    try:
+        return CropBox.from_params(a.obb_pos, a.obb_rpy, a.obb_scale)
+    except ValueError as e:
+        ap.error(str(e))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--ply", required=True)
@@ -90,7 +120,9 @@ def parse_args(argv=None):
     ap.add_argument("--rasterize-mode", default="classic", choices=["classic", "antialiased"],
                     help="the mode the model was trained in: antialiased composites opacities * compensation "
                          "(a model trained that way gives wrong depth and alpha in classic mode)")
+    add_obb_arguments(ap)
     a = ap.parse_args(argv)
+    a.crop_box = obb_from_args(ap, a)
     if a.min_component_faces < 0:
         ap.error("--min-component-faces must not be negative")
     if a.gt_threshold is not None and not a.gt_threshold >= 0:
@@ -118,7 +150,13 @@ def main(argv=None):
     if a.bounds:
         lo, hi = np.asarray(a.bounds[:3]), np.asarray(a.bounds[3:])
     else:
-        lo, hi = default_bounds(raw["means"], a.sdf_trunc)
+        means = raw["means"]
+        if a.crop_box is not None:
+            inside = a.crop_box.within(torch.from_numpy(np.ascontiguousarray(means, np.float32))).numpy()
+            if not inside.any():
+                raise SystemExit("export_tsdf: the crop box keeps no Gaussian")
+            means = means[inside]
+        lo, hi = default_bounds(means, a.sdf_trunc)
     if not (hi > lo).all():
         raise SystemExit("export_tsdf: empty bounds")
     blocks = np.maximum(1, np.ceil((hi - lo) / (8.0 * a.voxel_length) - 1e-9)).astype(int)
@@ -128,7 +166,8 @@ def main(argv=None):
     K = params["sh_coeffs"].shape[1]
     bg = torch.tensor(a.background, dtype=torch.float32, device=vol.device)
     fuse_views(vol, params, cams, bg, {1: 0, 4: 1, 9: 2, 16: 3}.get(K, 4), alpha_min=a.alpha_min,
-               depth_trunc=a.depth_trunc, masks=masks, bounding_box=a.bounding_box, rasterize_mode=a.rasterize_mode)
+               depth_trunc=a.depth_trunc, masks=masks, bounding_box=a.bounding_box, rasterize_mode=a.rasterize_mode,
+               crop_box=a.crop_box)
     points, colors, normals = vol.extract_point_cloud()
     vertices, vcolors, triangles = vol.extract_mesh()
     os.makedirs(a.out, exist_ok=True)
@@ -140,6 +179,8 @@ def main(argv=None):
                "vertices": int(vertices.shape[0]), "triangles": int(triangles.shape[0]), "out": a.out}
     if masks is not None:
         summary["masks"] = "bounding box" if a.bounding_box else "mask"
+    if a.crop_box is not None:
+        summary["crop_box"] = {"pos": list(a.obb_pos), "rpy": list(a.obb_rpy), "scale": list(a.obb_scale)}
     if a.clean:
         summary.update(write_cleaned(a.out, vertices, vcolors, triangles, a.min_component_faces))
     if a.gt:
