@@ -14,3 +14,4 @@ from .render import DensifyStats, ListCapacity, ViewSpec, render_gaussians  # no
 from rasterizer.project_gaussians import project_gaussians_antialiased  # noqa: F401
 from .crop import CropBox, crop_gaussians, project_gaussians_cropped  # noqa: F401
 from .knn import KNN, initial_log_scales, k_nearest, knn, knn_mean_distance  # noqa: F401
+from .target import DeferredTarget, ImageCache, plane_from_int, target_from_u8  # noqa: F401

@@ -392,7 +392,7 @@ class ViewGraph:
     (``torch.cuda.CUDAGraph`` = hipGraph on ROCm) and replayed for every view with the same
     `ViewSpec`, number of Gaussians and list capacity.  What varies per view -- the camera
     matrices and position, the target image(s), the crop box of a graph built with one (`set_crop`) -- is copied into
-    static buffers before the replay; the parameter gradients land in static ``.grad`` tensors that the optimizer
+    static buffers before the replay (a target may be a `gs_fused.DeferredTarget`, which writes its buffer itself); the parameter gradients land in static ``.grad`` tensors that the optimizer
     then reads as usual.  The graph holds ~45 kernel nodes that are otherwise ~45 launches
     from Python through ctypes / autograd.
 
@@ -425,7 +425,10 @@ class ViewGraph:
         self.projmat.copy_(projmat)
         self.campos.copy_(campos)
         for dst, src in zip(self.targets, targets):
-            dst.copy_(src)
+            if hasattr(src, "write"):  # a gs_fused.DeferredTarget: its kernel writes the static tensor itself
+                src.write(dst)
+            else:
+                dst.copy_(src)
 
     @staticmethod
     def _crop_values(box) -> Tensor:

@@ -28,7 +28,7 @@ import gc
 import math
 import os
 import time
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -516,6 +516,29 @@ class TrainConfig:
     # the ground truth stays rendered from the true poses, so a synthetic run has something to recover
     pose_noise: tuple = (0.0, 0.0)
     pose_noise_seed: int = 20241019
+    # a dataset directory (or its transforms.json) instead of the hidden synthetic scene: read by
+    # gs_io.dataset.load_dataset with the `dataset_*` fields below (the dataparser's config,
+    # gs_toolkit_dataparser.py:36-67), uploaded as integers into a gs_fused.ImageCache (uint8 images, uint8 masks,
+    # uint16 / uint8 depth: DESIGN.md section 4.15) and turned into each step's target by ONE kernel
+    # (gs_fused.target_from_u8).  `num_views`, `width` and `height` then come from the dataset; the model starts from
+    # the seed cloud as `populate_modules` does (vanilla_gs.py:126-174), or -- no cloud, or `dataset_random_init` --
+    # from `dataset_num_random` uniform points in a cube of edge `dataset_random_scale`; `scene`, `init`, `mask`,
+    # `pose_noise` and `fused_target` do not apply (masks and depth are used when the dataset has them).  One GPU.
+    # After training the `dataset_eval_split` views are rendered and measured (`evaluate_dataset`; None: skipped).
+    dataset: Optional[str] = None
+    dataset_scale_factor: float = 1.0
+    dataset_downscale_factor: Optional[int] = None
+    dataset_orientation_method: str = "up"
+    dataset_center_method: str = "poses"
+    dataset_auto_scale_poses: bool = False
+    dataset_eval_mode: str = "fraction"
+    dataset_train_split_fraction: float = 0.9
+    dataset_eval_interval: int = 8
+    dataset_depth_unit_scale_factor: float = 1e-3
+    dataset_random_init: bool = False
+    dataset_num_random: int = 50000
+    dataset_random_scale: float = 10.0
+    dataset_eval_split: Optional[str] = "val"
 
 
 def quantise_depth_mm(depth: torch.Tensor) -> torch.Tensor:
@@ -617,6 +640,70 @@ class TrainData:
     masks: Optional[List[torch.Tensor]]       # TrainConfig.mask: [H,W,1] per view
     cams_np: Optional[list] = None            # the training cameras as given (scene.Camera; `pose_noise` applied)
     true_cams_np: Optional[list] = None       # the cameras the ground truth was rendered from
+    cache: Optional[object] = None            # `TrainConfig.dataset`: the gs_fused.ImageCache `gt` / `gt_depth` / `masks` read
+    dataset: Optional[object] = None          # ... and the gs_io.dataset.Dataset it was filled from (the training split)
+
+
+class _CacheViews:
+    """`TrainData.gt` / `gt_depth` / `masks` of a dataset: indexed like the lists of tensors `make_data` renders, formed
+    from the integer cache when asked for (full size)."""
+
+    def __init__(self, n: int, get):
+        self.n, self.get = n, get
+
+    def __len__(self) -> int:
+        return self.n
+
+    def __getitem__(self, v: int) -> torch.Tensor:
+        return self.get(int(v))
+
+
+def dataset_config(cfg: TrainConfig) -> Dict:
+    """The keyword arguments of gs_io.dataset.load_dataset from the `dataset_*` fields."""
+    return dict(scale_factor=cfg.dataset_scale_factor, downscale_factor=cfg.dataset_downscale_factor,
+                orientation_method=cfg.dataset_orientation_method, center_method=cfg.dataset_center_method,
+                auto_scale_poses=cfg.dataset_auto_scale_poses, eval_mode=cfg.dataset_eval_mode,
+                train_split_fraction=cfg.dataset_train_split_fraction, eval_interval=cfg.dataset_eval_interval,
+                depth_unit_scale_factor=cfg.dataset_depth_unit_scale_factor)
+
+
+def upload_dataset(ds, device):
+    """A split's files -> gs_fused.ImageCache: every file read into its integer dtype and copied to the device once
+    (pinned memory, one `copy_` per file, no float copy on either side)."""
+    from gs_fused import ImageCache
+
+    n = len(ds)
+    return ImageCache([ds.image(i) for i in range(n)],
+                      None if ds.mask_filenames is None else [ds.mask(i) for i in range(n)],
+                      None if ds.depth_filenames is None else [ds.depth(i) for i in range(n)],
+                      depth_unit=ds.depth_unit, device=device)
+
+
+def _schedule_factors(cfg: TrainConfig) -> List[int]:
+    return sorted({downscale_factor(s_, cfg.num_downscales, cfg.resolution_schedule)
+                   for s_ in range(0, max(cfg.iters, 1), max(min(cfg.resolution_schedule, cfg.iters), 1))} | {1})
+
+
+def make_dataset_data(cfg: TrainConfig, device) -> TrainData:
+    """`make_data` for `TrainConfig.dataset`: the training split's cameras, and its images, masks and depth as an
+    integer cache on the device."""
+    from gs_io.dataset import load_dataset
+
+    ds = load_dataset(cfg.dataset, "train", **dataset_config(cfg))
+    if len(ds) == 0:
+        raise ValueError(f"dataset {cfg.dataset!r}: the training split is empty")
+    if cfg.model == "co-gs" and ds.depth_filenames is None:
+        raise ValueError(f"dataset {cfg.dataset!r}: model 'co-gs' needs depth_path in every frame")
+    cache = upload_dataset(ds, device)
+    cams_np = ds.cameras
+    factors = _schedule_factors(cfg)
+    cams_by_d = {d: [CameraTensors.from_numpy(rescale_camera(c, d), device) for c in cams_np] for d in factors}
+    bg = torch.tensor(S.BACKGROUND, device=device)
+    n = len(ds)
+    return TrainData(factors, cams_by_d, bg, _CacheViews(n, lambda v: cache.target(v, 1, bg)), None,
+                     None if cache.depths is None else _CacheViews(n, lambda v: cache.depth(v, 1)),
+                     None if cache.masks is None else _CacheViews(n, lambda v: cache.mask(v, 1)),
+                     cams_np, None, cache, ds)
 
 
 def make_data(cfg: TrainConfig, device) -> TrainData:
@@ -628,8 +715,7 @@ def make_data(cfg: TrainConfig, device) -> TrainData:
         cams_np = perturb_cameras(true_np, cfg.pose_noise[0], cfg.pose_noise[1], cfg.pose_noise_seed)
         cams = [CameraTensors.from_numpy(c, device) for c in cams_np]
     # the coarse-to-fine schedule's cameras, one set per downscale factor
-    factors = sorted({downscale_factor(s_, cfg.num_downscales, cfg.resolution_schedule)
-                      for s_ in range(0, max(cfg.iters, 1), max(min(cfg.resolution_schedule, cfg.iters), 1))} | {1})
+    factors = _schedule_factors(cfg)
     cams_by_d = {d: (cams if d == 1 else [CameraTensors.from_numpy(rescale_camera(c, d), device) for c in cams_np])
                  for d in factors}
     bg = torch.tensor(S.BACKGROUND, device=device)
@@ -690,6 +776,86 @@ def evaluate(model: GaussianParams, data: TrainData, cfg: TrainConfig, cams=None
                 de.append(float((o["depth"][..., 0] - data.gt_depth[i]).abs()[m].mean()) if bool(m.any()) else 0.0)
     return {"psnr": float(np.mean(ps)), "psnr_masked": float(np.mean(pm)) if masked else None,
             "depth_err": float(np.mean(de)) if cogs else None}
+
+
+def evaluate_dataset(model: GaussianParams, dataset_or_cache, cfg: TrainConfig, split: str = "val", device=None) -> Dict:
+    """Held-out evaluation as the toolkit's `get_average_eval_image_metrics(get_std=True)` reports it
+    (pipelines/base_pipeline.py): every view of `split` rendered at full size over the fixed background, the ground
+    truth formed by gs_fused.target_from_u8 (d = 1, same background).  Per image: PSNR = 10 log10(1 / mse) over all
+    elements, SSIM from the fused head (`l1_ssim_loss(..., return_terms=True)`), the view's rays per second and frames
+    per second (wall clock around the render, synchronised).  -> means and, as `torch.std_mean` gives it (unbiased; 0
+    for one image), `*_std`, plus the per-image lists.  LPIPS is left out: no network weights ship with this package.
+    `dataset_or_cache`: a path, a gs_io.dataset.Dataset of that split, or a (Dataset, ImageCache) pair."""
+    from gs_fused import l1_ssim_loss
+    from gs_io.dataset import Dataset, load_dataset
+
+    device = model.gauss["means"].device if device is None else device
+    if isinstance(dataset_or_cache, (tuple, list)):
+        ds, cache = dataset_or_cache
+    else:
+        ds = dataset_or_cache if isinstance(dataset_or_cache, Dataset) else \
+            load_dataset(dataset_or_cache, split, **dataset_config(cfg))
+        cache = upload_dataset(ds, device) if len(ds) else None
+    if len(ds) == 0:
+        raise ValueError(f"the {split!r} split holds no views")
+    bg = torch.tensor(S.BACKGROUND, device=device)
+    cogs = cfg.model == "co-gs"
+    per = {"psnr": [], "ssim": [], "num_rays_per_sec": [], "fps": []}
+    with torch.no_grad():
+        for v, cam_np in enumerate(ds.cameras):
+            cam = CameraTensors.from_numpy(cam_np, device)
+            torch.cuda.synchronize(device)
+            t0 = time.perf_counter()
+            if cogs:
+                o = model.render(cam, bg, cfg.sh_degree, render_depth=True, fused_depth=True,
+                                 rasterize_mode=cfg.rasterize_mode)
+            else:
+                o = model.render(cam, bg, cfg.sh_degree, rasterize_mode=cfg.rasterize_mode)
+            torch.cuda.synchronize(device)
+            dt = time.perf_counter() - t0
+            rgb, gt = o["rgb"].contiguous(), cache.target(v, 1, bg)
+            mse = ((rgb - gt) ** 2).mean()
+            per["psnr"].append(float(10.0 * torch.log10(1.0 / mse)))
+            per["ssim"].append(float(l1_ssim_loss(rgb, gt, cfg.ssim_lambda, return_terms=True)[2]))
+            per["num_rays_per_sec"].append(cam.height * cam.width / dt)
+            per["fps"].append(1.0 / dt)
+    out = {}
+    for k, vals in per.items():
+        t = torch.tensor(vals, dtype=torch.float64)
+        std, mean = torch.std_mean(t) if len(vals) > 1 else (torch.tensor(0.0), t.mean())
+        out[k], out[f"{k}_std"] = float(mean), float(std)
+    out.update({f"{k}_per_image": v for k, v in per.items()})
+    out.update({"num_images": len(ds), "split": split, "lpips": None,
+                "lpips_note": "not computed: no network weights ship with this package"})
+    return out
+
+
+def dataset_initial_model(cfg: TrainConfig, ds, device) -> GaussianParams:
+    """`populate_modules` (vanilla_gs.py:126-174) on the dataset's seed cloud: means = the points, DC colour =
+    RGB2SH(rgb / 255), higher bands zero, log-scales = log(mean distance to the 3 nearest seeds) on all axes
+    (gs_fused.initial_log_scales on the GPU), random unit quaternions, opacity logit(0.1).  Without a cloud, or with
+    `dataset_random_init`: `dataset_num_random` points uniform in a cube of edge `dataset_random_scale`, DC = rand."""
+    rng = np.random.default_rng(cfg.seed + 1)
+    f32 = np.float32
+    if ds.points3D_xyz is not None and len(ds.points3D_xyz) > 0 and not cfg.dataset_random_init:
+        means = np.ascontiguousarray(ds.points3D_xyz, f32)
+        dc = ((ds.points3D_rgb.astype(f32) / f32(255.0)) - f32(0.5)) / f32(SH_C0)
+    else:
+        means = ((rng.uniform(size=(cfg.dataset_num_random, 3)) - 0.5) * cfg.dataset_random_scale).astype(f32)
+        dc = rng.uniform(size=(cfg.dataset_num_random, 3)).astype(f32)
+    n = means.shape[0]
+    if device.type == "cuda":
+        from gs_fused import initial_log_scales
+
+        scales = initial_log_scales(torch.from_numpy(means).to(device), 3, floor=1e-7).cpu().numpy()
+    else:
+        scales = np.repeat(np.log(np.maximum(knn_mean_distance(means, 3), 1e-7))[:, None], 3, axis=1).astype(f32)
+    raw = {"means": means, "scales": scales.astype(f32), "quats": random_quats(n, rng),
+           "opacities": np.full((n, 1), math.log(0.1 / 0.9), f32), "features_dc": dc.astype(f32),
+           "features_rest": np.zeros((n, S.num_sh_bases(cfg.sh_degree) - 1, 3), f32)}
+    model = GaussianParams(raw, device)
+    model.split_sh, model.fused_activations = cfg.split_sh, cfg.fused_activations
+    return model
 
 
 def initial_model(cfg: TrainConfig, device) -> GaussianParams:
@@ -801,6 +967,7 @@ class StepInputs:
 
     def __init__(self, cfg: TrainConfig, data: TrainData, device, rank: int = 0):
         self.data, self.device, self.fused_target = data, device, cfg.fused_target
+        self.cache, self.graph_targets = data.cache, bool(cfg.use_graph)
         random_bg = cfg.background_color == "random"
         # (the reference seeds every rank differently, scripts/train.py:54: the backgrounds differ per rank, as there)
         self.bg_gen = torch.Generator(device=device).manual_seed(cfg.seed + 977 * (rank + 1)) if random_bg else None
@@ -811,6 +978,8 @@ class StepInputs:
     def __call__(self, v: int, d: int):
         """-> (background [3], target [h,w,3], mask [h,w,1] or None); draws the step's background."""
         data = self.data
+        if self.cache is not None:
+            return self._from_cache(v, d)
         if self.bg_gen is None:
             bg, target = data.bg, downscale_image(data.gt[v], d)
         else:
@@ -833,6 +1002,22 @@ class StepInputs:
             if mask is None:
                 mask = self.mask_cache[(v, d)] = downscale_mask(data.masks[v], d).contiguous()
         return bg, target, mask
+
+
+    def _from_cache(self, v: int, d: int):
+        """The same three from the integer cache: the background stays the device tensor it is (never read back), the
+        target is one kernel over the uint8 image, and under `use_graph` that kernel writes the graph's static target
+        itself (a gs_fused.DeferredTarget: nothing is allocated or copied)."""
+        cache = self.cache
+        if self.bg_gen is None:
+            bg = self.data.bg
+        else:
+            bg = torch.rand(3, device=self.device, generator=self.bg_gen)
+            if self.bg_static is not None:
+                self.bg_static.copy_(bg)
+                bg = self.bg_static
+        target = cache.deferred_target(v, d, bg) if self.graph_targets else cache.target(v, d, bg)
+        return bg, target, cache.mask(v, d)
 
 
 class DensifyState:
@@ -1016,7 +1201,7 @@ class SeparateStep:
     overflow_views = 0  # (the tile lists are rasterizer.rasterize's here: `_list_rebuilds`)
 
     def __init__(self, cfg: TrainConfig, model, data: TrainData, heads, exchange, sh_views: bool, device):
-        self.cfg, self.model, self.gt_depth = cfg, model, data.gt_depth
+        self.cfg, self.model, self.gt_depth, self.cache = cfg, model, data.gt_depth, data.cache
         self.photo, self.depth_head, fused_clamp = heads
         cuda = device.type == "cuda"
         cogs = self.cogs = cfg.model == "co-gs"
@@ -1042,7 +1227,9 @@ class SeparateStep:
         loss = self.photo(out["rgb"], target, mask)
         if self.cogs:
             self.depth_on = step > self.depth_after
-            for term in _cogs_terms(self.cfg, step, self.model, out, target, mask, self.gt_depth[v], d,
+            # (a dataset: the integer depth resized by the cache's kernel, so nothing is left to downscale)
+            gt_depth, d_depth = (self.gt_depth[v], d) if self.cache is None else (self.cache.depth(v, d), 1)
+            for term in _cogs_terms(self.cfg, step, self.model, out, target, mask, gt_depth, d_depth,
                                     self.depth_head, self.depth_on):
                 loss = loss + term
         if self.camera_opt is not None:
@@ -1178,7 +1365,7 @@ def phase_record(marks, cfg: TrainConfig, factors) -> Dict:
 def result_record(cfg: TrainConfig, device, world: int, model, run: Dict, eval0: Dict, eval1: Dict, phases: Dict) -> Dict:
     """What `train` returns.  `run`: what the driver counted (see there)."""
     steps, elapsed = cfg.iters - run["start_step"], run["elapsed"]
-    cogs, masked = cfg.model == "co-gs", cfg.mask != "none"
+    cogs, masked = cfg.model == "co-gs", cfg.mask != "none" or bool((run.get("dataset") or {}).get("masks"))
     checksum = float(sum(p.detach().double().sum() for p in model.param_list()))
     return {"iters": steps, "start_step": run["start_step"], "seconds": elapsed,
             "iters_per_s": steps / elapsed, "psnr_start": eval0["psnr"],
@@ -1200,6 +1387,8 @@ def result_record(cfg: TrainConfig, device, world: int, model, run: Dict, eval0:
                        "mean_abs_error_start_end": [eval0["depth_err"], eval1["depth_err"]]} if cogs else None),
             "peak_memory_bytes": (int(torch.cuda.max_memory_allocated(device)) if device.type == "cuda" else None),
             "densify_grad_thresh": (run["rcfg"].densify_grad_thresh if cfg.densify else None),
+            # (only where it was asked for, as above)
+            **({"dataset": run["dataset"]} if run.get("dataset") is not None else {}),
             **run.get("pose", {})}
 
 
@@ -1215,8 +1404,17 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
     _check_camera_optimizer(cfg, device, world)
     cuda = device.type == "cuda"
     dp = world > 1 or (cfg.force_exchange and dist.is_available() and dist.is_initialized())
-    data = make_data(cfg, device)
-    model = initial_model(cfg, device)
+    if cfg.dataset is not None:
+        if world > 1 or dp:
+            raise ValueError("dataset: a dataset directory trains on one GPU (world size 1): the per-rank view "
+                             "sampling of a real dataset is not implemented")
+        data = make_dataset_data(cfg, device)
+        ds = data.dataset
+        cfg = replace(cfg, num_views=len(ds), width=ds.width, height=ds.height)  # (a copy: the caller's is left alone)
+        model = dataset_initial_model(cfg, ds, device)
+    else:
+        data = make_data(cfg, device)
+        model = initial_model(cfg, device)
     optims, sharded = make_optimisers(cfg, model, device, dp)
     heads = loss_heads(cfg, device)
     rcfg = cfg.refine
@@ -1323,7 +1521,19 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
         from gs_io.ply import write_gaussian_ply
 
         write_gaussian_ply(cfg.export_ply, {k: model.gauss[k].detach().cpu().numpy() for k in PARAM_NAMES})
+    heldout = None
+    if data.cache is not None and cfg.dataset_eval_split and cuda:
+        from gs_io.dataset import load_dataset
+
+        held = load_dataset(cfg.dataset, cfg.dataset_eval_split, **dataset_config(cfg))
+        heldout = evaluate_dataset(model, held, cfg, cfg.dataset_eval_split, device) if len(held) else None
     run = {"start_step": start_step, "elapsed": elapsed, "n0": n0, "losses": losses, "history": history,
+           "dataset": None if data.cache is None else {
+               "path": cfg.dataset, "num_train_views": cfg.num_views, "width": cfg.width, "height": cfg.height,
+               "channels": data.cache.channels, "masks": data.cache.masks is not None,
+               "depth": data.cache.depths is not None, "cache_bytes": data.cache.nbytes,
+               "seed_points": None if data.dataset.points3D_xyz is None else int(len(data.dataset.points3D_xyz)),
+               "dataparser_scale": data.dataset.scale, "heldout": heldout},
            "exchanged_bytes": exchanged_bytes, "rcfg": rcfg,
            "render": ("hip graph per view" if cfg.use_graph else "one fused op") if use_fused else "separate ops",
            "overflow_views": run_step.overflow_views + (_list_rebuilds() - rebuilds0),

@@ -128,6 +128,8 @@ SYMBOLS = (
     "gsr_knn_workspace_bytes",
     "gsr_knn_build",
     "gsr_knn_query",
+    "gsr_target_from_u8",
+    "gsr_plane_from_int",
     "gsr_debug_count_staged",
     "gsr_debug_wave_trace",
     "gsr_calibrate_valu",

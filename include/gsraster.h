@@ -1398,6 +1398,32 @@ int gsr_knn_query(int num_points, const void *tree, size_t tree_bytes, int num_u
                   size_t workspace_bytes, float *distance, int32_t *index, int32_t *state,
                   gsr_stream_t stream);
 
+/* ---- targets from an integer image cache (csrc/target.hip) ------
+ * A training step's ground truth formed from images that stay uint8 on the device, in the
+ * order of the models' get_gt_img (vanilla_gs.py:859-881): convert, resize, composite.
+ * gsr_target_from_u8: image uint8 [height,width,channels], channels 3 or 4 (RGBA 4-byte
+ *   aligned); background float32 [3] ON THE DEVICE (read for channels = 4 only); out float32
+ *   [out_height,out_width,3].  Per output pixel and channel:
+ *     1. v = float(u8) / 255, correctly rounded;
+ *     2. bilinear resize without antialiasing, half-pixel centres (align_corners = False):
+ *        per axis s = max(scale * (dst + 0.5) - 0.5, 0) with scale = float(in) / float(out),
+ *        i0 = int(s), i1 = i0 + (i0 < in - 1), l1 = s - i0, l0 = 1 - l1;
+ *        value = ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 + lx1 * v11); alpha included;
+ *     3. channels = 4: a * rgb + (1 - a) * background from the RESIZED rgba.
+ *   Every operation is rounded on its own (no contraction).  out == in: no resize, the value is
+ *   v00 itself, and with channels = 3 the output is exactly u8 / 255.
+ * gsr_plane_from_int: plane uint8 (elem_bytes 1) or uint16 (2) [height,width]; out float32
+ *   [out_height,out_width]: v = float(value) * unit, then step 2.  Masks (unit 1), 16-bit depth
+ *   in millimetres (1e-3), 8-bit monocular depth (1 / 255); zeros are interpolated like any
+ *   other value.
+ * Both: 1 <= out_height <= height, 1 <= out_width <= width, out_height <= 262140 (GSR_EINVAL
+ * otherwise, nothing launched).  One launch, nothing allocated, no workspace. */
+int gsr_target_from_u8(const uint8_t *image, int height, int width, int channels,
+                       const float *background, int out_height, int out_width, float *out,
+                       gsr_stream_t stream);
+int gsr_plane_from_int(const void *plane, int elem_bytes, int height, int width, float unit,
+                       int out_height, int out_width, float *out, gsr_stream_t stream);
+
 /* ---- measurement hook ---------------------------------------------------------
  * counters: two device uint64 (or NULL = off, the default).  While set, the 16x16
  * compositing kernels add the number of list entries they stage to counters[0]
