@@ -172,15 +172,18 @@ constexpr int kPartialStride = 12;  // floats per list entry in deterministic mo
 // lives in row slot_of[e] -- so the result does not depend on which tile's wave finished
 // first.  Rows a tile never reached (it stopped early / the splat was culled at staging)
 // carry flag 0.
-template <bool RGBD>
+// ABS: slots 10, 11 of a row hold the (tile, entry) absgrad sums (written only by the ABS walk) -> v_xy_abs.
+template <bool RGBD, bool ABS = false>
 __global__ __launch_bounds__(256) void reduce_partials_kernel(
     const int n, const int num_bands, const int capacity, const int *__restrict__ order,
     const int *__restrict__ cum, const int *__restrict__ slot_of, const float *__restrict__ partials,
     const unsigned char *__restrict__ pflags, float *__restrict__ v_xy, float *__restrict__ v_conic,
-    float *__restrict__ v_colors, float *__restrict__ v_opacity, float *__restrict__ v_extra) {
+    float *__restrict__ v_colors, float *__restrict__ v_opacity, float *__restrict__ v_extra,
+    float *__restrict__ v_xy_abs = nullptr) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   float acc[10] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  [[maybe_unused]] float abs_x = 0.f, abs_y = 0.f;
   for (int b = 0; b < num_bands; ++b) {
     const long long ci = (long long)b * n + i;
     int e0 = ci > 0 ? cum[ci - 1] : 0, e1 = cum[ci];
@@ -195,6 +198,7 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(
       acc[4] += r1.x, acc[5] += r1.y, acc[6] += r1.z, acc[7] += r1.w;
       acc[8] += r2.x;
       if (RGBD) acc[9] += r2.y;
+      if constexpr (ABS) abs_x += r2.z, abs_y += r2.w;
     }
   }
   const int g = order[i];
@@ -203,6 +207,7 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(
   v_colors[3 * g] = acc[5], v_colors[3 * g + 1] = acc[6], v_colors[3 * g + 2] = acc[7];
   v_opacity[g] = acc[8];
   if (RGBD) v_extra[g] = acc[9];
+  if constexpr (ABS) v_xy_abs[2 * g] = abs_x, v_xy_abs[2 * g + 1] = abs_y;
 }
 
 // ---- depth segments (docs/history/DESIGN_r01-r05.md 4.16) -------------------------------------------------------------------
@@ -215,7 +220,12 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(
 // segments behind it to (T_final, K_0) and walks only its own entries.  Same per-entry arithmetic; T reaches a
 // segment as a product of segment products instead of one chain: equal to the single walk to rounding, not bitwise.
 
-template <int G, bool RGBD, bool SEG = false>
+// ABS: the absgrad of include/gsraster.h (gsr_rasterize_backward_abs) next to the gradients -- per splat a lane keeps
+// two more sums, sum_p |w (2 ha dx + b dy)| and sum_p |w (b dx + 2 hc dy)| (|v_xy(p, g)| / |opac|: the absolute value
+// cannot wait for the moments, it is taken per pixel), reduced by a butterfly of their own (8 values per group of 4
+// splats: 4 + 2 + 1 halving steps, then 3 plain DPP adds) and scaled by |opac| once.  `if constexpr` only: an
+// instantiation without it is the kernel it was.
+template <int G, bool RGBD, bool SEG = false, bool ABS = false>
 __global__ __launch_bounds__(64) void raster_bwd_tile16_kernel(
     const int tiles_x, const int num_tiles, const int img_w, const int img_h,
     const int *__restrict__ ids_sorted, const int2 *__restrict__ tile_bins,
@@ -229,10 +239,11 @@ __global__ __launch_bounds__(64) void raster_bwd_tile16_kernel(
     float *__restrict__ v_extra, const int deep_threshold, const unsigned base_grid,
     float *__restrict__ partials, unsigned char *__restrict__ pflags, const int2 *__restrict__ tile_bins2,
     const int idx_base2, const int seg_count = 1, const int seg_min = 0,
-    const float2 *__restrict__ seg_state = nullptr) {
+    const float2 *__restrict__ seg_state = nullptr, float *__restrict__ v_xy_abs = nullptr) {
   // tile_bins2 (two-round lists, gsr_rasterize_forward_round): a tile's list is its range in tile_bins followed by
   // its range in tile_bins2 (relative to idx_base2 in ids_sorted): walked back to front, second segment first.
   static_assert(!RGBD || G == 4, "the 10-component butterfly exists for groups of 4");
+  static_assert(!ABS || G == 4, "the absgrad butterfly exists for groups of 4");
   constexpr int NC = RGBD ? 10 : 9;
   __shared__ SplatA sA[kChunk];
   __shared__ SplatB sB[kChunk];
@@ -394,12 +405,14 @@ __global__ __launch_bounds__(64) void raster_bwd_tile16_kernel(
 
     for (int t0 = 0; t0 < count; t0 += G) {
       float P[NC * G];
+      [[maybe_unused]] float AB[ABS ? 2 * G : 1];  // ABS: AB[2 j], AB[2 j + 1] = this lane's |x|, |y| sums of splat j
       bool lane_any = false;
 #pragma unroll
       for (int j = 0; j < G; ++j) {
         const int t = t0 + j;
         float m0 = 0.f, mx = 0.f, my = 0.f, mxx = 0.f, mxy = 0.f, myy = 0.f;
         float sr = 0.f, sg = 0.f, sb = 0.f, se = 0.f;
+        [[maybe_unused]] float abx = 0.f, aby = 0.f;
         if (t < count) {  // wave-uniform
           const SplatA A = sA[t];
           const SplatB B = sB[t];
@@ -413,6 +426,14 @@ __global__ __launch_bounds__(64) void raster_bwd_tile16_kernel(
                                 (ax0 + cy1) + bx0 * dy1, (ax1 + cy1) + bx1 * dy1};
           const float dxs[4] = {dx0, dx1, dx0, dx1};
           const float dys[4] = {dy0, dy0, dy1, dy1};
+          // ABS: (a dx + b dy, b dx + c dy) at the lane's four pixels
+          [[maybe_unused]] float gxs[4], gys[4];
+          if constexpr (ABS) {
+            const float a0 = 2.f * A.ha * dx0, a1 = 2.f * A.ha * dx1, c0 = 2.f * B.hc * dy0, c1 = 2.f * B.hc * dy1;
+            const float by0 = A.b * dy0, by1 = A.b * dy1;
+            gxs[0] = a0 + by0, gxs[1] = a1 + by0, gxs[2] = a0 + by1, gxs[3] = a1 + by1;
+            gys[0] = bx0 + c0, gys[1] = bx1 + c0, gys[2] = bx0 + c1, gys[3] = bx1 + c1;
+          }
 #pragma unroll
           for (int p = 0; p < 4; ++p) {
             // wave-uniform: sub-tile out of the splat's reach, or every pixel of
@@ -452,6 +473,10 @@ __global__ __launch_bounds__(64) void raster_bwd_tile16_kernel(
             mxx += wx * dxs[p];
             mxy += wx * dys[p];
             myy += wy * dys[p];
+            if constexpr (ABS) {  // (an invalid pair has w = 0: exactly 0 here as well)
+              abx += fabsf(w * gxs[p]);
+              aby += fabsf(w * gys[p]);
+            }
             lane_any = lane_any || valid;
           }
         }
@@ -468,6 +493,7 @@ __global__ __launch_bounds__(64) void raster_bwd_tile16_kernel(
         P[NC * j + 7] = sb;
         P[NC * j + 8] = m0;
         if constexpr (RGBD) P[NC * j + 9] = se;
+        if constexpr (ABS) AB[2 * j] = abx, AB[2 * j + 1] = aby;
       }
       if (!__any(lane_any)) continue;  // nothing in this group touched a live pixel
 
@@ -481,6 +507,19 @@ __global__ __launch_bounds__(64) void raster_bwd_tile16_kernel(
       // v_conic = -opac (Sxx/2, Sxy, Syy/2),  v_rgb = the colour sums,  v_opacity = S0
       const float other = BF::swap01(main_v);
       const int t = t0 + BF::splat_of_lane(lane);
+      // ABS: lane l ends with the |x| sum (bit 3 of l clear) or the |y| sum (set) of splat l >> 4, in all 8 lanes
+      [[maybe_unused]] float abs_v = 0.f;
+      if constexpr (ABS) {
+        float Q[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) Q[i] = fold32(AB[i], AB[i + 4]);  // lane bit 5 <-> splat bit 1
+        const float rx = fold16(Q[0], Q[2]), ry = fold16(Q[1], Q[3]);  // lane bit 4 <-> splat bit 0
+        float e = halve<DPP_ROW_ROR8>(rx, ry, (lane & 8) != 0);
+        e += dpp<DPP_ROW_HALF_MIRROR>(e);
+        e += dpp<DPP_QUAD_XOR1>(e);
+        e += dpp<DPP_QUAD_XOR2>(e);
+        abs_v = e;
+      }
       if (t < count) {
         const SplatA A = sA[t];
         const SplatB B = sB[t];
@@ -502,12 +541,19 @@ __global__ __launch_bounds__(64) void raster_bwd_tile16_kernel(
           if constexpr (RGBD) {
             if ((lane & 15) == 1) row[9] = extra2_v;
           }
+          if constexpr (ABS) {
+            if ((lane & 7) == 2) row[10 + ((lane >> 3) & 1)] = fabsf(B.opac) * abs_v;
+          }
         } else {
         if (owns_main && grad != 0.f)
           unsafeAtomicAdd(dst_base + (size_t)g * dst_stride + dst_off, grad);
         if (owns_extra && extra_v != 0.f) unsafeAtomicAdd(v_opacity + g, extra_v);
         if constexpr (RGBD) {
           if ((lane & 15) == 1 && extra2_v != 0.f) unsafeAtomicAdd(v_extra + g, extra2_v);
+        }
+        if constexpr (ABS) {
+          const float av = fabsf(B.opac) * abs_v;
+          if ((lane & 7) == 2 && av != 0.f) unsafeAtomicAdd(v_xy_abs + 2 * (size_t)g + ((lane >> 3) & 1), av);
         }
         }
       }
@@ -849,9 +895,10 @@ struct Bwd16 {
   unsigned char *pflags = nullptr;
   int segments = 0, segment_min_entries = 0;  // depth segments: >= 2 runs, with the workspace of
   void *workspace = nullptr;                  // gsr_rasterize_backward_seg_workspace_bytes
+  float *v_xy_abs = nullptr;  // absgrad [n,2] (include/gsraster.h): cleared here, never by the forward
 };
 
-template <bool RGBD>
+template <bool RGBD, bool ABS>
 void launch_tile16_backward(const Bwd16 &a, const int tiles_x, const int tiles_y, const int deep, hipStream_t s) {
   const int num_tiles = tiles_x * tiles_y, img_w = (int)a.img_w, img_h = (int)a.img_h;
   const unsigned base = gsr_xcd_grid(tiles_x, tiles_y);
@@ -861,10 +908,11 @@ void launch_tile16_backward(const Bwd16 &a, const int tiles_x, const int tiles_y
   const float *v_output_extra = RGBD ? a.v_output_extra : nullptr;
   float *v_extra = RGBD ? a.v_extra : nullptr;
   if (a.segments < 2) {
-    hipLaunchKernelGGL((raster_bwd_tile16_kernel<4, RGBD, false>), dim3(deep ? 4 * base : base), dim3(64), 0, s, tiles_x,
+    hipLaunchKernelGGL((raster_bwd_tile16_kernel<4, RGBD, false, ABS>), dim3(deep ? 4 * base : base), dim3(64), 0, s, tiles_x,
                        num_tiles, img_w, img_h, a.ids, bins, xys, a.conics, a.colors, a.opacities, a.background,
                        a.final_Ts, a.final_idx, a.v_output, a.v_output_alpha, a.v_xy, a.v_conic, a.v_colors, a.v_opacity,
-                       a.extra, bg_extra, v_output_extra, v_extra, deep, base, a.partials, a.pflags, bins2, a.idx_base2);
+                       a.extra, bg_extra, v_output_extra, v_extra, deep, base, a.partials, a.pflags, bins2, a.idx_base2, 1, 0,
+                       (const float2 *)nullptr, a.v_xy_abs);
     return;
   }
   // (R, S) of the runs behind each run per pixel, their prefixes, then one wave per (tile, sub-tile, run)
@@ -876,11 +924,11 @@ void launch_tile16_backward(const Bwd16 &a, const int tiles_x, const int tiles_y
                      a.v_output, a.extra, v_output_extra, deep, base, segments, seg_min, state);
   hipLaunchKernelGGL(raster_bwd_segprefix_kernel, dim3((unsigned)(((size_t)a.img_h * a.img_w + 255) / 256)), dim3(256), 0,
                      s, tiles_x, img_w, img_h, bins, threshold, segments, seg_min, state);
-  hipLaunchKernelGGL((raster_bwd_tile16_kernel<4, RGBD, true>), dim3((unsigned)segments * 4u * base), dim3(64), 0, s,
+  hipLaunchKernelGGL((raster_bwd_tile16_kernel<4, RGBD, true, ABS>), dim3((unsigned)segments * 4u * base), dim3(64), 0, s,
                      tiles_x, num_tiles, img_w, img_h, a.ids, bins, xys, a.conics, a.colors, a.opacities, a.background,
                      a.final_Ts, a.final_idx, a.v_output, a.v_output_alpha, a.v_xy, a.v_conic, a.v_colors, a.v_opacity,
                      a.extra, bg_extra, v_output_extra, v_extra, deep, base, a.partials, a.pflags, bins2, a.idx_base2,
-                     segments, seg_min, (const float2 *)state);
+                     segments, seg_min, (const float2 *)state, a.v_xy_abs);
 }
 
 // Checks what every 16-px entry requires, clears the accumulators unless the caller has, builds the job order where the
@@ -896,11 +944,19 @@ int launch_tile16_backward(const char *who, const Bwd16 &a, hipStream_t s) {
               "%s: null pointer", who);
   if (!a.accumulators_zeroed)  // (else: cleared by the forward launch's zero_ptr, untouched since)
     if (int rc = zero_accumulators(a.num_points, rgbd, a.v_xy, a.v_conic, a.v_colors, a.v_opacity, a.v_extra, s)) return rc;
+  // (deterministic mode: reduce_partials_kernel writes every element of it, like the gradients)
+  if (a.v_xy_abs && !a.partials)
+    if (int rc = gsr_zero_async(a.v_xy_abs, sizeof(float) * 2 * (size_t)a.num_points, s)) return rc;
   const int tiles_x = (int)gsr_cdiv(a.img_w, 16), tiles_y = (int)gsr_cdiv(a.img_h, 16);
   const int deep = a.static_order ? gsr_deep_threshold(a.deep_arg)
                                   : gsr_prepare_jobs(a.deep_arg, tiles_x, tiles_y, a.tile_bins, s);
-  if (rgbd) launch_tile16_backward<true>(a, tiles_x, tiles_y, deep, s);
-  else launch_tile16_backward<false>(a, tiles_x, tiles_y, deep, s);
+  if (a.v_xy_abs) {
+    if (rgbd) launch_tile16_backward<true, true>(a, tiles_x, tiles_y, deep, s);
+    else launch_tile16_backward<false, true>(a, tiles_x, tiles_y, deep, s);
+  } else {
+    if (rgbd) launch_tile16_backward<true, false>(a, tiles_x, tiles_y, deep, s);
+    else launch_tile16_backward<false, false>(a, tiles_x, tiles_y, deep, s);
+  }
   GSR_CHECK_LAUNCH(who);
   return GSR_OK;
 }
@@ -989,6 +1045,22 @@ GSR_EXPORT int gsr_rasterize_backward_seg(
     float *v_xy, float *v_conic, float *v_colors, float *v_extra, float *v_opacity, int deep_tile_threshold,
     int accumulators_zeroed, int segments, int segment_min_entries, void *workspace, size_t workspace_bytes,
     gsr_stream_t stream) {
+  return gsr_rasterize_backward_abs(img_height, img_width, num_points, gaussian_ids_sorted, tile_bins, xys, conics, colors,
+                                    extra, opacities, background, extra_background, final_Ts, final_idx, v_output,
+                                    v_output_extra, v_output_alpha, v_xy, v_conic, v_colors, v_extra, v_opacity,
+                                    deep_tile_threshold, accumulators_zeroed, segments, segment_min_entries, workspace,
+                                    workspace_bytes, nullptr, stream);
+}
+
+// ---- absgrad (include/gsraster.h): _seg / _two / _det with v_xy_abs; NULL = the entry each extends ----
+GSR_EXPORT int gsr_rasterize_backward_abs(
+    unsigned img_height, unsigned img_width, int num_points, const int32_t *gaussian_ids_sorted,
+    const int32_t *tile_bins, const float *xys, const float *conics, const float *colors, const float *extra,
+    const float *opacities, const float *background, float extra_background, const float *final_Ts,
+    const int32_t *final_idx, const float *v_output, const float *v_output_extra, const float *v_output_alpha,
+    float *v_xy, float *v_conic, float *v_colors, float *v_extra, float *v_opacity, int deep_tile_threshold,
+    int accumulators_zeroed, int segments, int segment_min_entries, void *workspace, size_t workspace_bytes,
+    float *v_xy_abs, gsr_stream_t stream) {
   Bwd16 a = {img_height, img_width, num_points, gaussian_ids_sorted, tile_bins, xys, conics, colors,
              opacities, background, final_Ts, final_idx, v_output, v_output_alpha, v_xy, v_conic,
              v_colors, v_opacity, deep_tile_threshold, accumulators_zeroed != 0};
@@ -1001,6 +1073,7 @@ GSR_EXPORT int gsr_rasterize_backward_seg(
                 "rasterize_backward_seg: workspace too small or not 8-byte aligned");
     a.segments = segments, a.segment_min_entries = segment_min_entries, a.workspace = workspace;
   }
+  a.v_xy_abs = v_xy_abs;
   return launch_tile16_backward("rasterize_backward_seg", a, (hipStream_t)stream);
 }
 
@@ -1012,6 +1085,20 @@ GSR_EXPORT int gsr_rasterize_backward_two(
     const float *final_Ts, const int32_t *final_idx, const float *v_output, const float *v_output_extra,
     const float *v_output_alpha, float *v_xy, float *v_conic, float *v_colors, float *v_extra, float *v_opacity,
     int deep_tile_threshold, int accumulators_zeroed, gsr_stream_t stream) {
+  return gsr_rasterize_backward_two_abs(img_height, img_width, num_points, gaussian_ids_sorted, tile_bins, tile_bins2,
+                                        idx_base2, xys, conics, colors, extra, opacities, background, extra_background,
+                                        final_Ts, final_idx, v_output, v_output_extra, v_output_alpha, v_xy, v_conic,
+                                        v_colors, v_extra, v_opacity, deep_tile_threshold, accumulators_zeroed, nullptr,
+                                        stream);
+}
+
+GSR_EXPORT int gsr_rasterize_backward_two_abs(
+    unsigned img_height, unsigned img_width, int num_points, const int32_t *gaussian_ids_sorted,
+    const int32_t *tile_bins, const int32_t *tile_bins2, int idx_base2, const float *xys, const float *conics,
+    const float *colors, const float *extra, const float *opacities, const float *background, float extra_background,
+    const float *final_Ts, const int32_t *final_idx, const float *v_output, const float *v_output_extra,
+    const float *v_output_alpha, float *v_xy, float *v_conic, float *v_colors, float *v_extra, float *v_opacity,
+    int deep_tile_threshold, int accumulators_zeroed, float *v_xy_abs, gsr_stream_t stream) {
   GSR_REQUIRE(idx_base2 >= 0, "rasterize_backward_two: negative size");
   GSR_REQUIRE(tile_bins2 || num_points <= 0, "rasterize_backward_two: null pointer");
   Bwd16 a = {img_height, img_width, num_points, gaussian_ids_sorted, tile_bins, xys, conics, colors,
@@ -1020,6 +1107,7 @@ GSR_EXPORT int gsr_rasterize_backward_two(
   a.static_order = true;  // (two-round lists: no job order behind either tile_bins)
   a.extra = extra, a.extra_background = extra_background, a.v_output_extra = v_output_extra, a.v_extra = v_extra;
   a.tile_bins2 = tile_bins2, a.idx_base2 = idx_base2;
+  a.v_xy_abs = v_xy_abs;
   return launch_tile16_backward("rasterize_backward_two", a, (hipStream_t)stream);
 }
 
@@ -1038,6 +1126,21 @@ GSR_EXPORT int gsr_rasterize_backward_det(
     const int32_t *order, const int32_t *cum_sorted, int num_bands, const int32_t *slot_of_entry, void *workspace,
     size_t workspace_bytes, float *v_xy, float *v_conic, float *v_colors, float *v_extra, float *v_opacity,
     gsr_stream_t stream) {
+  return gsr_rasterize_backward_det_abs(img_height, img_width, num_points, list_capacity, gaussian_ids_sorted, tile_bins,
+                                        xys, conics, colors, extra, opacities, background, extra_background, final_Ts,
+                                        final_idx, v_output, v_output_extra, v_output_alpha, order, cum_sorted, num_bands,
+                                        slot_of_entry, workspace, workspace_bytes, v_xy, v_conic, v_colors, v_extra,
+                                        v_opacity, nullptr, stream);
+}
+
+GSR_EXPORT int gsr_rasterize_backward_det_abs(
+    unsigned img_height, unsigned img_width, int num_points, int list_capacity, const int32_t *gaussian_ids_sorted,
+    const int32_t *tile_bins, const float *xys, const float *conics, const float *colors, const float *extra,
+    const float *opacities, const float *background, float extra_background, const float *final_Ts,
+    const int32_t *final_idx, const float *v_output, const float *v_output_extra, const float *v_output_alpha,
+    const int32_t *order, const int32_t *cum_sorted, int num_bands, const int32_t *slot_of_entry, void *workspace,
+    size_t workspace_bytes, float *v_xy, float *v_conic, float *v_colors, float *v_extra, float *v_opacity,
+    float *v_xy_abs, gsr_stream_t stream) {
   GSR_REQUIRE(img_height > 0 && img_width > 0, "rasterize_backward_det: empty image");
   GSR_REQUIRE(num_points >= 0 && list_capacity >= 0, "rasterize_backward_det: negative size");
   if (num_points == 0) return GSR_OK;
@@ -1061,8 +1164,18 @@ GSR_EXPORT int gsr_rasterize_backward_det(
   a.pflags = reinterpret_cast<unsigned char *>(workspace) +
              (((size_t)list_capacity * kPartialStride * sizeof(float) + 255) & ~(size_t)255);
   if (int zrc = gsr_zero_async(a.pflags, ((size_t)list_capacity + 3) & ~(size_t)3, s)) return zrc;
+  a.v_xy_abs = v_xy_abs;
   if (int rc = launch_tile16_backward("rasterize_backward_det", a, s)) return rc;
-  if (extra)
+  if (v_xy_abs) {
+    if (extra)
+      hipLaunchKernelGGL((reduce_partials_kernel<true, true>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0, s, num_points,
+                         num_bands, list_capacity, order, cum_sorted, slot_of_entry, (const float *)a.partials,
+                         (const unsigned char *)a.pflags, v_xy, v_conic, v_colors, v_opacity, v_extra, v_xy_abs);
+    else
+      hipLaunchKernelGGL((reduce_partials_kernel<false, true>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0, s, num_points,
+                         num_bands, list_capacity, order, cum_sorted, slot_of_entry, (const float *)a.partials,
+                         (const unsigned char *)a.pflags, v_xy, v_conic, v_colors, v_opacity, (float *)nullptr, v_xy_abs);
+  } else if (extra)
     hipLaunchKernelGGL(reduce_partials_kernel<true>, dim3(gsr_cdiv(num_points, 256)), dim3(256), 0, s, num_points,
                        num_bands, list_capacity, order, cum_sorted, slot_of_entry, (const float *)a.partials,
                        (const unsigned char *)a.pflags, v_xy, v_conic, v_colors, v_opacity, v_extra);

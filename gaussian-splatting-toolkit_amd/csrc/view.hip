@@ -143,17 +143,17 @@ GSR_EXPORT int gsr_view_backward(const gsr_view_desc *v, const gsr_view_grads *g
   GSR_REQUIRE(!v->render_depth || g->v_depth != nullptr, "view_backward: render_depth without its cotangent");
   GSR_REQUIRE(!v->antialiased || v->opac_aa != nullptr, "view_backward: antialiased without opac_aa");
   if (!g->accumulators_final) {  // (else: the caller's deterministic compositing backward has filled them)
-    GSR_TRY(gsr_rasterize_backward_seg((unsigned)v->img_height, (unsigned)v->img_width, n, v->ids, v->tile_bins, v->xys,
+    GSR_TRY(gsr_rasterize_backward_abs((unsigned)v->img_height, (unsigned)v->img_width, n, v->ids, v->tile_bins, v->xys,
                                      v->conics, v->colors, v->render_depth ? v->depths : nullptr,
                                      v->antialiased ? v->opac_aa : v->opac,
                                      v->background, 0.f, v->final_Ts, v->final_idx, g->v_img,
                                      v->render_depth ? g->v_depth : nullptr, g->v_alpha, v_xy, v_conic, v_colors,
                                      v->render_depth ? v_extra : nullptr, v_opac, v->deep_tile_threshold,
                                      g->accumulators_zeroed, v->segments, v->segment_min_entries, v->seg_ws,
-                                     v->seg_ws_bytes, stream));
+                                     v->seg_ws_bytes, g->v_xy_abs, stream));
   }
-  if (g->stats_first != nullptr)
-    GSR_TRY(gsr_densify_stats_dev(n, v_xy, v->radii, g->stats_inv_size, g->stats_first, g->xys_grad_norm,
+  if (g->stats_first != nullptr)  // (absgrad: the densification signal is ITS norm, the chain below keeps v_xy)
+    GSR_TRY(gsr_densify_stats_dev(n, g->v_xy_abs ? g->v_xy_abs : v_xy, v->radii, g->stats_inv_size, g->stats_first, g->xys_grad_norm,
                                   g->vis_counts, g->max_2dsize, stream));
   // v_dc == NULL: the caller forms the SH gradient itself from the colour cotangents left in the accumulators (data
   // parallel: gathered over the ranks, gsr_sh_backward_views)

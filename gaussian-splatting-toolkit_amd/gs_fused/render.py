@@ -68,7 +68,7 @@ class _ViewGrads(C.Structure):  # gsr_view_grads
                 + [(k, C.c_void_p) for k in ("xys_grad_norm", "vis_counts", "max_2dsize", "tmp_v_cov2d", "tmp_v_cov3d",
                                              "tmp_v_scales", "tmp_v_quats", "v_means", "v_log_scales", "v_raw_quats",
                                              "v_logits", "v_dc", "v_rest")]
-                + [("accumulators_final", C.c_int)])
+                + [("accumulators_final", C.c_int), ("v_xy_abs", C.c_void_p)])
 
 
 def _segments(spec, capacity, dev):
@@ -129,6 +129,10 @@ class ViewSpec:
     # "classic", or "antialiased": the view composites sigmoid(logits) * compensation (vanilla_gs.py:96-104,815-816),
     # formed and differentiated inside the projection kernels (gsr_project_forward_aa / _backward_aa)
     rasterize_mode: str = "classic"
+    # absgrad (AbsGS; include/gsraster.h, gsr_rasterize_backward_abs): the compositing backward also sums |dL/dxy| per
+    # pixel into `DensifyStats.absgrad`, and `xys_grad_norm` accumulates THAT norm instead of the signed gradient's.
+    # Needs a `DensifyStats` (render_gaussians(stats=...)).
+    absgrad: bool = False
 
     def __post_init__(self):
         if self.rasterize_mode not in ("classic", "antialiased"):
@@ -151,6 +155,9 @@ class DensifyStats:
         self.xys_grad_norm = torch.zeros(n, device=device)
         self.vis_counts = torch.zeros(n, device=device, dtype=_i32)
         self.max_2dsize = torch.zeros(n, device=device)
+        # `ViewSpec.absgrad`: overwritten by every backward of such a view (never accumulated; allocated here, outside
+        # any capture, so that a graph's backward node has a fixed address to write)
+        self.absgrad = torch.zeros((n, 2), device=device)
         self.max_dim = int(max_dim)
         # 1 = the next update is the first after a refinement (vanilla_gs.py:354-356); kept on the
         # DEVICE so that a captured graph replays correctly across refinement boundaries
@@ -256,6 +263,11 @@ class _Render(Function):
                 v_dep = torch.zeros(H, W, device=dev) if v_dep is None else v_dep.contiguous()
             acc, ctx.accumulators = ctx.accumulators, None
             zeroed = acc is not None
+            v_xy_abs = None
+            if spec.absgrad:
+                v_xy_abs = stats.absgrad
+                if tuple(v_xy_abs.shape) != (n, 2) or v_xy_abs.device != dev:
+                    raise ValueError("absgrad: DensifyStats.absgrad must be [N,2] on the parameters' device")
             if ctx.det is not None:
                 # fixed summation order: the compositing backward from Python, its sums laid out as the accumulators,
                 # and gsr_view_backward for everything behind it
@@ -264,7 +276,7 @@ class _Render(Function):
                 sums = _C.rasterize_backward_det(
                     H, W, d_ids, d_bins, xys, conics, colors, op, background, Ts, idx, v_img, v_a, d_order, d_cum,
                     d_slots, extra=depths if spec.render_depth else None,
-                    v_output_extra=v_dep if spec.render_depth else None)
+                    v_output_extra=v_dep if spec.render_depth else None, v_xy_abs=v_xy_abs)
                 if spec.render_depth:  # (v_xy, v_conic, v_colors, v_extra, v_opacity) -> ... v_opacity | v_extra
                     sums = sums[:3] + (sums[4], sums[3])
                 acc = torch.cat([t.reshape(-1) for t in sums])
@@ -293,7 +305,8 @@ class _Render(Function):
                                p(stats.first) if use_stats else None, (1.0 / stats.max_dim) if use_stats else 0.0,
                                p(stats.xys_grad_norm) if use_stats else None, p(stats.vis_counts) if use_stats else None,
                                p(stats.max_2dsize) if use_stats else None, p(t_cov2d), p(t_cov3d), p(t_vs), p(t_vq),
-                               p(v_means), p(g_s), p(g_q), p(g_o), p(v_dc), p(v_rest), int(ctx.det is not None))
+                               p(v_means), p(g_s), p(g_q), p(g_o), p(v_dc), p(v_rest), int(ctx.det is not None),
+                               p(v_xy_abs))
             _call("gsr_view_backward", C.byref(desc), C.byref(grads), _stream(dev))
             del seg
             if use_stats:
@@ -320,6 +333,8 @@ def render_gaussians(means: Tensor, log_scales: Tensor, raw_quats: Tensor, opaci
     all on the device.  ``capacity``: entries the tile lists are sized for; ``count`` receives
     the entries the view really needs -- if it exceeds the capacity the lists were cut and
     the result is incomplete: render again with a larger capacity (`ListCapacity`).
+    ``spec.absgrad``: the backward overwrites ``stats.absgrad`` [N,2] with the per-pixel |dL/dxy| sums and
+    ``stats.xys_grad_norm`` accumulates its norm (``stats`` is then required: ValueError without).
     ``count_out`` may be a caller-owned int32[1] (device, or pinned host memory).    ``sh_collector`` (data parallel, `harness.parallel.GradientExchange.begin_sh_views`): the backward skips its SH
     backward, hands the colour cotangents [N,3] to ``sh_collector.offer`` and returns no gradient for
     ``features_dc`` / ``features_rest`` -- the exchange forms it from all ranks' cotangents.
@@ -335,6 +350,8 @@ def render_gaussians(means: Tensor, log_scales: Tensor, raw_quats: Tensor, opaci
         raise ValueError("expected scales [N,3], quats [N,4], opacities [N,1]")
     if capacity < 1:
         raise ValueError("capacity must be positive")
+    if spec.absgrad and stats is None:
+        raise ValueError("ViewSpec.absgrad needs stats=DensifyStats(...): the absgrad lands in its `absgrad` buffer")
     if count_out is None:
         count_out = torch.empty(1, dtype=_i32, device=means.device)
     if crop is not None:
@@ -404,6 +421,8 @@ class ViewGraph:
 
     def __init__(self, params: Dict[str, Tensor], spec: ViewSpec, capacity: int, loss_fn, background: Tensor,
                  target_shapes, stats: Optional[DensifyStats] = None, crop: Optional[Tensor] = None):
+        if spec.absgrad and stats is None:
+            raise ValueError("ViewSpec.absgrad needs stats=DensifyStats(...): the absgrad lands in its `absgrad` buffer")
         self.params, self.spec, self.capacity, self.loss_fn, self.stats = params, spec, int(capacity), loss_fn, stats
         dev = params["means"].device
         self.device = dev

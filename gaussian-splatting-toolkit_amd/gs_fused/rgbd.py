@@ -25,6 +25,7 @@ from torch import Tensor
 from torch.autograd import Function
 
 import rasterizer.cuda as _C
+from rasterizer.rasterize import AbsgradOf
 
 _f32 = torch.float32
 BLOCK = 16
@@ -33,7 +34,7 @@ BLOCK = 16
 class _RasterizeRGBD(Function):
     @staticmethod
     def forward(ctx, xys, depths, radii, conics, num_tiles_hit, colors, extra, opacity, img_height, img_width,
-                background, extra_background):
+                background, extra_background, absgrad_of=None):
         from rasterizer.rasterize import build_tile_lists
 
         n = xys.size(0)
@@ -106,6 +107,7 @@ class _RasterizeRGBD(Function):
             bins = torch.zeros(0, 2, dtype=torch.int32, device=dev)
             acc, alpha_out[0] = None, None
         ctx.accumulators = acc
+        ctx.absgrad_of = absgrad_of  # (rasterizer.rasterize.AbsgradOf: the caller's `xys`, or None)
         ctx.det = _R.last_list_aux() if (_R.is_deterministic() and num_intersects >= 1) else None
         ctx.two = (two_aux[1], two_aux[2]) if (two_aux is not None and num_intersects >= 1) else None
         ctx.set_materialize_grads(False)
@@ -119,37 +121,42 @@ class _RasterizeRGBD(Function):
         H, W, num_intersects, ebg = ctx.meta
         n = xys.size(0)
         dev = xys.device
+        v_xy_abs = None
+        if ctx.absgrad_of is not None:
+            v_xy_abs = (torch.zeros if num_intersects < 1 else torch.empty)((n, 2), dtype=_f32, device=dev)
+            ctx.absgrad_of.tensor.absgrad = v_xy_abs
         if num_intersects < 1:
             z = torch.zeros_like
-            return (z(xys), None, None, z(conics), None, z(colors), z(extra), z(opacity)) + (None,) * 4
+            return (z(xys), None, None, z(conics), None, z(colors), z(extra), z(opacity)) + (None,) * 5
         v_img = torch.zeros(H, W, 3, device=dev) if v_img is None else v_img
         v_ext = torch.zeros(H, W, device=dev) if v_ext is None else v_ext
         if ctx.two is not None:
             acc, ctx.accumulators = ctx.accumulators, None
             v_xy, v_conic, v_colors, v_extra, v_opacity = _C.rasterize_backward_two(
                 H, W, ids, bins, ctx.two[0], ctx.two[1], xys, conics, colors, extra, opacity, background, ebg, Ts, idx,
-                v_img, v_ext, v_alpha, accumulators=acc)
+                v_img, v_ext, v_alpha, accumulators=acc, v_xy_abs=v_xy_abs)
         elif ctx.det is not None:  # fixed summation order (rasterizer.rasterize.set_deterministic)
             v_xy, v_conic, v_colors, v_extra, v_opacity = _C.rasterize_backward_det(
                 H, W, ids, bins, xys, conics, colors, opacity, background, Ts, idx, v_img, v_alpha, *ctx.det,
-                extra=extra, extra_background=ebg, v_output_extra=v_ext)
+                extra=extra, extra_background=ebg, v_output_extra=v_ext, v_xy_abs=v_xy_abs)
         else:
             acc, ctx.accumulators = ctx.accumulators, None  # a second backward (retain_graph) clears its own
             v_xy, v_conic, v_colors, v_extra, v_opacity = _C.rasterize_backward_rgbd(
                 H, W, ids, bins, xys, conics, colors, extra, opacity, background, ebg, Ts, idx, v_img, v_ext,
-                v_alpha, accumulators=acc)
+                v_alpha, accumulators=acc, v_xy_abs=v_xy_abs)
         return (v_xy, None, None, v_conic, None, v_colors, v_extra.view(extra.shape),
-                v_opacity.reshape(opacity.shape)) + (None,) * 4
+                v_opacity.reshape(opacity.shape)) + (None,) * 5
 
 
 def rasterize_gaussians_rgbd(xys: Tensor, depths: Tensor, radii: Tensor, conics: Tensor, num_tiles_hit: Tensor,
                              colors: Tensor, extra: Tensor, opacity: Tensor, img_height: int, img_width: int,
-                             background: Optional[Tensor] = None, extra_background: float = 0.0
-                             ) -> Tuple[Tensor, Tensor, Tensor]:
+                             background: Optional[Tensor] = None, extra_background: float = 0.0,
+                             absgrad: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
     """-> (rgb [H,W,3], alpha [H,W], extra image [H,W,1]): `rasterize_gaussians(..., colors,
     return_alpha=True)` and the channel-0 image of `rasterize_gaussians(..., extra repeated
     as 3 colours, background=extra_background)` from one pass.  ``extra``: [N] or [N,1]
-    (typically ``depths``).  Differentiable w.r.t. xys, conics, colors, extra, opacity."""
+    (typically ``depths``).  Differentiable w.r.t. xys, conics, colors, extra, opacity.
+    ``absgrad``: as in :func:`rasterizer.rasterize_gaussians` -- every backward leaves ``xys.absgrad`` [N,2]."""
     if colors.dim() != 2 or colors.shape[1] != 3:
         raise ValueError("colors must have dimensions (N, 3)")
     if extra.numel() != xys.shape[0]:
@@ -163,5 +170,6 @@ def rasterize_gaussians_rgbd(xys: Tensor, depths: Tensor, radii: Tensor, conics:
     img, alpha, ext = _RasterizeRGBD.apply(
         xys.contiguous(), depths.contiguous(), radii.contiguous(), conics.contiguous(), num_tiles_hit.contiguous(),
         colors.contiguous().float(), extra.contiguous().float(), opacity.contiguous(), int(img_height),
-        int(img_width), background.contiguous().float(), float(extra_background))
+        int(img_width), background.contiguous().float(), float(extra_background),
+        AbsgradOf(xys) if absgrad else None)
     return img, alpha, ext[..., None]

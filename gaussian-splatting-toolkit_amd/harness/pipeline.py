@@ -75,6 +75,9 @@ def render_view(
                 # with `caller_syncs` the branch below returns what the reference returns for `crop_ids.sum() == 0`
                 # (:750-757: background, depth 10, accumulation 0); without a read-back nobody can know, and the image
                 # is what compositing nothing gives -- the background with alpha 0, depth 0
+    absgrad: bool = False,  # the compositing backward also leaves `out["xys"].absgrad` [N,2] (rasterize_gaussians /
+                            # rasterize_gaussians_rgbd, `absgrad=True`); with two passes (depth not fused) it is the
+                            # RGB pass's: the colour image's share of the per-pixel gradient
 ) -> Dict[str, Optional[torch.Tensor]]:
     H, W = cam.height, cam.width
     if caller_syncs == "camera" and cam.scalars is not None:
@@ -146,15 +149,16 @@ def render_view(
         raise ValueError("Unknown rasterize_mode: %s" % rasterize_mode)
 
     depth_im = depth_acc = None
+    abs_kw = {"absgrad": True} if absgrad else {}  # (only where asked for: the default call is what it was)
     if render_depth and fused_depth:
         from gs_fused import rasterize_gaussians_rgbd
 
         rgb, alpha, depth_im = rasterize_gaussians_rgbd(xys, depths, radii, conics, num_tiles_hit, rgbs, depths, opac,
-                                                        H, W, background=background)
+                                                        H, W, background=background, **abs_kw)
     else:
         rgb, alpha = rasterize_gaussians(
             xys, depths, radii, conics, num_tiles_hit, rgbs, opac, H, W, BLOCK_WIDTH,
-            background=background, return_alpha=True,
+            background=background, return_alpha=True, **abs_kw,
         )
     alpha = alpha[..., None]
     if crop is not None:

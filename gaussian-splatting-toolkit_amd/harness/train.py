@@ -298,7 +298,7 @@ class GaussianParams(torch.nn.Module):
 
     def render(self, cam: CameraTensors, background, sh_degree_to_use: int, render_depth=False,
                retain_xys_grad=False, clamp_rgb=True, sh_exchange=None, caller_syncs=False, fused_depth=False,
-               normalise_depth=True, rasterize_mode="classic"):
+               normalise_depth=True, rasterize_mode="classic", absgrad=False):
         g = self.gauss
         if self.split_sh and g["features_dc"].is_cuda and g["features_rest"].shape[1] in (3, 8, 15):
             coeffs = (g["features_dc"], g["features_rest"])  # gs_fused.spherical_harmonics_split
@@ -316,7 +316,7 @@ class GaussianParams(torch.nn.Module):
         return render_view(g["means"], scales, quats, opac, coeffs, cam, background, sh_degree_to_use,
                            render_depth=render_depth, retain_xys_grad=retain_xys_grad, viewdirs=dirs,
                            clamp_rgb=clamp_rgb, caller_syncs=caller_syncs, fused_depth=fused_depth,
-                           normalise_depth=normalise_depth, rasterize_mode=rasterize_mode,
+                           normalise_depth=normalise_depth, rasterize_mode=rasterize_mode, absgrad=absgrad,
                            sh_exchange=None if sh_exchange is None else (
                                sh_exchange, ("features_dc", "features_rest"), (g["features_dc"], g["features_rest"])))
 
@@ -405,6 +405,12 @@ class TrainConfig:
     # `ViewSpec.rasterize_mode` (the product inside the projection kernels).  A model trained in one mode renders
     # wrongly in the other.
     rasterize_mode: str = "classic"
+    # absgrad (AbsGS; `absgrad` of gsplat / splatfacto): densification thresholds the accumulated norm of the per-pixel
+    # |dL/dxy| sums instead of the signed screen-space gradient's, which cancels under a large Gaussian over texture.
+    # Both step bodies: `ViewSpec.absgrad` on the one-node view and its graph, `rasterize_gaussians(absgrad=True)`
+    # (`_rgbd` for co-gs' fused depth) on the separate ops.  The sums are larger than the signed norms, so
+    # `densify_grad_thresh` wants raising with it; its default stays.  CUDA only.
+    absgrad: bool = False
     # checkpoints in the toolkit's layout (harness/checkpoint.py; trainer.py:404-476)
     checkpoint_dir: Optional[str] = None
     save_every: int = 0                   # steps_per_save; 0 = never
@@ -601,6 +607,11 @@ def _check_config(cfg: TrainConfig) -> None:
         if cfg.use_graph:
             raise ValueError("camera_optimizer needs the separate-ops path: a replayed HIP graph (use_graph) holds the "
                              "camera's matrices as constants of the capture")
+
+
+def _check_absgrad(cfg: TrainConfig, device) -> None:
+    if cfg.absgrad and device.type != "cuda":
+        raise ValueError("absgrad needs CUDA tensors: the per-pixel sums come from the HIP compositing backward")
 
 
 def _check_camera_optimizer(cfg: TrainConfig, device, world: int) -> None:
@@ -1029,8 +1040,9 @@ class DensifyState:
     data-parallel run, which Gaussians the first view after a restart really saw (parallel.allreduce_densify_stats)."""
 
     def __init__(self, n: int, device, max_dim: int, densify_until: Optional[int] = None, rank: int = 0,
-                 world: int = 1, kernel=None, native: bool = False):
+                 world: int = 1, kernel=None, native: bool = False, absgrad: bool = False):
         self.device, self.max_dim, self.kernel, self.native = device, max_dim, kernel, native
+        self.absgrad = absgrad  # `update` reads out["xys"].absgrad (TrainConfig.absgrad, the separate ops)
         self.stop_at = math.inf if densify_until is None else densify_until
         self.watch_first_view = world > 1 and rank > 0 and densify_until is not None
         self.reset(n)
@@ -1062,12 +1074,14 @@ class DensifyState:
             if self.native:
                 pass  # done by the backward
             elif self.kernel is not None:
-                self.kernel(out["xys"].grad, out["radii"], max_dim, self.xys_grad_norm, self.vis_counts,
+                # (absgrad: the per-pixel |dL/dxy| sums the compositing backward left on the tensor, in place of .grad)
+                g = getattr(out["xys"], "absgrad", None) if self.absgrad else out["xys"].grad
+                self.kernel(g, out["radii"], max_dim, self.xys_grad_norm, self.vis_counts,
                             self.max_2dsize, first=self.first)
             else:
                 with torch.no_grad():
                     visible = out["radii"] > 0
-                    g = out["xys"].grad
+                    g = getattr(out["xys"], "absgrad", None) if self.absgrad else out["xys"].grad
                     gnorm = torch.zeros_like(self.xys_grad_norm) if g is None else g.norm(dim=-1)
                     size = out["radii"].float() / max_dim
                     if self.first:
@@ -1117,7 +1131,7 @@ class FusedStep:
                 probe = render_gaussians(g_["means"], g_["scales"], g_["quats"], g_["opacities"], g_["features_dc"],
                                          g_["features_rest"], cam.viewmat, cam.projmat, cam.campos, data.bg,
                                          ViewSpec(cfg.height, cfg.width, cam.fx, cam.fy, cam.cx, cam.cy, cfg.sh_degree,
-                                                  rasterize_mode=cfg.rasterize_mode),
+                                                  rasterize_mode=cfg.rasterize_mode),  # (no backward: no absgrad)
                                          self.caps.capacity)
                 need = int(probe["count"].item())
                 if need <= self.caps.capacity:
@@ -1128,7 +1142,7 @@ class FusedStep:
     def __call__(self, step, v, d, cam, deg, bg, target, mask):
         cfg, caps, fstats, g_ = self.cfg, self.caps, self.stats.native, self.model.gauss
         spec = self.ViewSpec(cam.height, cam.width, cam.fx, cam.fy, cam.cx, cam.cy, deg,
-                             rasterize_mode=cfg.rasterize_mode)
+                             rasterize_mode=cfg.rasterize_mode, absgrad=cfg.absgrad)
         fstats.enabled = step < self.stats.stop_at
         fstats.max_dim = max(cam.width, cam.height)  # `max(self.last_size)` of after_train
         if not cfg.use_graph:
@@ -1208,7 +1222,7 @@ class SeparateStep:
         self.render_kw = dict(
             retain_xys_grad=True, clamp_rgb=not fused_clamp, sh_exchange=exchange if sh_views else None,
             caller_syncs=cfg.caller_syncs, render_depth=cogs, fused_depth=cogs and cfg.fused_depth and cuda,
-            rasterize_mode=cfg.rasterize_mode,
+            rasterize_mode=cfg.rasterize_mode, absgrad=cfg.absgrad,
             normalise_depth=not (cogs and cfg.fused_depth and cfg.fused_loss and cuda and not cfg.use_est_depth))
         self.depth_after = cfg.depth_loss_start_iteration if cogs and cfg.use_depth_loss else math.inf
         self.phase_every = cfg.phase_every if cuda else 0
@@ -1382,6 +1396,7 @@ def result_record(cfg: TrainConfig, device, world: int, model, run: Dict, eval0:
             **({"psnr_masked_start": eval0["psnr_masked"], "psnr_masked_end": eval1["psnr_masked"]} if masked else {}),
             # (only where it was asked for: a classic run's record stays what it was, to the byte)
             **({"rasterize_mode": cfg.rasterize_mode} if cfg.rasterize_mode != "classic" else {}),
+            **({"absgrad": True} if cfg.absgrad else {}),
             "depth": ({"loss_from_step": cfg.depth_loss_start_iteration + 1 if cfg.use_depth_loss else None,
                        "one_compositing_pass": bool(cfg.fused_depth and device.type == "cuda"),
                        "mean_abs_error_start_end": [eval0["depth_err"], eval1["depth_err"]]} if cogs else None),
@@ -1402,6 +1417,7 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
     and quality numbers; every rank ends with identical parameters."""
     _check_config(cfg)
     _check_camera_optimizer(cfg, device, world)
+    _check_absgrad(cfg, device)
     cuda = device.type == "cuda"
     dp = world > 1 or (cfg.force_exchange and dist.is_available() and dist.is_initialized())
     if cfg.dataset is not None:
@@ -1437,7 +1453,7 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
         from gs_fused import densify_stats_ as kernel
     stats = DensifyState(model.num_points, device, max(cfg.width, cfg.height),
                          densify_until=rcfg.stop_split_at if cfg.densify else None, rank=rank, world=world,
-                         kernel=kernel, native=use_fused)
+                         kernel=kernel, native=use_fused, absgrad=cfg.absgrad and not use_fused)
     eval0 = evaluate(model, data, cfg, None if camera is None else camera.eval_cameras(data))
     pose0 = pose_errors(cfg, data, camera, device)
     exchange, sh_views = make_exchange(cfg, model, sharded is not None, dp)

@@ -714,9 +714,11 @@ def rasterize_forward_round(rnd: int, tile_bounds, img_size, gaussian_ids_sorted
 
 def rasterize_backward_two(img_height, img_width, gaussian_ids_sorted, tile_bins, tile_bins2, idx_base2: int, xys,
                            conics, colors, extra, opacities, background, extra_background: float, final_Ts, final_idx,
-                           v_output, v_output_extra, v_output_alpha, accumulators: Optional[Tensor] = None):
+                           v_output, v_output_extra, v_output_alpha, accumulators: Optional[Tensor] = None,
+                           v_xy_abs: Optional[Tensor] = None):
     """``gsr_rasterize_backward_two``: the backward over two-round lists -> (v_xy, v_conic, v_colors, v_opacity)
-    or, with ``extra``, (v_xy, v_conic, v_colors, v_extra, v_opacity)."""
+    or, with ``extra``, (v_xy, v_conic, v_colors, v_extra, v_opacity).  ``v_xy_abs`` ([N,2], optional): overwritten
+    with the absgrad (``gsr_rasterize_backward_two_abs``)."""
     v_output = _check(v_output.contiguous(), "v_output", _f32)
     if v_output_alpha is not None:
         v_output_alpha = _check(v_output_alpha.contiguous(), "v_output_alpha", _f32)
@@ -728,7 +730,8 @@ def rasterize_backward_two(img_height, img_width, gaussian_ids_sorted, tile_bins
         zeroed = accumulators is not None
         v_xy, v_conic, v_colors, v_opacity, v_extra = _carve_accumulators(accumulators, n, 3, extra is not None, dev)
         nt = ((img_width + 15) // 16) * ((img_height + 15) // 16)
-        _call("gsr_rasterize_backward_two", C.c_uint(img_height), C.c_uint(img_width), C.c_int(n),
+        v_xy_abs = _check_absgrad(v_xy_abs, n, dev)
+        _call("gsr_rasterize_backward_two" if v_xy_abs is None else "gsr_rasterize_backward_two_abs", C.c_uint(img_height), C.c_uint(img_width), C.c_int(n),
               _ptr(gaussian_ids_sorted), _ptr(tile_bins), _ptr(tile_bins2), C.c_int(int(idx_base2)), _ptr(xys),
               _ptr(conics), _ptr(colors), _ptr(extra) if extra is not None else None, _ptr(opacities),
               _ptr(background), C.c_float(extra_background), _ptr(final_Ts), _ptr(final_idx), _ptr(v_output),
@@ -736,10 +739,21 @@ def rasterize_backward_two(img_height, img_width, gaussian_ids_sorted, tile_bins
               _ptr(v_output_alpha) if v_output_alpha is not None else None, _ptr(v_xy), _ptr(v_conic), _ptr(v_colors),
               _ptr(v_extra) if v_extra is not None else None, _ptr(v_opacity),
               C.c_int(deep_tile_threshold(tile_bins.shape[0] * 400, nt, backward=True)), C.c_int(1 if zeroed else 0),
-              _stream(dev))
+              *(() if v_xy_abs is None else (_ptr(v_xy_abs),)), _stream(dev))
     if extra is not None:
         return v_xy, v_conic, v_colors, v_extra, v_opacity
     return v_xy, v_conic, v_colors, v_opacity
+
+
+def _check_absgrad(v_xy_abs: Optional[Tensor], n: int, dev) -> Optional[Tensor]:
+    """``v_xy_abs``: None, or the caller's [n,2] float32 output of the ``gsr_rasterize_backward_*abs`` entries (a
+    contiguous view of a larger allocation will do: exactly 2 n floats are written)."""
+    if v_xy_abs is None:
+        return None
+    _check(v_xy_abs, "v_xy_abs", _f32)
+    if tuple(v_xy_abs.shape) != (n, 2) or v_xy_abs.device != dev:
+        raise RuntimeError("v_xy_abs must have dimensions (num_points, 2) on the inputs' device")
+    return v_xy_abs
 
 
 def _raster_inputs(gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, background):
@@ -1241,9 +1255,11 @@ def rasterize_forward_rgbd(tile_bounds, img_size, gaussian_ids_sorted, tile_bins
 
 def rasterize_backward_rgbd(img_height, img_width, gaussian_ids_sorted, tile_bins, xys, conics, colors, extra,
                             opacities, background, extra_background, final_Ts, final_idx, v_output,
-                            v_output_extra, v_output_alpha, accumulators: Optional[Tensor] = None):
+                            v_output_extra, v_output_alpha, accumulators: Optional[Tensor] = None,
+                            v_xy_abs: Optional[Tensor] = None):
     """-> (v_xy, v_conic, v_colors, v_extra [N], v_opacity [N,1]); ``gsr_rasterize_backward_rgbd``.
-    ``accumulators``: ``backward_accumulators(n, 4, dev)`` already cleared by the forward launch."""
+    ``accumulators``: ``backward_accumulators(n, 4, dev)`` already cleared by the forward launch.
+    ``v_xy_abs`` ([N,2], optional): overwritten with the absgrad."""
     _raster_inputs(gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, background)
     _check(extra, "extra", _f32)
     v_output = _check(v_output.contiguous(), "v_output", _f32)
@@ -1257,16 +1273,19 @@ def rasterize_backward_rgbd(img_height, img_width, gaussian_ids_sorted, tile_bin
         _composite16_backward(img_height, img_width, n, gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities,
                               background, final_Ts, final_idx, v_output, v_output_alpha, v_xy, v_conic, v_colors,
                               v_opacity, accumulators is not None, dev, extra=extra, extra_background=extra_background,
-                              v_output_extra=v_output_extra, v_extra=v_extra)
+                              v_output_extra=v_output_extra, v_extra=v_extra, v_xy_abs=v_xy_abs)
     return v_xy, v_conic, v_colors, v_extra, v_opacity
 
 
 def rasterize_backward_det(img_height, img_width, gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities,
                            background, final_Ts, final_idx, v_output, v_output_alpha, order, cum_sorted, slot_of_entry,
-                           extra=None, extra_background: float = 0.0, v_output_extra=None):
+                           extra=None, extra_background: float = 0.0, v_output_extra=None,
+                           v_xy_abs: Optional[Tensor] = None):
     """``gsr_rasterize_backward_det``: the compositing backward with a fixed summation order
     (bit-identical gradients from run to run) -> (v_xy, v_conic, v_colors, v_opacity [N,1]) or,
-    with ``extra`` / ``v_output_extra``, (v_xy, v_conic, v_colors, v_extra [N], v_opacity)."""
+    with ``extra`` / ``v_output_extra``, (v_xy, v_conic, v_colors, v_extra [N], v_opacity).
+    ``v_xy_abs`` ([N,2], optional): overwritten with the absgrad, bit-reproducible as well
+    (``gsr_rasterize_backward_det_abs``)."""
     _raster_inputs(gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, background)
     for t, nm in ((order, "order"), (cum_sorted, "cum_sorted"), (slot_of_entry, "slot_of_entry")):
         _check(t, nm, _i32)
@@ -1292,12 +1311,13 @@ def rasterize_backward_det(img_height, img_width, gaussian_ids_sorted, tile_bins
         v_extra = torch.empty((n,), dtype=_f32, device=dev) if rgbd else None
         nbytes = int(_lib().gsr_rasterize_backward_det_workspace_bytes(C.c_int(L)))
         ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
-        _call("gsr_rasterize_backward_det", C.c_uint(img_height), C.c_uint(img_width), C.c_int(n), C.c_int(L),
+        v_xy_abs = _check_absgrad(v_xy_abs, n, dev)
+        _call("gsr_rasterize_backward_det" if v_xy_abs is None else "gsr_rasterize_backward_det_abs", C.c_uint(img_height), C.c_uint(img_width), C.c_int(n), C.c_int(L),
               _ptr(gaussian_ids_sorted), _ptr(tile_bins), _ptr(xys), _ptr(conics), _ptr(colors), _o(extra),
               _ptr(opacities), _ptr(background), C.c_float(extra_background), _ptr(final_Ts), _ptr(final_idx),
               _ptr(v_output), _o(v_output_extra), _o(v_output_alpha), _ptr(order), _ptr(cum_sorted), C.c_int(bands),
               _ptr(slot_of_entry), _ptr(ws), C.c_size_t(nbytes), _ptr(v_xy), _ptr(v_conic), _ptr(v_colors),
-              _o(v_extra), _ptr(v_opacity), _stream(dev))
+              _o(v_extra), _ptr(v_opacity), *(() if v_xy_abs is None else (_ptr(v_xy_abs),)), _stream(dev))
     if rgbd:
         return v_xy, v_conic, v_colors, v_extra, v_opacity
     return v_xy, v_conic, v_colors, v_opacity
@@ -1328,27 +1348,35 @@ def _carve_accumulators(flat: Optional[Tensor], n: int, channels: int, with_extr
 def _composite16_backward(img_height, img_width, n: int, gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities,
                           background, final_Ts, final_idx, v_output, v_output_alpha, v_xy, v_conic, v_colors, v_opacity,
                           zeroed: bool, dev, *, extra=None, extra_background: float = 0.0, v_output_extra=None,
-                          v_extra=None) -> None:
+                          v_extra=None, v_xy_abs: Optional[Tensor] = None) -> None:
     """The one call of ``gsr_rasterize_backward_seg`` -- the 16-px, 3-channel compositing backward, with or without
     the ``extra`` channel.  The entry cuts the deep lists into the runs of :func:`depth_segments` where that gives any,
-    and is ``gsr_rasterize_backward_ex`` / ``_rgbd`` where not.  ``zeroed``: the accumulators are cleared already."""
+    and is ``gsr_rasterize_backward_ex`` / ``_rgbd`` where not.  ``zeroed``: the accumulators are cleared already.
+    ``v_xy_abs`` ([n,2]): ``gsr_rasterize_backward_abs`` instead -- the same call, which also overwrites it with the
+    absgrad."""
     _o = lambda t: None if t is None else _ptr(t)  # noqa: E731
     tb = ((int(img_width) + 15) // 16, (int(img_height) + 15) // 16)
     entries, tiles = gaussian_ids_sorted.numel(), tb[0] * tb[1]
     segs, seg_min = depth_segments(entries, tiles)
     ws = torch.empty(((segs - 1) * int(img_height) * int(img_width), 2), dtype=_f32, device=dev) if segs > 1 else None
-    _call("gsr_rasterize_backward_seg", C.c_uint(img_height), C.c_uint(img_width), C.c_int(n),
-          _ptr(gaussian_ids_sorted), _ptr(tile_bins), _ptr(xys), _ptr(conics), _ptr(colors), _o(extra), _ptr(opacities),
+    v_xy_abs = _check_absgrad(v_xy_abs, n, dev)
+    _call("gsr_rasterize_backward_seg" if v_xy_abs is None else "gsr_rasterize_backward_abs", C.c_uint(img_height),
+          C.c_uint(img_width), C.c_int(n), _ptr(gaussian_ids_sorted), _ptr(tile_bins), _ptr(xys), _ptr(conics), _ptr(colors), _o(extra), _ptr(opacities),
           _ptr(background), C.c_float(extra_background), _ptr(final_Ts), _ptr(final_idx), _ptr(v_output),
           _o(v_output_extra), _o(v_output_alpha), _ptr(v_xy), _ptr(v_conic), _ptr(v_colors), _o(v_extra), _ptr(v_opacity),
           C.c_int(backward_order(tile_bins, entries, tiles, tb)), C.c_int(1 if zeroed else 0),
           C.c_int(segs if ws is not None else 0), C.c_int(seg_min), _o(ws),
-          C.c_size_t(ws.numel() * 4 if ws is not None else 0), _stream(dev))
+          C.c_size_t(ws.numel() * 4 if ws is not None else 0), *(() if v_xy_abs is None else (_ptr(v_xy_abs),)),
+          _stream(dev))
 
 
 def _rasterize_backward(img_height, img_width, block_width, gaussian_ids_sorted, tile_bins, xys,
                         conics, colors, opacities, background, final_Ts, final_idx, v_output,
-                        v_output_alpha, nd: bool, accumulators: Optional[Tensor] = None, trusted: bool = False):
+                        v_output_alpha, nd: bool, accumulators: Optional[Tensor] = None, trusted: bool = False,
+                        v_xy_abs: Optional[Tensor] = None):
+    if v_xy_abs is not None and (nd or block_width != 16 or colors.size(1) != 3):
+        raise ValueError("absgrad (v_xy_abs) needs block_width 16 and 3 colour channels: the generic kernels do not "
+                         "compute it")
     if not trusted:  # (trusted: everything but the two cotangents went through the forward's checks)
         _raster_inputs(gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, background)
         if not nd and colors.size(1) != 3:
@@ -1367,7 +1395,7 @@ def _rasterize_backward(img_height, img_width, block_width, gaussian_ids_sorted,
         if tile16:
             _composite16_backward(img_height, img_width, n, gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities,
                                   background, final_Ts, final_idx, v_output, v_output_alpha, v_xy, v_conic, v_colors,
-                                  v_opacity, zeroed, dev)
+                                  v_opacity, zeroed, dev, v_xy_abs=v_xy_abs)
         else:
             sizes = (C.c_uint(img_height), C.c_uint(img_width), C.c_uint(block_width))
             args = (C.c_int(n), _ptr(gaussian_ids_sorted), _ptr(tile_bins), _ptr(xys), _ptr(conics), _ptr(colors),
@@ -1385,13 +1413,16 @@ def _rasterize_backward(img_height, img_width, block_width, gaussian_ids_sorted,
 
 def rasterize_backward(img_height, img_width, block_width, gaussian_ids_sorted, tile_bins, xys,
                        conics, colors, opacities, background, final_Ts, final_idx, v_output,
-                       v_output_alpha, accumulators: Optional[Tensor] = None, trusted: bool = False):
+                       v_output_alpha, accumulators: Optional[Tensor] = None, trusted: bool = False,
+                       v_xy_abs: Optional[Tensor] = None):
     """-> (v_xy, v_conic, v_colors, v_opacity [N,1]);
     replaces ``rasterize_backward_tensor`` (bindings.cu:476-528).  ``accumulators``: a
-    :func:`backward_accumulators` buffer already cleared by :func:`rasterize_forward_ex`."""
+    :func:`backward_accumulators` buffer already cleared by :func:`rasterize_forward_ex`.
+    ``v_xy_abs`` ([N,2], optional; block_width 16): overwritten with the absgrad (``gsr_rasterize_backward_abs``)."""
     return _rasterize_backward(img_height, img_width, block_width, gaussian_ids_sorted, tile_bins,
                                xys, conics, colors, opacities, background, final_Ts, final_idx,
-                               v_output, v_output_alpha, nd=False, accumulators=accumulators, trusted=trusted)
+                               v_output, v_output_alpha, nd=False, accumulators=accumulators, trusted=trusted,
+                               v_xy_abs=v_xy_abs)
 
 
 def nd_rasterize_backward(img_height, img_width, block_width, gaussian_ids_sorted, tile_bins, xys,

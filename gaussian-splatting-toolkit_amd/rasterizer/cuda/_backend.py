@@ -55,6 +55,9 @@ SYMBOLS = (
     "gsr_rasterize_forward_seg_workspace_bytes",
     "gsr_rasterize_backward_seg",
     "gsr_rasterize_backward_seg_workspace_bytes",
+    "gsr_rasterize_backward_abs",
+    "gsr_rasterize_backward_two_abs",
+    "gsr_rasterize_backward_det_abs",
     "gsr_rasterize_forward_nd",
     "gsr_rasterize_backward_nd",
     "gsr_cov2d_bounds",

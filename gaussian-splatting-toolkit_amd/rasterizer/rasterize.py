@@ -455,6 +455,15 @@ def _same_reach_inputs(conics, opacity, reach):
     return verdict
 
 
+class AbsgradOf:
+    """The tensor the caller passed as ``xys`` with ``absgrad=True``: every backward of that call sets its attribute
+    ``absgrad`` ([N,2]: the sum over the pixels of |dL/dxy| per component, include/gsraster.h) -- gsplat's convention.
+    (An object, not the tensor: an argument of ``Function.apply`` that is no tensor stays out of the graph.)"""
+
+    def __init__(self, tensor: Tensor):
+        self.tensor = tensor
+
+
 def rasterize_gaussians(
     xys: Tensor,
     depths: Tensor,
@@ -468,10 +477,16 @@ def rasterize_gaussians(
     block_width: int,
     background: Optional[Tensor] = None,
     return_alpha: Optional[bool] = False,
+    absgrad: bool = False,
 ) -> Tensor:
     """Sort the Gaussians per tile by depth and composite them front to back.
 
     Differentiable w.r.t. ``xys``, ``conics``, ``colors`` and ``opacity``.
+
+    ``absgrad`` (block_width 16, 3 channels): every backward also leaves ``xys.absgrad`` [N,2] on the tensor passed
+    as ``xys`` -- per Gaussian the sum over the pixels that composite it of |dL/dxy|, the absolute value taken per
+    pixel and per component (``xys.grad`` is the signed sum, which cancels under a large Gaussian).  Overwritten by
+    each backward; zeros for a view with nothing on screen.
 
     Args:
         xys [N,2], depths [N], radii [N] int32, conics [N,3], num_tiles_hit [N]
@@ -497,11 +512,14 @@ def rasterize_gaussians(
         raise ValueError("xys must have dimensions (N, 2)")
     if colors.ndimension() != 2:
         raise ValueError("colors must have dimensions (N, D)")
+    if absgrad and (block_width != 16 or colors.shape[-1] != 3):
+        raise ValueError("absgrad=True needs block_width 16 and 3 colour channels (the generic kernels do not "
+                         "compute it)")
 
     return _RasterizeGaussians.apply(
         xys.contiguous(), depths.contiguous(), radii.contiguous(), conics.contiguous(),
         num_tiles_hit.contiguous(), colors.contiguous(), opacity.contiguous(), img_height,
-        img_width, block_width, background.contiguous(), return_alpha,
+        img_width, block_width, background.contiguous(), return_alpha, AbsgradOf(xys) if absgrad else None,
     )
 
 
@@ -777,7 +795,7 @@ def _build_fresh(xys, depths, radii, conics, num_tiles_hit, opacity, tile_bounds
 class _RasterizeGaussians(Function):
     @staticmethod
     def forward(ctx, xys, depths, radii, conics, num_tiles_hit, colors, opacity, img_height,
-                img_width, block_width, background=None, return_alpha=False):
+                img_width, block_width, background=None, return_alpha=False, absgrad_of=None):
         tile_bounds = (
             (img_width + block_width - 1) // block_width,
             (img_height + block_width - 1) // block_width,
@@ -884,6 +902,7 @@ class _RasterizeGaussians(Function):
         ctx.num_intersects = num_intersects
         ctx.block_width = block_width
         ctx.accumulators = acc  # cleared by the forward launch; used (once) by the backward
+        ctx.absgrad_of = absgrad_of
         ctx.save_for_backward(gaussian_ids_sorted, tile_bins, xys, conics, colors, opacity,
                               background, final_Ts, final_idx)
 
@@ -901,6 +920,11 @@ class _RasterizeGaussians(Function):
         if v_out_img is None:  # only the alpha output was used
             v_out_img = torch.zeros(ctx.img_height, ctx.img_width, colors.shape[-1], device=xys.device)
 
+        v_xy_abs = None
+        if ctx.absgrad_of is not None:
+            v_xy_abs = (torch.zeros if ctx.num_intersects < 1 else torch.empty)(
+                (xys.size(0), 2), dtype=torch.float32, device=xys.device)
+            ctx.absgrad_of.tensor.absgrad = v_xy_abs
         if ctx.num_intersects < 1:
             v_xy = torch.zeros_like(xys)
             v_conic = torch.zeros_like(conics)
@@ -912,18 +936,18 @@ class _RasterizeGaussians(Function):
                 v_xy, v_conic, v_colors, v_opacity = _C.rasterize_backward_two(
                     ctx.img_height, ctx.img_width, gaussian_ids_sorted, tile_bins, ctx.two[0], ctx.two[1], xys, conics,
                     colors, None, opacity, background, 0.0, final_Ts, final_idx, v_out_img, None, v_out_alpha,
-                    accumulators=acc)
+                    accumulators=acc, v_xy_abs=v_xy_abs)
             elif ctx.det is not None:
                 v_xy, v_conic, v_colors, v_opacity = _C.rasterize_backward_det(
                     ctx.img_height, ctx.img_width, gaussian_ids_sorted, tile_bins, xys, conics, colors, opacity,
-                    background, final_Ts, final_idx, v_out_img, v_out_alpha, *ctx.det)
+                    background, final_Ts, final_idx, v_out_img, v_out_alpha, *ctx.det, v_xy_abs=v_xy_abs)
             else:
                 acc, ctx.accumulators = ctx.accumulators, None  # a second backward (retain_graph) clears its own
                 if colors.shape[-1] == 3:
                     v_xy, v_conic, v_colors, v_opacity = _C.rasterize_backward(
                         ctx.img_height, ctx.img_width, ctx.block_width, gaussian_ids_sorted, tile_bins, xys,
                         conics, colors, opacity, background, final_Ts, final_idx, v_out_img, v_out_alpha,
-                        accumulators=acc, trusted=True)
+                        accumulators=acc, trusted=True, v_xy_abs=v_xy_abs)
                 else:
                     v_xy, v_conic, v_colors, v_opacity = _C.nd_rasterize_backward(
                         ctx.img_height, ctx.img_width, ctx.block_width, gaussian_ids_sorted, tile_bins, xys,
@@ -931,4 +955,4 @@ class _RasterizeGaussians(Function):
             v_opacity = v_opacity.reshape(opacity.shape)
 
         # xys, depths, radii, conics, num_tiles_hit, colors, opacity, then 5 non-differentiable
-        return (v_xy, None, None, v_conic, None, v_colors, v_opacity) + (None,) * 5
+        return (v_xy, None, None, v_conic, None, v_colors, v_opacity) + (None,) * 6

@@ -503,6 +503,50 @@ int gsr_rasterize_backward_seg(unsigned img_height, unsigned img_width, int num_
                                int segment_min_entries, void *workspace, size_t workspace_bytes,
                                gsr_stream_t stream);
 
+/* ---- absgrad: per-pixel |dL/dxy| sums (AbsGS; `absgrad` of gsplat) ---------------------------------------------
+ * v_xy is a SIGNED sum over the pixels a Gaussian covers: where the pixels of a large Gaussian pull its centre in
+ * opposite directions the sum cancels, and densification -- which thresholds its norm -- never splits it.  The three
+ * entries below are gsr_rasterize_backward_seg / _two / _det with one more output, v_xy_abs [N,2] float32:
+ *   v_xy_abs[g] = sum over every pixel p that composites g of |v_xy(p, g)|,
+ *   v_xy(p, g)  = v_sigma (a dx + b dy, b dx + c dy),  v_sigma = -opac vis v_alpha,  (dx, dy) = xy_g - pixel centre,
+ * the absolute value taken per component and per pixel, before any sum; same units as v_xy.  A pixel composites g
+ * under the backward's unchanged rule: g is in the tile's list at or before final_idx[p], sigma >= 0, and alpha
+ * (clamped at 0.99) is at least 1/255.  The call clears v_xy_abs itself (the forward's zero_ptr does not cover it,
+ * whatever accumulators_zeroed says); _det writes every element and its sums are bit-reproducible.
+ * v_xy_abs == NULL: the entry each one extends, launch for launch.  16 x 16 tiles, 3 colour channels (+ extra). */
+int gsr_rasterize_backward_abs(unsigned img_height, unsigned img_width, int num_points,
+                               const int32_t *gaussian_ids_sorted, const int32_t *tile_bins,
+                               const float *xys, const float *conics, const float *colors,
+                               const float *extra, const float *opacities, const float *background,
+                               float extra_background, const float *final_Ts, const int32_t *final_idx,
+                               const float *v_output, const float *v_output_extra,
+                               const float *v_output_alpha, float *v_xy, float *v_conic,
+                               float *v_colors, float *v_extra, float *v_opacity,
+                               int deep_tile_threshold, int accumulators_zeroed, int segments,
+                               int segment_min_entries, void *workspace, size_t workspace_bytes,
+                               float *v_xy_abs, gsr_stream_t stream);
+int gsr_rasterize_backward_two_abs(unsigned img_height, unsigned img_width, int num_points,
+                                   const int32_t *gaussian_ids_sorted, const int32_t *tile_bins,
+                                   const int32_t *tile_bins2, int idx_base2, const float *xys,
+                                   const float *conics, const float *colors, const float *extra,
+                                   const float *opacities, const float *background, float extra_background,
+                                   const float *final_Ts, const int32_t *final_idx, const float *v_output,
+                                   const float *v_output_extra, const float *v_output_alpha, float *v_xy,
+                                   float *v_conic, float *v_colors, float *v_extra, float *v_opacity,
+                                   int deep_tile_threshold, int accumulators_zeroed, float *v_xy_abs,
+                                   gsr_stream_t stream);
+int gsr_rasterize_backward_det_abs(
+    unsigned img_height, unsigned img_width, int num_points, int list_capacity,
+    const int32_t *gaussian_ids_sorted, const int32_t *tile_bins,
+    const float *xys, const float *conics, const float *colors,
+    const float *extra, const float *opacities, const float *background,
+    float extra_background, const float *final_Ts, const int32_t *final_idx,
+    const float *v_output, const float *v_output_extra,
+    const float *v_output_alpha, const int32_t *order,
+    const int32_t *cum_sorted, int num_bands, const int32_t *slot_of_entry,
+    void *workspace, size_t workspace_bytes, float *v_xy, float *v_conic,
+    float *v_colors, float *v_extra, float *v_opacity, float *v_xy_abs, gsr_stream_t stream);
+
 /* generic channel count; replace nd_rasterize_forward_tensor /
  * nd_rasterize_backward_tensor (bindings.cu:330-469), kernels
  * forward.cu:159-276 / backward.cu:23-131.  Accumulation is fp32 here (the
@@ -838,6 +882,10 @@ typedef struct gsr_view_grads {
    * gsr_rasterize_backward_det on the view's lists for a fixed summation order: that launch is skipped here
    * (v_img may then be NULL) and everything behind it runs as usual */
   int accumulators_final;
+  /* NULL, or [n,2]: the absgrad of gsr_rasterize_backward_abs.  The compositing backward of this call overwrites it
+   * (with accumulators_final the caller's gsr_rasterize_backward_det_abs has), and the statistics accumulate ITS
+   * norm into xys_grad_norm in place of v_xy's. */
+  float *v_xy_abs;
 } gsr_view_grads;
 
 int gsr_view_forward(const gsr_view_desc *view, gsr_stream_t stream);
