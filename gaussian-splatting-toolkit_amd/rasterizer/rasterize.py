@@ -18,7 +18,8 @@ the same memory), and an in-place update bumps the version and misses.
 import os
 import threading
 import time
-from typing import Optional
+from functools import partial
+from typing import NamedTuple, Optional
 
 import torch
 from torch import Tensor
@@ -30,13 +31,12 @@ from rasterizer.cuda import _tuning
 # One entry, shared by every thread of the process.  Readers take a SNAPSHOT under `_state_lock`
 # and writers replace all four fields under it, so forwards interleaved on one device (an
 # evaluation thread next to the training thread, side streams) each see a consistent entry; what
-# a forward needs later (the deterministic backward's `aux`) travels with the call, in
-# thread-local storage, never through this dictionary.
+# a forward needs later (the deterministic backward's `aux`) travels with the call, in the
+# `TileLists` record it was handed, never through this dictionary.
 _bin_cache = {"key": None, "value": None, "keepalive": None, "reach": None}
 # guards the list cache, the sizing dictionaries below (`_count_hint`, `_last_capacity`, `_two_hint`) and the pinned
 # slot pool; re-entrant: a hint update may hand a slot back to the pool
 _state_lock = threading.RLock()
-_tls = threading.local()
 # views whose device-sized lists came out too small and were built again (harness.train reports the delta per run)
 # list constructions by kind (tests and harness.train read these; never reset by the package):
 #   list_builds_exact / _device_sized   lists built inside rasterize_gaussians, sized by a read-back / by the previous view
@@ -57,11 +57,6 @@ def _cache_snapshot():
     with _state_lock:
         return dict(_bin_cache)
 
-
-def last_list_aux():
-    """(order, cum_sorted, slot_of_entry) of the lists the calling THREAD's last `build_tile_lists`
-    returned (deterministic mode; None otherwise)."""
-    return getattr(_tls, "aux", None)
 
 # Deterministic backward (include/gsraster.h, gsr_rasterize_backward_det): per-(tile, entry)
 # partials summed per Gaussian in a fixed order instead of float atomics -- bit-identical
@@ -264,7 +259,8 @@ def _two_round_plan_locked(device, num_points, tile_bounds, mode, asked=False):
 
 def _build_two_round(xys, depths, radii, conics, num_tiles_hit, opacity, tile_bounds, block_width, plan, remember,
                      round1, order_ready=None):
-    """-> (None, ids, bins1, finish); `round1(ids, bins1, tile_flags)` composites the prefix lists (raw state)."""
+    """-> (lists, finish) as `build_tile_lists`, `lists.bins` the first segment and `lists.aux` = ("two", bins2,
+    idx_base); `round1(ids, bins1, tile_flags)` composites the prefix lists (raw state)."""
     dev = xys.device
     n, n1, cap1, cap2 = xys.size(0), plan["n1"], plan["cap1"], plan["cap2"]
     if order_ready is not None:  # the depth order was built ahead of time on the side stream
@@ -287,8 +283,7 @@ def _build_two_round(xys, depths, radii, conics, num_tiles_hit, opacity, tile_bo
     _C.publish_int32(stats[:1], p4.buf)  # tiles with a live pixel after round 1
     p4.mark()
     p1.event = p2.event = p4.event
-    aux = ("two", bins2, cap1)
-    _tls.aux = aux
+    lists = TileLists(None, ids, bins1, ("two", bins2, cap1))
 
     def finish():
         c1, c2, unfinished = p1.resolve(), p2.resolve(), p4.resolve()
@@ -298,13 +293,13 @@ def _build_two_round(xys, depths, radii, conics, num_tiles_hit, opacity, tile_bo
             _note_count(xys.device, n, tile_bounds, note)
         if c1 > cap1 or c2 > cap2:  # a guess was too small: this view falls back to one exact round
             counters["list_rebuilds"] += 1
-            nn, i2, b2, _ = _build_fresh(xys, depths, radii, conics, num_tiles_hit, opacity, tile_bounds, block_width,
-                                         True, remember, speculate=False, round1=None)
-            return nn, i2, b2, True
-        remember(c1 + c2, ids, bins1, aux)
-        return c1 + c2, ids, bins1, False
+            return _build_fresh(xys, depths, radii, conics, num_tiles_hit, opacity, tile_bounds, block_width, True,
+                                remember, speculate=False)[0], True
+        done = lists._replace(num_intersects=c1 + c2)
+        remember(done)
+        return done, False
 
-    return None, ids, bins1, finish
+    return lists, finish
 
 
 def _two_round_feedback(plan, c1, c2, unfinished):
@@ -527,6 +522,38 @@ def _is_two(aux) -> bool:
     return isinstance(aux, tuple) and len(aux) == 3 and aux[0] == "two"
 
 
+class TileLists(NamedTuple):
+    """The lists of one view.  `aux` is what only some of them carry: ("two", bins2, idx_base) -- `bins` is then the
+    first of two segments -- or the deterministic backward's (order, cum_sorted, slot_of_entry)."""
+    num_intersects: Optional[int]  # None until `finish()` has read the count of device-sized lists
+    ids: Optional[Tensor]
+    bins: Optional[Tensor]
+    aux: Optional[tuple] = None
+
+    @property
+    def two(self) -> bool:
+        return _is_two(self.aux)
+
+
+def _finish_for(pending, capacity, lists, rebuild, on_overflow=None, *, note, remember):
+    """-> `finish()` of device-sized `lists` (room for `capacity` entries): reads the count (`pending.resolve()`),
+    notes it for the next view's sizing, and returns `(lists with the count, False)` after `remember`-ing them --
+    or, where the guess was too small, `(rebuild(count), True)`: lists built again, which `rebuild` remembers."""
+    def finish():
+        num_intersects = pending.resolve()
+        note(num_intersects)
+        if num_intersects > capacity:
+            counters["list_rebuilds"] += 1
+            if on_overflow is not None:
+                on_overflow()
+            return rebuild(num_intersects), True
+        done = lists._replace(num_intersects=num_intersects)
+        remember(done)
+        return done, False
+
+    return finish
+
+
 class FusedForward:
     """What `build_tile_lists` needs to run the compositing in the SAME native call as the list construction
     (`gsr_rasterize_gaussians_forward`, 16x16 tiles / 3 channels): the colours, background and output wishes of
@@ -543,24 +570,23 @@ def build_tile_lists(xys, depths, radii, conics, num_tiles_hit, opacity, img_hei
                      round1=None, fuse: Optional[FusedForward] = None):
     """The per-tile depth-sorted lists every compositing call walks.
 
-    -> ``(num_intersects, gaussian_ids_sorted, tile_bins, finish)``.  Either the count is
-    known (``finish is None``; a cache hit, the first view, or a tile grid the
-    device-sized path does not serve), or the lists were sized from the previous view
-    and ``num_intersects is None``: enqueue the compositing, then call ``finish()`` ->
-    ``(num_intersects, gaussian_ids_sorted, tile_bins, rebuilt)``; with ``rebuilt`` the
-    guess was too small, the lists were built again and the compositing must be repeated.
-    The result is cached for the next call with the same geometry (the depth pass).
+    -> ``(lists, finish)``, ``lists`` a `TileLists` ``(num_intersects, ids, bins, aux)``.  Either the count is
+    known (``finish is None``; a cache hit, the first view, or a tile grid the device-sized path does not
+    serve), or the lists were sized from the previous view and ``lists.num_intersects is None``: enqueue the
+    compositing, then call ``finish()`` -> ``(lists, rebuilt)``, now with the count; with ``rebuilt`` the
+    guess was too small, these are other lists (``aux`` included), built again, and the compositing must be
+    repeated.  The record is cached for the next call with the same geometry (the depth pass).
+    `composite_lists` below is the caller's half of this protocol.
 
     ``round1(ids, bins1, tile_flags)`` (optional): the caller can composite in two rounds
-    (``_C.rasterize_forward_round``).  On deep scenes the lists then come in two segments: ``bins`` is the
-    first, ``last_list_aux()`` returns ``("two", bins2, idx_base)``, and ``round1`` has already been called
+    (``_C.rasterize_forward_round``).  On deep scenes the lists then come in two segments (``lists.two``):
+    ``bins`` is the first, ``aux`` is ``("two", bins2, idx_base)``, and ``round1`` has already been called
     on the first segment when this function returns -- the caller runs round 2 (and, for lists from the
     cache, both rounds).
 
     ``fuse`` (optional, `FusedForward`): where the lists are device-sized single-round ones the compositing runs in
     the same native call and ``fuse.outputs`` holds its results; the caller composites itself when it is None."""
     num_points = xys.size(0)
-    _tls.aux = None  # (what the PREVIOUS call of this thread left: every path below sets its own)
     tile_bounds = ((img_width + block_width - 1) // block_width, (img_height + block_width - 1) // block_width, 1)
     key = _geometry_key(xys, depths, radii, num_tiles_hit, img_height, img_width, block_width)
     # With 16x16 tiles the lists leave out the (Gaussian, tile) pairs that cannot
@@ -570,15 +596,16 @@ def build_tile_lists(xys, depths, radii, conics, num_tiles_hit, opacity, img_hei
     # conics and opacity.
     exact = block_width == 16
 
-    def remember(num_intersects, ids, bins, aux=None):
-        entry = {"key": key, "value": (num_intersects, ids, bins, aux),
+    def remember(lists):
+        entry = {"key": key, "value": lists,
                  "keepalive": tuple(t.detach() for t in (xys, depths, radii, num_tiles_hit)),
                  "reach": (conics.detach(), opacity.detach(), conics._version, opacity._version,
                            _producer_signature(conics), _producer_signature(opacity))}
         with _state_lock:
             _bin_cache.update(entry)
-        _tls.aux = aux
 
+    fresh = partial(_build_fresh, xys, depths, radii, conics, num_tiles_hit, opacity, tile_bounds, block_width, exact,
+                    remember)
     order_ready = None
     if exact:
         _note_opacity_recipe(xys.device, opacity)
@@ -600,25 +627,15 @@ def build_tile_lists(xys, depths, radii, conics, num_tiles_hit, opacity, img_hei
             if "ids" in ahead and ("aux" in ahead) == _deterministic["on"] and _ahead_matches(conics, opacity, ahead):
                 # this view's lists were built on the side stream while the caller was busy (or blocked)
                 counters["ahead_hits"] += 1
-                ids, bins, pending, capacity = ahead["ids"], ahead["bins"], ahead["pending"], ahead["capacity"]
                 # (ids / bins come from the side stream's pool and are read on the caller's: no `record_stream` --
                 # memory goes back to that pool only when autograd drops them, and the pool hands it out again only
                 # inside `speculate_lists`, behind `side.wait_stream(main)`)
+                lists = TileLists(None, ahead["ids"], ahead["bins"], ahead.get("aux"))
                 if fuse is not None:
                     fuse.prealloc = ahead.get("outs")
-
-                def finish_ahead():
-                    num_intersects = pending.resolve()
-                    _note_count(xys.device, num_points, tile_bounds, num_intersects)
-                    if num_intersects > capacity:  # the guess was too small: build the lists again, sized exactly
-                        counters["list_rebuilds"] += 1
-                        n, i2, b2, _ = _build_fresh(xys, depths, radii, conics, num_tiles_hit, opacity, tile_bounds,
-                                                    block_width, exact, remember, speculate=False)
-                        return n, i2, b2, True
-                    remember(num_intersects, ids, bins, ahead.get("aux"))
-                    return num_intersects, ids, bins, False
-
-                return None, ids, bins, finish_ahead
+                return lists, _finish_for(ahead["pending"], ahead["capacity"], lists,
+                                          lambda _count: fresh(speculate=False)[0], remember=remember,
+                                          note=partial(_note_count, xys.device, num_points, tile_bounds))
             if "order" in ahead:
                 order_ready = ahead["order"]
                 order_ready.record_stream(main)
@@ -626,7 +643,7 @@ def build_tile_lists(xys, depths, radii, conics, num_tiles_hit, opacity, img_hei
                 counters["ahead_misses"] += 1  # other opacities than predicted: the lists are of no use
 
     snap = _cache_snapshot()
-    if snap["key"] == key and round1 is None and _is_two(snap["value"][3]):
+    if snap["key"] == key and round1 is None and snap["value"].two:
         # two-segment lists (a deep scene's RGB pass) cached, but THIS caller composites one segment only (N-D
         # colours, another block width ...): walking `bins1` alone would silently drop everything behind the
         # prefix -- build single-round lists
@@ -635,9 +652,8 @@ def build_tile_lists(xys, depths, radii, conics, num_tiles_hit, opacity, img_hei
         same = _same_reach_inputs(conics, opacity, snap["reach"]) if exact else True
         cached = snap["value"]
         if same is True:
-            _tls.aux = cached[3]
-            return cached[:3] + (None,)
-        if same == "verify" and cached[0] >= 1:
+            return cached, None
+        if same == "verify" and cached.num_intersects >= 1:
             # use the cached lists now; compare the values on the device and look at the
             # answer once the compositing is queued (no host wait in front of the GPU work)
             c0, o0 = snap["reach"][:2]
@@ -648,18 +664,14 @@ def build_tile_lists(xys, depths, radii, conics, num_tiles_hit, opacity, img_hei
 
             def verify():
                 if not check.resolve():
-                    _tls.aux = cached[3]
-                    return cached[:3] + (False,)
-                n, ids, bins, fin = _build_fresh(xys, depths, radii, conics, num_tiles_hit, opacity, tile_bounds,
-                                                 block_width, exact, remember, round1=None)
+                    return cached, False
+                lists, fin = fresh(round1=None)
                 if fin is not None:
-                    n, ids, bins, _ = fin()
-                return n, ids, bins, True
+                    lists, _ = fin()
+                return lists, True
 
-            _tls.aux = cached[3]
-            return None, cached[1], cached[2], verify
-    return _build_fresh(xys, depths, radii, conics, num_tiles_hit, opacity, tile_bounds, block_width, exact, remember,
-                        round1=round1, fuse=fuse, order_ready=order_ready)
+            return cached._replace(num_intersects=None), verify
+    return fresh(round1=round1, fuse=fuse, order_ready=order_ready)
 
 
 def _build_fresh(xys, depths, radii, conics, num_tiles_hit, opacity, tile_bounds, block_width, exact, remember,
@@ -680,6 +692,11 @@ def _build_fresh(xys, depths, radii, conics, num_tiles_hit, opacity, tile_bounds
     det = _deterministic["on"] and exact and os.environ.get("GSR_TILE_SORT", "s")[:1] not in ("r", "m")
     banded = exact and (det or os.environ.get("GSR_TILE_SORT", "")[:1] == "b")
     capacity = _speculative_capacity(xys.device, num_points, tile_bounds, exact) if speculate else None
+    note = partial(_note_count, xys.device, num_points, tile_bounds)
+
+    def rebuild(_count):  # a guess was too small: the lists again, sized exactly
+        return _build_fresh(xys, depths, radii, conics, num_tiles_hit, opacity, tile_bounds, block_width, exact,
+                            remember, speculate=False)[0]
 
     if fuse is not None and exact and capacity is not None and not banded and not det and \
             int(_tuning.get("one_call")):
@@ -696,19 +713,11 @@ def _build_fresh(xys, depths, radii, conics, num_tiles_hit, opacity, tile_bounds
         if order_ready is not None:
             counters["ahead_orders_used"] += 1
 
-        def finish_one():
-            num_intersects = pending.resolve()
-            _note_count(xys.device, num_points, tile_bounds, num_intersects)
-            if num_intersects > capacity:  # the guess was too small: build the lists again, sized exactly
-                counters["list_rebuilds"] += 1
-                fuse.outputs = None
-                n, i2, b2, _ = _build_fresh(xys, depths, radii, conics, num_tiles_hit, opacity, tile_bounds,
-                                            block_width, exact, remember, speculate=False)
-                return n, i2, b2, True
-            remember(num_intersects, ids, bins, None)
-            return num_intersects, ids, bins, False
+        def drop_outputs():  # (composited from lists that were cut short)
+            fuse.outputs = None
 
-        return None, ids, bins, finish_one
+        lists = TileLists(None, ids, bins, None)
+        return lists, _finish_for(pending, capacity, lists, rebuild, drop_outputs, note=note, remember=remember)
 
     if exact and capacity is not None and not banded and \
             not _C.lists_need_counts(num_points, capacity, tile_bounds, device_sized=True, want_slots=det):
@@ -725,18 +734,8 @@ def _build_fresh(xys, depths, radii, conics, num_tiles_hit, opacity, tile_bounds
         pending.mark()
         counters["list_builds_device_sized"] += 1
 
-        def finish_lean():
-            num_intersects = pending.resolve()
-            _note_count(xys.device, num_points, tile_bounds, num_intersects)
-            if num_intersects > capacity:  # the guess was too small: build the lists again, sized exactly
-                counters["list_rebuilds"] += 1
-                n, i2, b2, _ = _build_fresh(xys, depths, radii, conics, num_tiles_hit, opacity, tile_bounds,
-                                            block_width, exact, remember, speculate=False)
-                return n, i2, b2, True
-            remember(num_intersects, ids, bins, None)
-            return num_intersects, ids, bins, False
-
-        return None, ids, bins, finish_lean
+        lists = TileLists(None, ids, bins, None)
+        return lists, _finish_for(pending, capacity, lists, rebuild, note=note, remember=remember)
 
     tiles, records = num_tiles_hit, None
     if exact:
@@ -747,11 +746,7 @@ def _build_fresh(xys, depths, radii, conics, num_tiles_hit, opacity, tile_bounds
     def build(count, device_sized=False):
         out = _C.bin_sorted(num_points, count, order, cum_sorted, xys, radii, tile_bounds, block_width, records,
                             device_sized=device_sized, want_slots=det)
-        if det:
-            build.aux = (order, cum_sorted, out[2])
-        return out[0], out[1]
-
-    build.aux = None
+        return TileLists(None if device_sized else count, out[0], out[1], (order, cum_sorted, out[2]) if det else None)
 
     if capacity is None:
         # the one host sync (utils.py:124).  The count is summed in 64 bits: the int32 prefix
@@ -761,11 +756,11 @@ def _build_fresh(xys, depths, radii, conics, num_tiles_hit, opacity, tile_bounds
         if num_intersects >= 2**31:
             raise RuntimeError(f"rasterize_gaussians: {num_intersects} (Gaussian, tile) intersections do not fit the "
                                f"int32 lists (the reference's cum_tiles_hit is int32 as well)")
-        _note_count(xys.device, num_points, tile_bounds, num_intersects)
-        ids, bins = build(num_intersects) if num_intersects >= 1 else (None, None)
+        note(num_intersects)
+        lists = build(num_intersects) if num_intersects >= 1 else TileLists(0, None, None, None)
         counters["list_builds_exact"] += 1
-        remember(num_intersects, ids, bins, build.aux)
-        return num_intersects, ids, bins, None
+        remember(lists)
+        return lists, None
 
     # Size the lists from the previous view instead of waiting for the count to reach the
     # host (utils.py:124).  The count goes to the host right behind the depth-order scan,
@@ -774,22 +769,94 @@ def _build_fresh(xys, depths, radii, conics, num_tiles_hit, opacity, tile_bounds
     pending = _PendingCount(xys.device)
     _C.publish_int32(cum_sorted[-1:], pending.buf)
     pending.mark()
-    ids, bins = build(capacity, device_sized=True)
+    lists = build(capacity, device_sized=True)
     counters["list_builds_device_sized"] += 1
 
-    def finish():
-        nonlocal ids, bins
-        num_intersects = pending.resolve()
-        _note_count(xys.device, num_points, tile_bounds, num_intersects)
-        rebuilt = num_intersects > capacity  # the guess was too small: build the lists again
-        if rebuilt:
-            counters["list_rebuilds"] += 1
-            counters["list_builds_exact"] += 1
-            ids, bins = build(num_intersects)
-        remember(num_intersects, ids, bins, build.aux)
-        return num_intersects, ids, bins, rebuilt
+    def build_again(count):  # from the same counts and depth order
+        counters["list_builds_exact"] += 1
+        again = build(count)
+        remember(again)
+        return again
 
-    return None, ids, bins, finish
+    return lists, _finish_for(pending, capacity, lists, build_again, note=note, remember=remember)
+
+
+def composite_lists(xys, depths, radii, conics, num_tiles_hit, opacity, img_height, img_width, block_width, composite,
+                    round1=None, round2=None, fuse: Optional[FusedForward] = None):
+    """The forward both rasterize ops share: the view's lists (`build_tile_lists`) and one walk over them ->
+    ``(lists, outputs)``, ``outputs`` whatever the caller's ``composite(ids, bins)`` / ``round2(ids, aux)`` return
+    (``fuse.outputs`` where the list build composited), or None for a view with nothing on screen.
+    ``round1(ids, bins1, tile_flags)`` / ``round2``: the caller's two-round compositing (None: single walks only).
+    Device-sized lists are walked before their count is known and once more if they had to be built again."""
+    ran_round1 = []
+
+    def round1_of_the_build(ids, bins1, flags):
+        ran_round1.append(True)
+        round1(ids, bins1, flags)
+
+    def walk(lists):
+        if not lists.two:
+            return composite(lists.ids, lists.bins)
+        tiles = ((img_width + block_width - 1) // block_width) * ((img_height + block_width - 1) // block_width)
+        round1(lists.ids, lists.bins, torch.zeros((tiles,), dtype=torch.int32, device=xys.device))
+        return round2(lists.ids, lists.aux)
+
+    lists, finish = build_tile_lists(xys, depths, radii, conics, num_tiles_hit, opacity, img_height, img_width,
+                                     block_width, round1=None if round1 is None else round1_of_the_build, fuse=fuse)
+    if finish is None:
+        return lists, (walk(lists) if lists.num_intersects >= 1 else None)
+    if fuse is not None and fuse.outputs is not None:  # composited by the call that built the lists
+        outputs = fuse.outputs
+    elif lists.two and ran_round1:
+        outputs = round2(lists.ids, lists.aux)
+    else:  # (cached two-segment lists used speculatively take both rounds)
+        outputs = walk(lists)
+    lists, rebuilt = finish()
+    if lists.num_intersects < 1:
+        return lists, None
+    # (no rebuild returns two-segment lists today -- each builds single-round ones -- but `walk` serves them as well)
+    return lists, (walk(lists) if rebuilt else outputs)
+
+
+def backward_16px(ctx, num_intersects, img_height, img_width, ids, bins, xys, conics, colors, extra, opacity,
+                  background, extra_background, final_Ts, final_idx, v_img, v_extra_img, v_alpha):
+    """The backward of both ops at block width 16 and 3 colours (``extra`` / ``v_extra_img`` None: no fourth channel)
+    -> (v_xy, v_conic, v_colors, v_extra or None, v_opacity).  Reads ``ctx.absgrad_of`` / ``.two`` / ``.det`` and takes
+    ``ctx.accumulators`` (a second backward, under retain_graph, clears its own)."""
+    n, dev = xys.size(0), xys.device
+    v_xy_abs = None
+    if ctx.absgrad_of is not None:
+        v_xy_abs = (torch.zeros if num_intersects < 1 else torch.empty)((n, 2), dtype=torch.float32, device=dev)
+        ctx.absgrad_of.tensor.absgrad = v_xy_abs
+    if num_intersects < 1:
+        z = torch.zeros_like
+        return z(xys), z(conics), z(colors), (None if extra is None else z(extra)), z(opacity)
+    # v_alpha stays None when the alpha output was not requested / not used: the kernels read a missing cotangent
+    # as zero (no H x W zero tensor)
+    if v_img is None:  # only the other outputs were used
+        v_img = torch.zeros(img_height, img_width, 3, device=dev)
+    if extra is not None and v_extra_img is None:
+        v_extra_img = torch.zeros(img_height, img_width, device=dev)
+    acc, ctx.accumulators = ctx.accumulators, None
+    if ctx.two is not None:
+        grads = _C.rasterize_backward_two(
+            img_height, img_width, ids, bins, ctx.two[0], ctx.two[1], xys, conics, colors, extra, opacity, background,
+            extra_background, final_Ts, final_idx, v_img, v_extra_img, v_alpha, accumulators=acc, v_xy_abs=v_xy_abs)
+    elif ctx.det is not None:  # fixed summation order (`set_deterministic`)
+        grads = _C.rasterize_backward_det(
+            img_height, img_width, ids, bins, xys, conics, colors, opacity, background, final_Ts, final_idx, v_img,
+            v_alpha, *ctx.det, extra=extra, extra_background=extra_background, v_output_extra=v_extra_img,
+            v_xy_abs=v_xy_abs)
+    elif extra is None:
+        grads = _C.rasterize_backward(
+            img_height, img_width, 16, ids, bins, xys, conics, colors, opacity, background, final_Ts, final_idx, v_img,
+            v_alpha, accumulators=acc, trusted=True, v_xy_abs=v_xy_abs)
+    else:
+        grads = _C.rasterize_backward_rgbd(
+            img_height, img_width, ids, bins, xys, conics, colors, extra, opacity, background, extra_background,
+            final_Ts, final_idx, v_img, v_extra_img, v_alpha, accumulators=acc, v_xy_abs=v_xy_abs)
+    v_extra = None if extra is None else grads[3].view(extra.shape)
+    return grads[0], grads[1], grads[2], v_extra, grads[-1].reshape(opacity.shape)
 
 
 class _RasterizeGaussians(Function):
@@ -810,95 +877,61 @@ class _RasterizeGaussians(Function):
         acc = None
         if fused and any(ctx.needs_input_grad[i] for i in (0, 3, 5, 6)) and not _deterministic["on"]:
             acc = _C.backward_accumulators(xys.size(0), 3, xys.device)
-        alpha_out = [None]
         state = []  # two-round compositing: the caller-owned raw state both rounds work on
 
-        def composite(ids, bins):
+        def composite(ids, bins):  # -> (out_img, final_Ts, final_idx, alpha or None), as both rounds together
             if not fused:
-                return rasterize_fn(tile_bounds, block, img_size, ids, bins, xys, conics, colors, opacity, background)
+                return rasterize_fn(tile_bounds, block, img_size, ids, bins, xys, conics, colors, opacity,
+                                    background) + (None,)
             if fuse.prealloc is not None:  # lists AND output buffers were made ahead of time: straight to the launch
                 (img0, planes), fuse.prealloc = fuse.prealloc, None
                 if colors.dtype == torch.float32 and background.dtype == torch.float32 and opacity.dtype == torch.float32 \
                         and colors.size(0) == xys.size(0) and opacity.numel() == xys.size(0) and background.numel() == 3 \
                         and colors.device == xys.device and background.device == xys.device:
-                    img, Ts, idx, alpha_out[0] = _C.composite_prepared(
+                    return _C.composite_prepared(
                         tile_bounds, img_width, img_height, ids, bins, xys, conics, colors, opacity, background, img0,
                         planes, return_alpha, zero=acc)
-                    return img, Ts, idx
-            img, Ts, idx, alpha_out[0] = _C.rasterize_forward_ex(tile_bounds, block, img_size, ids, bins, xys, conics,
-                                                                 colors, opacity, background, want_alpha=return_alpha,
-                                                                 zero=acc)
-            return img, Ts, idx
+            return _C.rasterize_forward_ex(tile_bounds, block, img_size, ids, bins, xys, conics, colors, opacity,
+                                           background, want_alpha=return_alpha, zero=acc)
 
         def round1(ids, bins1, flags):
             dev = xys.device
             with torch.cuda.device(dev):
                 state[:] = [torch.empty((img_height, img_width, 3), dtype=torch.float32, device=dev),
                             torch.empty((img_height, img_width), dtype=torch.float32, device=dev),
-                            torch.empty((img_height, img_width), dtype=torch.int32, device=dev), flags]
-                alpha_out[0] = torch.empty((img_height, img_width), dtype=torch.float32, device=dev) if return_alpha else None
+                            torch.empty((img_height, img_width), dtype=torch.int32, device=dev), flags,
+                            torch.empty((img_height, img_width), dtype=torch.float32, device=dev) if return_alpha else None]
             _C.rasterize_forward_round(1, tile_bounds, img_size, ids, bins1, 0, xys, conics, colors, None, opacity,
-                                       background, 0.0, state[0], None, state[1], state[2], flags, out_alpha=alpha_out[0],
+                                       background, 0.0, state[0], None, state[1], state[2], flags, out_alpha=state[4],
                                        zero=acc)
 
         def round2(ids, aux):
             _C.rasterize_forward_round(2, tile_bounds, img_size, ids, aux[1], aux[2], xys, conics, colors, None, opacity,
-                                       background, 0.0, state[0], None, state[1], state[2], state[3],
-                                       out_alpha=alpha_out[0])
-            return state[0], state[1], state[2]
-
-        is_two = _is_two
+                                       background, 0.0, state[0], None, state[1], state[2], state[3], out_alpha=state[4])
+            return state[0], state[1], state[2], state[4]
 
         fuse = FusedForward(colors, background, img_height, img_width, return_alpha, acc) if fused else None
-        num_intersects, gaussian_ids_sorted, tile_bins, finish = build_tile_lists(
-            xys, depths, radii, conics, num_tiles_hit, opacity, img_height, img_width, block_width,
-            round1=round1 if fused else None, fuse=fuse)
-        two = is_two(last_list_aux()) and fused
-        two_aux = last_list_aux() if two else None
-        if finish is not None:
-            if fuse is not None and fuse.outputs is not None:  # composited by the call that built the lists
-                out_img, final_Ts, final_idx, alpha_out[0] = fuse.outputs
-            elif two and state:      # round 1 ran inside build_tile_lists
-                out_img, final_Ts, final_idx = round2(gaussian_ids_sorted, two_aux)
-            elif two:              # cached two-segment lists used speculatively
-                flags = torch.zeros((tile_bounds[0] * tile_bounds[1],), dtype=torch.int32, device=xys.device)
-                round1(gaussian_ids_sorted, tile_bins, flags)
-                out_img, final_Ts, final_idx = round2(gaussian_ids_sorted, two_aux)
-            else:
-                out_img, final_Ts, final_idx = composite(gaussian_ids_sorted, tile_bins)
-            num_intersects, gaussian_ids_sorted, tile_bins, rebuilt = finish()
-            if rebuilt:
-                two = is_two(last_list_aux()) and fused
-                two_aux = last_list_aux() if two else None
-                if two:
-                    flags = torch.zeros((tile_bounds[0] * tile_bounds[1],), dtype=torch.int32, device=xys.device)
-                    round1(gaussian_ids_sorted, tile_bins, flags)
-                    out_img, final_Ts, final_idx = round2(gaussian_ids_sorted, two_aux)
-                else:
-                    out_img, final_Ts, final_idx = composite(gaussian_ids_sorted, tile_bins)
-
-        if num_intersects < 1:
+        lists, outputs = composite_lists(
+            xys, depths, radii, conics, num_tiles_hit, opacity, img_height, img_width, block_width, composite,
+            round1 if fused else None, round2, fuse)
+        num_intersects, gaussian_ids_sorted, tile_bins, aux = lists
+        if outputs is None:
             # nothing on screen: background everywhere (rasterize.py:119-127)
             out_img = torch.ones(img_height, img_width, colors.shape[-1], device=xys.device) * background
             gaussian_ids_sorted = torch.zeros(0, 1, device=xys.device)
             tile_bins = torch.zeros(0, 2, device=xys.device)
             final_Ts = torch.zeros(img_height, img_width, device=xys.device)
             final_idx = torch.zeros(img_height, img_width, device=xys.device)
-            acc, alpha_out[0] = None, None
-        elif finish is None:
-            if two:  # two-segment lists from the cache (the depth pass of a view)
-                flags = torch.zeros((tile_bounds[0] * tile_bounds[1],), dtype=torch.int32, device=xys.device)
-                round1(gaussian_ids_sorted, tile_bins, flags)
-                out_img, final_Ts, final_idx = round2(gaussian_ids_sorted, two_aux)
-            else:
-                out_img, final_Ts, final_idx = composite(gaussian_ids_sorted, tile_bins)
+            acc = alpha = aux = None
+        else:
+            out_img, final_Ts, final_idx, alpha = outputs
 
         ctx.set_materialize_grads(False)
         ctx.img_width = img_width
         ctx.img_height = img_height
         # deterministic backward: (order, cum_sorted, slot_of_entry) of the lists just used
-        ctx.det = last_list_aux() if (_deterministic["on"] and num_intersects >= 1 and colors.shape[-1] == 3) else None
-        ctx.two = (two_aux[1], two_aux[2]) if (two and num_intersects >= 1) else None
+        ctx.det = aux if (_deterministic["on"] and aux is not None and colors.shape[-1] == 3) else None
+        ctx.two = (aux[1], aux[2]) if _is_two(aux) else None
         ctx.num_intersects = num_intersects
         ctx.block_width = block_width
         ctx.accumulators = acc  # cleared by the forward launch; used (once) by the backward
@@ -907,52 +940,27 @@ class _RasterizeGaussians(Function):
                               background, final_Ts, final_idx)
 
         if return_alpha:
-            return out_img, (alpha_out[0] if alpha_out[0] is not None else 1 - final_Ts)
+            return out_img, (alpha if alpha is not None else 1 - final_Ts)
         return out_img
 
     @staticmethod
     def backward(ctx, v_out_img, v_out_alpha=None):
         (gaussian_ids_sorted, tile_bins, xys, conics, colors, opacity, background, final_Ts,
          final_idx) = ctx.saved_tensors
-
-        # v_out_alpha stays None when the alpha output was not requested / not used:
-        # the kernels read a missing cotangent as zero (no H x W zero tensor)
-        if v_out_img is None:  # only the alpha output was used
-            v_out_img = torch.zeros(ctx.img_height, ctx.img_width, colors.shape[-1], device=xys.device)
-
-        v_xy_abs = None
-        if ctx.absgrad_of is not None:
-            v_xy_abs = (torch.zeros if ctx.num_intersects < 1 else torch.empty)(
-                (xys.size(0), 2), dtype=torch.float32, device=xys.device)
-            ctx.absgrad_of.tensor.absgrad = v_xy_abs
-        if ctx.num_intersects < 1:
-            v_xy = torch.zeros_like(xys)
-            v_conic = torch.zeros_like(conics)
-            v_colors = torch.zeros_like(colors)
-            v_opacity = torch.zeros_like(opacity)
-        else:
-            if ctx.two is not None:
-                acc, ctx.accumulators = ctx.accumulators, None
-                v_xy, v_conic, v_colors, v_opacity = _C.rasterize_backward_two(
-                    ctx.img_height, ctx.img_width, gaussian_ids_sorted, tile_bins, ctx.two[0], ctx.two[1], xys, conics,
-                    colors, None, opacity, background, 0.0, final_Ts, final_idx, v_out_img, None, v_out_alpha,
-                    accumulators=acc, v_xy_abs=v_xy_abs)
-            elif ctx.det is not None:
-                v_xy, v_conic, v_colors, v_opacity = _C.rasterize_backward_det(
-                    ctx.img_height, ctx.img_width, gaussian_ids_sorted, tile_bins, xys, conics, colors, opacity,
-                    background, final_Ts, final_idx, v_out_img, v_out_alpha, *ctx.det, v_xy_abs=v_xy_abs)
-            else:
-                acc, ctx.accumulators = ctx.accumulators, None  # a second backward (retain_graph) clears its own
-                if colors.shape[-1] == 3:
-                    v_xy, v_conic, v_colors, v_opacity = _C.rasterize_backward(
-                        ctx.img_height, ctx.img_width, ctx.block_width, gaussian_ids_sorted, tile_bins, xys,
-                        conics, colors, opacity, background, final_Ts, final_idx, v_out_img, v_out_alpha,
-                        accumulators=acc, trusted=True, v_xy_abs=v_xy_abs)
-                else:
-                    v_xy, v_conic, v_colors, v_opacity = _C.nd_rasterize_backward(
-                        ctx.img_height, ctx.img_width, ctx.block_width, gaussian_ids_sorted, tile_bins, xys,
-                        conics, colors, opacity, background, final_Ts, final_idx, v_out_img, v_out_alpha)
+        if ctx.block_width == 16 and colors.shape[-1] == 3:
+            v_xy, v_conic, v_colors, _, v_opacity = backward_16px(
+                ctx, ctx.num_intersects, ctx.img_height, ctx.img_width, gaussian_ids_sorted, tile_bins, xys, conics,
+                colors, None, opacity, background, 0.0, final_Ts, final_idx, v_out_img, None, v_out_alpha)
+        elif ctx.num_intersects < 1:
+            v_xy, v_conic, v_colors, v_opacity = (torch.zeros_like(t) for t in (xys, conics, colors, opacity))
+        else:  # N-D colours, other block widths: the generic kernels
+            if v_out_img is None:  # only the alpha output was used
+                v_out_img = torch.zeros(ctx.img_height, ctx.img_width, colors.shape[-1], device=xys.device)
+            backward_fn = _C.rasterize_backward if colors.shape[-1] == 3 else _C.nd_rasterize_backward
+            v_xy, v_conic, v_colors, v_opacity = backward_fn(
+                ctx.img_height, ctx.img_width, ctx.block_width, gaussian_ids_sorted, tile_bins, xys, conics, colors,
+                opacity, background, final_Ts, final_idx, v_out_img, v_out_alpha)
             v_opacity = v_opacity.reshape(opacity.shape)
 
-        # xys, depths, radii, conics, num_tiles_hit, colors, opacity, then 5 non-differentiable
+        # xys, depths, radii, conics, num_tiles_hit, colors, opacity, then 6 non-differentiable
         return (v_xy, None, None, v_conic, None, v_colors, v_opacity) + (None,) * 6

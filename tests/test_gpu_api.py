@@ -1025,6 +1025,57 @@ def test_rgbd_single_pass_equals_two_passes(n, W, H):
         rasterize_gaussians_rgbd(xys, depths, radii, conics, tiles, colors2[:, :2], depths, p2["opacities"], H, W)
 
 
+def test_rgbd_lists_that_overflow_are_rebuilt_and_composited_again(monkeypatch, tune):
+    """`rasterize_gaussians_rgbd` on device-sized lists with room for half the view's entries: the count check behind
+    the compositing finds the overflow, the lists are built again and walked again -- images bit-identical to the
+    unspeculated run, gradients equal up to the order of the float atomics (1e-5 of the largest: the bound of
+    tools/exp/fuzz_sequence.py)."""
+    from gs_fused import rasterize_gaussians_rgbd
+    from rasterizer import project_gaussians
+    from rasterizer import rasterize as R
+
+    n, W, H = 3000, 160, 96
+    cam = S.make_camera(W, H, yaw=0.1)
+    sc = S.make_scene(n, cam, sh_degree=0, seed=21, scale_lo=0.01, scale_hi=0.1)
+    ct = CameraTensors.from_numpy(cam, DEV)
+    g = torch.Generator(device="cpu").manual_seed(1)
+    col_np = torch.rand(n, 3, generator=g)
+    cots = [torch.randn(H, W, 3, generator=g).to(DEV), torch.randn(H, W, generator=g).to(DEV),
+            torch.randn(H, W, 1, generator=g).to(DEV)]
+    bg = cu(np.array(S.BACKGROUND, np.float32))
+
+    def run():
+        R._bin_cache["key"] = None
+        p = {k: cu(v, True) for k, v in sc.items() if k in ("means3d", "scales", "quats", "opacities")}
+        xys, depths, radii, conics, comp, tiles, _ = project_gaussians(
+            p["means3d"], p["scales"], 1, p["quats"], ct.viewmat[:3], ct.projmat, cam.fx, cam.fy, cam.cx, cam.cy,
+            H, W, 16)
+        p["colors"] = col_np.to(DEV).requires_grad_(True)
+        outs = rasterize_gaussians_rgbd(xys, depths, radii, conics, tiles, p["colors"], depths, p["opacities"], H, W,
+                                        background=bg)
+        torch.autograd.backward(list(outs), cots)
+        torch.cuda.synchronize()
+        return [o.detach() for o in outs], {k: v.grad for k, v in p.items()}
+
+    tune(no_speculation=1)
+    ref, gref = run()
+    exact = int(R._bin_cache["value"][0])
+    assert exact >= 2
+    tune()
+    monkeypatch.setattr(R, "_speculative_capacity", lambda *a, **k: exact // 2)
+    before = dict(R.counters)
+    got, grads = run()
+    assert R.counters["list_rebuilds"] >= before["list_rebuilds"] + 1
+    assert R.counters["list_builds_device_sized"] >= before["list_builds_device_sized"] + 1
+    assert int(R._bin_cache["value"][0]) == exact
+    for a, b, nm in zip(got, ref, ("rgb", "alpha", "extra")):
+        assert torch.equal(a, b), nm
+    for nm, b in gref.items():
+        err, bound = (grads[nm] - b).abs().max().item(), 1e-5 * b.abs().max().item() + 1e-12
+        print(f"{nm}: max |grad - ref| {err:.3e}  (bound {bound:.3e})")
+        assert err <= bound, nm
+
+
 # ---- central differences through the three autograd Functions (BASELINE config 2: "gradcheck
 # tol 1e-3") --------------------------------------------------------------------------------
 def _directional_check(f, inputs, h, tol, trials=3, seed=0, tangent=()):
