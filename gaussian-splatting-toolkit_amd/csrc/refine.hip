@@ -40,6 +40,7 @@
 // (seed; Gaussian index, sample index) + Box-Muller: no dependence on how many
 // Gaussians split, identical on every data-parallel replica given the same seed.
 #include "gsr_common.h"
+#include "philox.h"
 
 namespace {
 
@@ -180,31 +181,7 @@ __global__ __launch_bounds__(kBlock) void refine_offsets_kernel(const int n, con
   }
 }
 
-// ---- Philox4x32-10 (Salmon et al., SC'11) + Box-Muller; mirrored in oracle/refine.py ----
-__device__ __forceinline__ void philox_round(uint32_t &c0, uint32_t &c1, uint32_t &c2, uint32_t &c3, uint32_t k0,
-                                             uint32_t k1) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1,
-                 n3 = (uint32_t)p0;
-  c0 = n0, c1 = n1, c2 = n2, c3 = n3;
-}
-
-__device__ __forceinline__ float u01(uint32_t x) { return ((float)(x >> 9) + 0.5f) * 1.1920928955078125e-07f; }
-
-__device__ __forceinline__ void split_normals(const uint64_t seed, const uint32_t i, const uint32_t j, float z[3]) {
-  uint32_t c0 = i, c1 = j, c2 = 0, c3 = 0, k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c0, c1, c2, c3, k0, k1);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  const float r0 = sqrtf(-2.f * logf(u01(c0))), r1 = sqrtf(-2.f * logf(u01(c2)));
-  const float a0 = 6.283185307179586f * u01(c1), a1 = 6.283185307179586f * u01(c3);
-  z[0] = r0 * cosf(a0);
-  z[1] = r0 * sinf(a0);
-  z[2] = r1 * cosf(a1);
-}
+// (Philox4x32-10 + Box-Muller, `split_normals`: philox.h, shared with mcmc.hip; mirrored in oracle/refine.py)
 
 // ---- data movement -----------------------------------------------------------
 constexpr int kMaxTensors = GSR_REFINE_MAX_TENSORS;

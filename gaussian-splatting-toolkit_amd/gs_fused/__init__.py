@@ -10,6 +10,8 @@ from .sh import sh_backward_views, spherical_harmonics_split  # noqa: F401
 from .activations import activate_gaussians, densify_stats_  # noqa: F401
 from .rgbd import rasterize_gaussians_rgbd  # noqa: F401
 from .refine import RefineConfig, adam_moments, refine_gaussians, refinement_branch, swap_parameters  # noqa: F401
+from .mcmc import (MCMCConfig, MCMCInfo, mcmc_add, mcmc_branch, mcmc_inject_noise_, mcmc_num_new,  # noqa: F401
+                   mcmc_refine, mcmc_regularizer, mcmc_relocate, relocation)
 from .render import DensifyStats, ListCapacity, ViewSpec, render_gaussians  # noqa: F401
 from rasterizer.project_gaussians import project_gaussians_antialiased  # noqa: F401
 from .crop import CropBox, crop_gaussians, project_gaussians_cropped  # noqa: F401

@@ -394,6 +394,12 @@ class TrainConfig:
     init_gaussians: Optional[int] = None  # the model starts from this many (coarser) Gaussians; default: all
     refine: Optional[object] = None       # gs_fused.RefineConfig; default: the reference's values
     refine_seed: int = 20240807           # broadcast by construction: the same on every rank
+    # the densification strategy: "default" = the schedule above (with `densify`); "mcmc" = relocation of dead
+    # Gaussians, growth by 5 % per refinement up to `mcmc.cap_max`, position noise after every optimiser step and the
+    # opacity / scale regularisers in the loss (gs_fused.mcmc) -- no gradient statistics, no
+    # opacity reset, no culling by size; `densify` and `refine` do not apply.  One GPU, CUDA only.
+    strategy: str = "default"
+    mcmc: Optional[object] = None         # gs_fused.MCMCConfig; default: gsplat's values
     # gs_fused.render_gaussians: the whole view as ONE autograd node (activations, projection, SH,
     # binning, compositing; densification statistics from its backward) instead of the op-by-op
     # call sequence of the models; use_graph: render -> loss -> backward replayed as one HIP graph
@@ -598,6 +604,15 @@ def _check_config(cfg: TrainConfig) -> None:
         raise ValueError(f"unknown mask {cfg.mask!r}")
     if cfg.rasterize_mode not in ("classic", "antialiased"):
         raise ValueError("Unknown rasterize_mode: %s" % cfg.rasterize_mode)
+    if cfg.strategy not in ("default", "mcmc"):
+        raise ValueError(f"unknown strategy {cfg.strategy!r}")
+    if cfg.strategy == "mcmc":
+        if cfg.refine is not None:
+            raise ValueError("strategy='mcmc' takes its schedule from `mcmc` (gs_fused.MCMCConfig): `refine` "
+                             "belongs to the default strategy and must stay None")
+        if cfg.sharded_adam:
+            raise ValueError("strategy='mcmc' does not run with `sharded_adam`: relocation rewrites whole rows of "
+                             "both Adam moments in place")
     if cfg.camera_optimizer not in ("off", "SO3xR3", "SE3"):
         raise ValueError(f"unknown camera_optimizer {cfg.camera_optimizer!r}")
     if cfg.camera_optimizer != "off":
@@ -612,6 +627,17 @@ def _check_config(cfg: TrainConfig) -> None:
 def _check_absgrad(cfg: TrainConfig, device) -> None:
     if cfg.absgrad and device.type != "cuda":
         raise ValueError("absgrad needs CUDA tensors: the per-pixel sums come from the HIP compositing backward")
+
+
+def _check_mcmc(cfg: TrainConfig, device, world: int) -> None:
+    """What else `strategy="mcmc"` refuses, once the device and the world size are known."""
+    if cfg.strategy != "mcmc":
+        return
+    if world > 1:
+        raise ValueError("strategy='mcmc' runs on one GPU (world size 1): the draws and the position noise of a "
+                         "data-parallel run are not coordinated")
+    if device.type != "cuda":
+        raise ValueError("strategy='mcmc' needs CUDA tensors: relocation, noise and regularisers are HIP kernels")
 
 
 def _check_camera_optimizer(cfg: TrainConfig, device, world: int) -> None:
@@ -1110,16 +1136,17 @@ class FusedStep:
     marks = ()
 
     def __init__(self, cfg: TrainConfig, model, data: TrainData, stats: DensifyState, photo, exchange, sh_views: bool,
-                 dp: bool, history: list):
+                 dp: bool, history: list, mcfg=None):
         from gs_fused import ListCapacity, ViewSpec, render_gaussians
         from gs_fused.render import ViewGraph
 
         self.ViewSpec, self.render_gaussians, self.ViewGraph = ViewSpec, render_gaussians, ViewGraph
         self.cfg, self.model, self.stats, self.photo, self.exchange = cfg, model, stats, photo, exchange
-        self.sh_views, self.dp, self.history = sh_views, dp, history
+        self.sh_views, self.dp, self.history, self.mcfg = sh_views, dp, history, mcfg
 
         def graph_loss(out, targets):  # (with a mask: the second static target of the graph, [h,w,1])
-            return photo(out["rgb"], targets[0], targets[1] if len(targets) > 1 else None)
+            loss = photo(out["rgb"], targets[0], targets[1] if len(targets) > 1 else None)
+            return loss if mcfg is None else _add_mcmc_regulariser(loss, model, mcfg)
 
         self.graph_loss = graph_loss  # (a closure over the head alone: a ViewGraph holds it, and must not hold this)
         self.caps = ListCapacity()
@@ -1156,6 +1183,8 @@ class FusedStep:
                                         g_["features_rest"], cam.viewmat, cam.projmat, cam.campos, bg, spec, used,
                                         count_out=slot, stats=fstats, sh_collector=collector)
             loss = self.photo(out["rgb"], target, mask)
+            if self.mcfg is not None:
+                loss = _add_mcmc_regulariser(loss, self.model, self.mcfg)
             loss.backward()
             caps.submitted(slot, used, bg.device)
             if caps.overflowed():
@@ -1229,6 +1258,7 @@ class SeparateStep:
         self.ph, self.depth_on = None, False
         self.marks = []  # (downscale factor, 5 events, depth loss on) per sampled step
         self.camera_opt = None  # a camera_opt.CameraOptimizer: its regulariser joins the loss (get_loss_dict)
+        self.mcfg = None  # a gs_fused.MCMCConfig: the opacity / scale regularisers join the loss
 
     def __call__(self, step, v, d, cam, deg, bg, target, mask):
         _zero_grads(self.model)
@@ -1248,6 +1278,8 @@ class SeparateStep:
                 loss = loss + term
         if self.camera_opt is not None:
             loss = loss + self.camera_opt.regulariser()
+        if self.mcfg is not None:
+            loss = _add_mcmc_regulariser(loss, self.model, self.mcfg)
         if ph:
             ph[2].record()
         loss.backward()
@@ -1347,6 +1379,26 @@ def refine_model(cfg: TrainConfig, rcfg, step: int, model, optims, sharded, exch
     stats.restart()
 
 
+def refine_model_mcmc(cfg: TrainConfig, mcfg, step: int, model, optims, exchange, stats: DensifyState,
+                      history: list) -> None:
+    """A refinement of `strategy="mcmc"` (gs_fused.mcmc_refine): dead Gaussians relocated in place, then the model
+    grown towards `cap_max`.  Nothing is read back; only a refinement that added rows installs new tensors in the model
+    and the optimisers -- a relocation leaves every tensor (and a captured view graph) where it is."""
+    old = _params(model)
+    moments = {}
+    for o in optims.values():
+        moments.update(_adam_moments(o, old))
+    new, new_moments, info = _mcmc_refine(old, moments, mcfg, step, seed=cfg.refine_seed)
+    if info["n_out"] != info["n_in"]:
+        model.replace(new)
+        cur = _params(model)
+        for o in optims.values():
+            _swap_parameters(o, old, cur, new_moments)
+        stats.reset(info["n_out"])
+        history.append((step, model.num_points))
+        exchange.rebind(_params(model))
+
+
 def phase_record(marks, cfg: TrainConfig, factors) -> Dict:
     """The four `phase_ms_*` entries of the result from the steps' events: medians over all sampled steps, per
     resolution under a coarse-to-fine schedule, before / after co-gs' depth loss joins, and every sample."""
@@ -1397,6 +1449,7 @@ def result_record(cfg: TrainConfig, device, world: int, model, run: Dict, eval0:
             # (only where it was asked for: a classic run's record stays what it was, to the byte)
             **({"rasterize_mode": cfg.rasterize_mode} if cfg.rasterize_mode != "classic" else {}),
             **({"absgrad": True} if cfg.absgrad else {}),
+            **({"strategy": cfg.strategy} if cfg.strategy != "default" else {}),
             "depth": ({"loss_from_step": cfg.depth_loss_start_iteration + 1 if cfg.use_depth_loss else None,
                        "one_compositing_pass": bool(cfg.fused_depth and device.type == "cuda"),
                        "mean_abs_error_start_end": [eval0["depth_err"], eval1["depth_err"]]} if cogs else None),
@@ -1418,7 +1471,16 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
     _check_config(cfg)
     _check_camera_optimizer(cfg, device, world)
     _check_absgrad(cfg, device)
+    _check_mcmc(cfg, device, world)
     cuda = device.type == "cuda"
+    mcfg = None
+    if cfg.strategy == "mcmc":
+        mcfg = cfg.mcmc
+        if mcfg is None:
+            from gs_fused import MCMCConfig
+
+            mcfg = MCMCConfig()
+        cfg = replace(cfg, densify=False)  # (a copy: the default strategy's schedule does not run)
     dp = world > 1 or (cfg.force_exchange and dist.is_available() and dist.is_initialized())
     if cfg.dataset is not None:
         if world > 1 or dp:
@@ -1452,7 +1514,8 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
     if cfg.fused_activations and cuda and not use_fused:
         from gs_fused import densify_stats_ as kernel
     stats = DensifyState(model.num_points, device, max(cfg.width, cfg.height),
-                         densify_until=rcfg.stop_split_at if cfg.densify else None, rank=rank, world=world,
+                         densify_until=0 if mcfg is not None else (rcfg.stop_split_at if cfg.densify else None),
+                         rank=rank, world=world,
                          kernel=kernel, native=use_fused, absgrad=cfg.absgrad and not use_fused)
     eval0 = evaluate(model, data, cfg, None if camera is None else camera.eval_cameras(data))
     pose0 = pose_errors(cfg, data, camera, device)
@@ -1477,10 +1540,11 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
     t0 = time.perf_counter()
     try:  # (an exception in the loop must not leave the collector frozen for the rest of the process)
         if use_fused:  # (sizes its tile lists with a probe render: inside the timed region, as the first view is)
-            run_step = FusedStep(cfg, model, data, stats, heads[0], exchange, sh_views, dp, history)
+            run_step = FusedStep(cfg, model, data, stats, heads[0], exchange, sh_views, dp, history, mcfg=mcfg)
         else:
             run_step = SeparateStep(cfg, model, data, heads, exchange, sh_views, device)
             run_step.camera_opt = None if camera is None else camera.opt
+            run_step.mcfg = mcfg
         rebuilds0 = _list_rebuilds()
         for step in range(start_step, cfg.iters):
             v = view_for_rank(step, rank, world, cfg.num_views)
@@ -1515,6 +1579,13 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
             # (TrainingCallback(update_every_num_iters=refine_every), vanilla_gs.py:610-616)
             if cfg.densify and step % rcfg.refine_every == 0 and step > rcfg.warmup_length:
                 refine_model(cfg, rcfg, step, model, optims, sharded, exchange, stats, max_dim, dp, history)
+            if mcfg is not None:
+                # gsplat's step_post_backward: the refinement when one is due, then the position noise -- every step,
+                # at the step's means learning rate, outside the captured graph
+                if _mcmc_branch(mcfg, step):
+                    refine_model_mcmc(cfg, mcfg, step, model, optims, exchange, stats, history)
+                lr = means_lr(step, LRS["means"]) if cfg.means_lr_schedule else LRS["means"]
+                _mcmc_noise(model, lr * mcfg.noise_lr, cfg.refine_seed ^ 0x5DEECE66D, step)
             if cfg.save_every and cfg.checkpoint_dir and step > 0 and step % cfg.save_every == 0 and \
                     (rank == 0 or sharded is not None):
                 from .checkpoint import save_checkpoint
@@ -1595,3 +1666,31 @@ def _refine(params, moments, stats, rcfg, step, num_train_data, max_dim, seed):
     from gs_fused import refine_gaussians
 
     return refine_gaussians(params, moments, stats, rcfg, step, num_train_data, max_dim, seed=seed)
+
+
+# the MCMC strategy's backend (module-level for the same reason)
+def _mcmc_branch(mcfg, step):
+    from gs_fused import mcmc_branch
+
+    return mcmc_branch(mcfg, step)
+
+
+def _mcmc_refine(params, moments, mcfg, step, seed):
+    from gs_fused import mcmc_refine
+
+    return mcmc_refine(params, moments, mcfg, step, seed=seed)
+
+
+def _mcmc_noise(model, scaler, seed, step):
+    from gs_fused import mcmc_inject_noise_
+
+    g = model.gauss
+    mcmc_inject_noise_(g["means"], g["scales"], g["quats"], g["opacities"], scaler, seed, step)
+
+
+def _add_mcmc_regulariser(loss, model, mcfg):
+    """loss + opacity_reg * mean(opacity) + scale_reg * mean(scale) (gs_fused.mcmc_regularizer: a float64 scalar)."""
+    from gs_fused import mcmc_regularizer
+
+    g = model.gauss
+    return loss + mcmc_regularizer(g["opacities"], g["scales"], mcfg.opacity_reg, mcfg.scale_reg).to(loss.dtype)

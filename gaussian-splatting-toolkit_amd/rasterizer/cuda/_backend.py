@@ -96,6 +96,14 @@ SYMBOLS = (
     "gsr_refine_workspace_bytes",
     "gsr_refine_plan",
     "gsr_refine_apply",
+    "gsr_mcmc_relocation",
+    "gsr_mcmc_workspace_bytes",
+    "gsr_mcmc_plan",
+    "gsr_mcmc_apply",
+    "gsr_mcmc_noise",
+    "gsr_mcmc_reg_workspace_bytes",
+    "gsr_mcmc_reg_forward",
+    "gsr_mcmc_reg_backward",
     "gsr_adam_step",
     "gsr_rasterize_backward_det_workspace_bytes",
     "gsr_rasterize_backward_det",
@@ -168,6 +176,8 @@ def _load():
     lib.gsr_depth_order_workspace_bytes.restype = C.c_size_t
     lib.gsr_bin_sorted_workspace_bytes.restype = C.c_size_t
     lib.gsr_refine_workspace_bytes.restype = C.c_size_t
+    lib.gsr_mcmc_workspace_bytes.restype = C.c_size_t
+    lib.gsr_mcmc_reg_workspace_bytes.restype = C.c_size_t
     lib.gsr_tile_lists_subrange_workspace_bytes.restype = C.c_size_t
     lib.gsr_saturation_filter_workspace_bytes.restype = C.c_size_t
     lib.gsr_rasterize_forward_seg_workspace_bytes.restype = C.c_size_t

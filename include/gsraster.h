@@ -1054,6 +1054,84 @@ int gsr_refine_apply(int num_points, int n_split_samples, const uint8_t *flags,
                      int num_tensors, const gsr_refine_tensor *tensors,
                      gsr_stream_t stream);
 
+/* ---- MCMC densification ---------------------------
+ * "3D Gaussian Splatting as Markov Chain Monte Carlo" (Kheradmand et al. 2024;
+ * gsplat's MCMCStrategy): dead Gaussians (sigmoid(logit) <= min_opacity) are
+ * relocated onto live ones sampled by opacity, the model grows to a cap, and a
+ * source drawn `count` times gets, with ratio n = min(count + 1, 51),
+ *   o' = 1 - (1 - o)^(1/n)
+ *   D  = sum_{i=1..n} sum_{k=0..i-1} C(i-1,k) (-1)^k o'^(k+1) / sqrt(k+1)
+ *   s' = (o / D) s
+ * evaluated in float64 on the device and rounded once to float32.
+ * gsr_mcmc_relocation is that rule on its own: opacities [n] in (0,1), scales
+ * [n,3], ratios [n] (clamped to [1, 51]).  raw_outputs = 0: o' clamped to
+ * [min_opacity, 1 - 2^-23] and s' (ratio 1: the inputs unchanged);
+ * raw_outputs != 0: logit of the clamped o' and log(s) + log(o / D).
+ * gsr_mcmc_plan, one phase (GSR_MCMC_RELOCATE or GSR_MCMC_ADD) of a refinement:
+ *   opac[n]        sigmoid(logit), float32
+ *   weight         (uint32) floor(opac * 2^24); relocate: 0 for dead rows
+ *   prefix[n]      inclusive uint64 prefix sum of the weights
+ *   dead_index[n]  the dead rows in ascending order (the first totals[1] entries)
+ *   totals[2]      {sum of the weights, number of dead rows}
+ *   draws          relocate: one per dead row; add: num_draws.  Draw j takes the
+ *                  Philox4x32-10 block of counter (j, phase, step, 0) and key
+ *                  seed; r = c0 * 2^32 + c1; target = (r * total) >> 64; source =
+ *                  the first index whose prefix is > target; draw_source[j] =
+ *                  source; counts[source] += 1; relocate: row_source[dead_index[j]]
+ *                  = source.  row_source[n] is -1 and counts[n] 0 elsewhere.
+ *                  total == 0: relocation draws nothing (draw_source -1); a new
+ *                  row copies row j mod n, which stays as it is.
+ * gsr_mcmc_apply moves up to GSR_REFINE_MAX_TENSORS tensors in one launch (all
+ * tensors of a refinement in ONE call): rows < n_in with counts > 0 take their new
+ * opacity logit (kind GSR_MCMC_OPACITIES, width 1) and log-scales
+ * (GSR_REFINE_LOG_SCALES), rows with row_source >= 0 and rows n_in + j (source
+ * draw_source[j]) become copies of their source after that update, and
+ * GSR_REFINE_MOMENT tensors are zeroed on all of those rows.  in == out: in place
+ * (n_out == n_in); otherwise every other row is copied.  scratch: 4 n_in floats.
+ * gsr_mcmc_noise: mean += Sigma (eps * gate * scaler) in place, Sigma = R diag(
+ * exp(log_scale)^2) R^T, gate = 1 / (1 + exp(-100 ((1 - sigmoid(logit)) - 0.995))),
+ * eps = noise[n,3] or, if NULL, the three normals of the Philox block of counter
+ * (i, step, 0, 0) (the construction of gsr_refine_apply's split samples).
+ * gsr_mcmc_reg_forward: out[3] (float64) = {opacity_reg * mean(sigmoid(logit)) +
+ * scale_reg * mean(exp(log_scale)), the two means}; float64 terms, fixed summation
+ * order, no atomics.  _backward: the gradients scaled by the cotangent v_out[0]
+ * (a device pointer). */
+#define GSR_MCMC_MAX_RATIO 51
+#define GSR_MCMC_RELOCATE 0
+#define GSR_MCMC_ADD 1
+#define GSR_MCMC_OPACITIES 4
+int gsr_mcmc_relocation(int n, const float *opacities, const float *scales,
+                        const int32_t *ratios, float min_opacity,
+                        int raw_outputs, float *new_opacities,
+                        float *new_scales, gsr_stream_t stream);
+size_t gsr_mcmc_workspace_bytes(int num_points);
+int gsr_mcmc_plan(int num_points, int num_draws, int phase,
+                  const float *opacity_logits, float min_opacity,
+                  unsigned int step, unsigned long long seed, float *opac,
+                  uint64_t *prefix, int32_t *dead_index, int32_t *draw_source,
+                  int32_t *row_source, int32_t *counts, uint64_t *totals,
+                  void *workspace, size_t workspace_bytes,
+                  gsr_stream_t stream);
+int gsr_mcmc_apply(int n_in, int n_out, const float *opac,
+                   const float *log_scales, float min_opacity,
+                   const int32_t *row_source, const int32_t *draw_source,
+                   const int32_t *counts, float *scratch, int num_tensors,
+                   const gsr_refine_tensor *tensors, gsr_stream_t stream);
+int gsr_mcmc_noise(int num_points, float *means, const float *log_scales,
+                   const float *raw_quats, const float *opacity_logits,
+                   float scaler, unsigned int step, unsigned long long seed,
+                   const float *noise, gsr_stream_t stream);
+size_t gsr_mcmc_reg_workspace_bytes(void);
+int gsr_mcmc_reg_forward(int num_points, const float *opacity_logits,
+                         const float *log_scales, double opacity_reg,
+                         double scale_reg, double *out, void *workspace,
+                         size_t workspace_bytes, gsr_stream_t stream);
+int gsr_mcmc_reg_backward(int num_points, const float *opacity_logits,
+                          const float *log_scales, double opacity_reg,
+                          double scale_reg, const double *v_out,
+                          float *v_logits, float *v_log_scales,
+                          gsr_stream_t stream);
+
 /* ---- optimiser step ------------------------------------
  * Adam over up to GSR_ADAM_MAX_TENSORS tensors in one launch; replaces the
  * per-group torch.optim.Adam objects the toolkit builds

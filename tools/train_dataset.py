@@ -2,7 +2,8 @@
 """Train on a dataset directory (a `transforms.json` with images and, optionally, masks, depth and a seed cloud).
 
     python tools/train_dataset.py DATA [--model gaussian-splatting|co-gs] [--iters 30000] [--output-dir outputs]
-        [--eval-mode fraction|filename|interval|all] [--fused-render] [--use-graph] [--camera-optimizer SO3xR3] ...
+        [--eval-mode fraction|filename|interval|all] [--fused-render] [--use-graph] [--camera-optimizer SO3xR3]
+        [--strategy default|mcmc [--cap-max 1000000]] ...
 
 `harness.train.train` with `TrainConfig.dataset`: the files are uploaded as integers into a
 gs_fused.ImageCache and every step's target comes from one kernel.  Writes `OUTPUT_DIR/step-*.ckpt` (the toolkit's
@@ -32,6 +33,9 @@ def parse_args(argv=None):
     ap.add_argument("--resolution-schedule", type=int, default=2000)
     ap.add_argument("--background-color", default="random", choices=["random", "fixed"])
     ap.add_argument("--no-densify", action="store_true")
+    ap.add_argument("--strategy", default="default", choices=["default", "mcmc"],
+                    help="densification: the reference's schedule, or MCMC relocation with growth to --cap-max")
+    ap.add_argument("--cap-max", type=int, default=1_000_000, help="--strategy mcmc: the model never exceeds this")
     ap.add_argument("--fused-render", action="store_true")
     ap.add_argument("--use-graph", action="store_true")
     ap.add_argument("--camera-optimizer", default="off", choices=["off", "SO3xR3", "SE3"])
@@ -59,7 +63,13 @@ def main(argv=None):
     # the last step is always saved: the trainer saves at the multiples of `save_every`; where the last step is none
     # of them, only the last step is saved
     save_every = a.save_every if 0 < a.save_every < a.iters and (a.iters - 1) % a.save_every == 0 else max(a.iters - 1, 1)
+    mcmc = None
+    if a.strategy == "mcmc":
+        from gs_fused import MCMCConfig
+
+        mcmc = MCMCConfig(cap_max=a.cap_max)
     cfg = HT.TrainConfig(
+        strategy=a.strategy, mcmc=mcmc,
         dataset=a.data, model=a.model, iters=a.iters, sh_degree=a.sh_degree, num_downscales=a.num_downscales,
         resolution_schedule=a.resolution_schedule, background_color=a.background_color, densify=not a.no_densify,
         fused_render=a.fused_render, use_graph=a.use_graph, camera_optimizer=a.camera_optimizer,

@@ -41,7 +41,12 @@ CASES = {
     # the shape of test_deterministic_mode_makes_training_bitwise_reproducible (--device cuda)
     "gpu": dict(num_gaussians=20_000, init_gaussians=4_000, width=320, height=180, num_views=8, iters=150, sh_degree=3,
                 sh_degree_interval=40, densify=True, scene_scale=(0.01, 0.06), log_every=0),
+    # strategy="mcmc" (--device cuda only: relocation, noise and regularisers are HIP kernels): 2 000 -> cap 3 000
+    "gpu_mcmc": dict(num_gaussians=6000, init_gaussians=2000, width=160, height=90, num_views=4, iters=300, sh_degree=3,
+                     sh_degree_interval=60, strategy="mcmc", scene_scale=(0.01, 0.06), log_every=0),
 }
+MCMC = dict(cap_max=3000, refine_start_iter=20, refine_every=20)
+GPU_ONLY = ("gpu", "gpu_mcmc")
 GPU_REFINE = dict(warmup_length=40, refine_every=20, reset_alpha_every=6, stop_screen_size_at=200, stop_split_at=260)
 TIMING = ("seconds", "iters_per_s", "views_per_s", "peak_memory_bytes")
 
@@ -82,6 +87,10 @@ def _run(rank, world, port, q, name, device, sharded, ckpt):
     runs = [kw] if name != "resume" else [dict(kw, checkpoint_dir=ckpt), dict(kw, save_every=0, resume_from=ckpt)]
     for kw in runs:
         rcfg = RefineConfig(**(GPU_REFINE if name == "gpu" else REFINE)) if kw.get("densify") else None
+        if kw.get("strategy") == "mcmc":
+            from gs_fused import MCMCConfig
+
+            kw = dict(kw, mcmc=MCMCConfig(**MCMC))
         res = HT.train(HT.TrainConfig(refine=rcfg, sharded_adam=sharded, **kw),
                        torch.device(device, 0) if device == "cuda" else torch.device(device), rank, world)
         q.put((rank, {k: _hex(v) for k, v in res.items() if k not in TIMING and not k.startswith("phase_")}))
@@ -98,7 +107,7 @@ def main():
     ap.add_argument("--sharded", action="store_true", help="TrainConfig.sharded_adam")
     args = ap.parse_args()
     ctx = mp.get_context("spawn")
-    for name in args.cases or [c for c in CASES if c != "gpu"]:
+    for name in args.cases or [c for c in CASES if c not in GPU_ONLY]:
         with tempfile.TemporaryDirectory() as ckpt:
             with socket.socket() as s:
                 s.bind(("127.0.0.1", 0))
