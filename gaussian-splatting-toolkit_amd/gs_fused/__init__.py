@@ -17,3 +17,4 @@ from rasterizer.project_gaussians import project_gaussians_antialiased  # noqa: 
 from .crop import CropBox, crop_gaussians, project_gaussians_cropped  # noqa: F401
 from .knn import KNN, initial_log_scales, k_nearest, knn, knn_mean_distance  # noqa: F401
 from .target import DeferredTarget, ImageCache, plane_from_int, target_from_u8  # noqa: F401
+from .bilagrid import BilateralGrids, bilagrid_slice, bilagrid_tv_loss  # noqa: F401

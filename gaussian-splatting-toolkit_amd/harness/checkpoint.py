@@ -27,6 +27,9 @@ _PREFIX = "_model.gauss_params."  # pipeline.state_dict() key prefix of the refe
 # cameras/camera_optimizers.py:63-65); its Adam is the `camera_opt` group (camera_optimizers.py:145-150)
 _CAMERA_KEY = "_model.camera_optimizer.pose_adjustment"
 _CAMERA_GROUP = "camera_opt"
+# the per-view bilateral grids (gs_fused.BilateralGrids, [V,L,Gh,Gw,12]; `to_gsplat` gives gsplat's layout) and their Adam
+_BILAGRID_KEY = "_model.bilateral_grids.grids"
+_BILAGRID_GROUP = "bilateral_grid"
 
 
 def checkpoint_path(directory: str, step: int) -> str:
@@ -88,7 +91,8 @@ def sharded_state_dicts(sharded) -> Dict[str, dict]:
 
 
 def save_checkpoint(directory: str, step: int, model, optims: Dict[str, torch.optim.Optimizer],
-                    save_only_latest: bool = True, sharded=None, write: bool = True, camera=None) -> Optional[str]:
+                    save_only_latest: bool = True, sharded=None, write: bool = True, camera=None,
+                    bilagrid=None) -> Optional[str]:
     """trainer.py:444-476.  With `sharded` (a `parallel.ShardedAdam`) EVERY rank calls this -- the moments are
     gathered by a collective -- and only the rank with `write=True` touches the disk (the reference: rank 0,
     trainer.py:446 `@check_main_thread`).  `camera`: (harness.camera_opt.CameraOptimizer, its torch.optim.Adam) --
@@ -99,6 +103,9 @@ def save_checkpoint(directory: str, step: int, model, optims: Dict[str, torch.op
     if camera is not None:
         pipeline[_CAMERA_KEY] = camera[0].pose_adjustment.detach()
         opt_state[_CAMERA_GROUP] = camera[1].state_dict()
+    if bilagrid is not None:  # (gs_fused.BilateralGrids, its optimizer): the grids in their own channel-last layout
+        pipeline[_BILAGRID_KEY] = bilagrid[0].grids.detach()
+        opt_state[_BILAGRID_GROUP] = bilagrid[1].state_dict()
     if not write:
         return None
     os.makedirs(directory, exist_ok=True)
@@ -158,8 +165,24 @@ def load_camera_state(camera, loaded: dict) -> None:
         adam.load_state_dict(sd)
 
 
+def load_bilagrid_state(bilagrid, loaded: dict) -> None:
+    """The grids and their Adam state (`step`, `exp_avg`, `exp_avg_sq`, learning rate) from a loaded checkpoint; a
+    checkpoint written without grids leaves both as they are (identity maps, fresh moments)."""
+    module, adam = bilagrid
+    saved = loaded["pipeline"].get(_BILAGRID_KEY)
+    if saved is None:
+        return
+    if saved.shape != module.grids.shape:
+        raise ValueError(f"checkpoint has bilateral grids {tuple(saved.shape)}, the run {tuple(module.grids.shape)}")
+    with torch.no_grad():
+        module.grids.copy_(saved)
+    sd = loaded.get("optimizers", {}).get(_BILAGRID_GROUP)
+    if sd:
+        adam.load_state_dict(sd)
+
+
 def load_checkpoint(path: str, model, optims: Dict[str, torch.optim.Optimizer], trust_pickle: bool = False,
-                    sharded=None, camera=None) -> int:
+                    sharded=None, camera=None, bilagrid=None) -> int:
     """trainer.py:404-443 for one file or a directory (latest step).  The model is resized,
     every optimizer is pointed at the new parameter objects and gets the saved Adam state
     (``step``, ``exp_avg``, ``exp_avg_sq``) and learning rate.  Returns the step to resume
@@ -174,6 +197,8 @@ def load_checkpoint(path: str, model, optims: Dict[str, torch.optim.Optimizer], 
     load_model_state(model, loaded["pipeline"])
     if camera is not None:
         load_camera_state(camera, loaded)
+    if bilagrid is not None:
+        load_bilagrid_state(bilagrid, loaded)
     if sharded is not None:
         moments, steps = {}, []
         for name in PARAM_NAMES:

@@ -528,6 +528,24 @@ class TrainConfig:
     # the ground truth stays rendered from the true poses, so a synthetic run has something to recover
     pose_noise: tuple = (0.0, 0.0)
     pose_noise_seed: int = 20241019
+    # per-view bilateral grids (gs_fused.BilateralGrids; `use_bilateral_grid` of gsplat /
+    # splatfacto, whose values the defaults are): an eighth parameter group -- one (grid_w, grid_h, grid_l) grid of 3x4
+    # affine colour maps per training view under its own gs_fused.FusedAdam (eps 1e-15, `bilagrid_lr` warmed up from
+    # 1 % over 1000 steps and decayed to 1 % over `iters`) -- through which the loss heads see the rendered image
+    # (`grids.slice(out["rgb"], v)`; `out["rgb"]` stays the raw render), plus `bilagrid_tv_weight` times the grids'
+    # total variation in the loss.  Absorbs what differs photometrically from view to view (exposure, white balance,
+    # vignetting) instead of leaving it to floaters.  Evaluation renders without grids.  The separate ops and the
+    # one-node view on one GPU: `use_graph`, a world size above 1 and CPU tensors are refused.  Off: nothing changes.
+    bilateral_grid: bool = False
+    bilagrid_shape: tuple = (16, 16, 8)
+    bilagrid_lr: float = 2e-3
+    bilagrid_tv_weight: float = 10.0
+    # (sigma of the log-gain, sigma of the bias): every synthetic training target is multiplied once by a per-view,
+    # per-channel gain exp(N(0, sigma_gain)) and shifted by N(0, sigma_bias), drawn from `view_exposure_seed`, standing
+    # in for auto-exposure and white balance (a random background: the RGBA ground truth's colour is disturbed, its
+    # alpha is not); evaluation keeps the true images.  Not with `dataset`.
+    view_exposure: tuple = (0.0, 0.0)
+    view_exposure_seed: int = 20241020
     # a dataset directory (or its transforms.json) instead of the hidden synthetic scene: read by
     # gs_io.dataset.load_dataset with the `dataset_*` fields below (the dataparser's config,
     # gs_toolkit_dataparser.py:36-67), uploaded as integers into a gs_fused.ImageCache (uint8 images, uint8 masks,
@@ -650,6 +668,30 @@ def _check_camera_optimizer(cfg: TrainConfig, device, world: int) -> None:
         raise ValueError("camera_optimizer needs CUDA tensors: the camera gradients come from the HIP projection")
 
 
+def _check_bilateral_grid(cfg: TrainConfig, device, world: int) -> None:
+    """What `bilateral_grid` and `view_exposure` refuse, once the device and the world size are known."""
+    if tuple(cfg.view_exposure) != (0.0, 0.0):
+        if len(tuple(cfg.view_exposure)) != 2 or min(cfg.view_exposure) < 0:
+            raise ValueError(f"view_exposure must be two non-negative sigmas (gain, bias), got {cfg.view_exposure!r}")
+        if cfg.dataset is not None:
+            raise ValueError("view_exposure disturbs the synthetic targets: it does not apply to `dataset`")
+    if not cfg.bilateral_grid:
+        return
+    if cfg.use_graph:
+        raise ValueError("bilateral_grid does not run under use_graph: the view index is a constant of a capture, and "
+                         "the grids' gradient is written for one view")
+    if world > 1:
+        raise ValueError("bilateral_grid runs on one GPU (world size 1): the grids' gradients of a data-parallel run "
+                         "are not exchanged")
+    if device.type != "cuda":
+        raise ValueError("bilateral_grid needs CUDA tensors: the slice and its backward are HIP kernels")
+    from gs_fused.bilagrid import check_grid_shape
+
+    if len(tuple(cfg.bilagrid_shape)) != 3:
+        raise ValueError(f"bilagrid_shape must be (grid_w, grid_h, grid_l), got {cfg.bilagrid_shape!r}")
+    check_grid_shape(*(int(s) for s in cfg.bilagrid_shape))
+
+
 def _params(model: GaussianParams) -> Dict[str, torch.nn.Parameter]:
     return {k: model.gauss[k] for k in PARAM_NAMES}
 
@@ -679,6 +721,20 @@ class TrainData:
     true_cams_np: Optional[list] = None       # the cameras the ground truth was rendered from
     cache: Optional[object] = None            # `TrainConfig.dataset`: the gs_fused.ImageCache `gt` / `gt_depth` / `masks` read
     dataset: Optional[object] = None          # ... and the gs_io.dataset.Dataset it was filled from (the training split)
+    gt_train: Optional[List[torch.Tensor]] = None  # `view_exposure`: the disturbed targets the steps fit (`gt` stays true)
+    gt_rgba_train: Optional[List[torch.Tensor]] = None  # ... and, random background, the disturbed [H,W,4] images
+    exposure: Optional[Dict] = None           # ... and the per-view gains and biases that made them ([V,3] lists)
+
+
+def disturb_exposure(gt: List[torch.Tensor], sigma_gain: float, sigma_bias: float, seed: int):
+    """-> (targets, {"gain", "bias"}): every view times a per-channel gain exp(N(0, sigma_gain)) plus a per-channel
+    bias N(0, sigma_bias), drawn on the host from `seed` (the same on every device)."""
+    rng = np.random.default_rng(seed)
+    gain = np.exp(rng.standard_normal((len(gt), 3)) * sigma_gain).astype(np.float32)
+    bias = (rng.standard_normal((len(gt), 3)) * sigma_bias).astype(np.float32)
+    out = [(g * torch.from_numpy(gain[v]).to(g.device) + torch.from_numpy(bias[v]).to(g.device)).contiguous()
+           for v, g in enumerate(gt)]
+    return out, {"gain": gain.tolist(), "bias": bias.tolist()}
 
 
 class _CacheViews:
@@ -787,7 +843,14 @@ def make_data(cfg: TrainConfig, device) -> TrainData:
             masks = view_masks(cfg.mask, cfg.height, cfg.width,
                                [truth.render(c, bg, cfg.sh_degree)["alpha"] if cfg.mask == "alpha" else None
                                 for c in true_cams], device)
-    return TrainData(factors, cams_by_d, bg, gt, gt_rgba, gt_depth, masks, cams_np, true_np)
+    data = TrainData(factors, cams_by_d, bg, gt, gt_rgba, gt_depth, masks, cams_np, true_np)
+    if tuple(cfg.view_exposure) != (0.0, 0.0):  # the trainer's targets carry a photometric error; evaluation's do not
+        sg, sb = cfg.view_exposure
+        data.gt_train, data.exposure = disturb_exposure(gt, sg, sb, cfg.view_exposure_seed)
+        if gt_rgba is not None:  # random background: the straight colour is disturbed, the alpha is not (same draws)
+            colour, _ = disturb_exposure([g[..., :3] for g in gt_rgba], sg, sb, cfg.view_exposure_seed)
+            data.gt_rgba_train = [torch.cat((c, g[..., 3:]), dim=-1) for c, g in zip(colour, gt_rgba)]
+    return data
 
 
 def evaluate(model: GaussianParams, data: TrainData, cfg: TrainConfig, cams=None) -> Dict[str, Optional[float]]:
@@ -1018,18 +1081,19 @@ class StepInputs:
         if self.cache is not None:
             return self._from_cache(v, d)
         if self.bg_gen is None:
-            bg, target = data.bg, downscale_image(data.gt[v], d)
+            bg, target = data.bg, downscale_image((data.gt if data.gt_train is None else data.gt_train)[v], d)
         else:
             bg = torch.rand(3, device=self.device, generator=self.bg_gen)
+            rgba = data.gt_rgba if data.gt_rgba_train is None else data.gt_rgba_train
             if self.fused_target:
                 planes = self.target_cache.get((v, d))
                 if planes is None:
-                    small = downscale_image(data.gt_rgba[v], d)
+                    small = downscale_image(rgba[v], d)
                     a = small[..., 3:4]
                     planes = self.target_cache[(v, d)] = ((a * small[..., :3]).contiguous(), (1 - a).contiguous())
                 target = torch.addcmul(planes[0], planes[1], bg)
             else:
-                target = composite_with_background(downscale_image(data.gt_rgba[v], d), bg)
+                target = composite_with_background(downscale_image(rgba[v], d), bg)
             if self.bg_static is not None:
                 self.bg_static.copy_(bg)
                 bg = self.bg_static
@@ -1150,6 +1214,7 @@ class FusedStep:
 
         self.graph_loss = graph_loss  # (a closure over the head alone: a ViewGraph holds it, and must not hold this)
         self.caps = ListCapacity()
+        self.bilagrid = None  # a BilagridGroup: the head sees the view through its grid (not under use_graph)
         self.vgraph = self.vkey = None
         self.overflow_views = 0
         cam, g_ = data.cams_by_d[1][0], model.gauss
@@ -1182,7 +1247,10 @@ class FusedStep:
             out = self.render_gaussians(g_["means"], g_["scales"], g_["quats"], g_["opacities"], g_["features_dc"],
                                         g_["features_rest"], cam.viewmat, cam.projmat, cam.campos, bg, spec, used,
                                         count_out=slot, stats=fstats, sh_collector=collector)
-            loss = self.photo(out["rgb"], target, mask)
+            if self.bilagrid is None:
+                loss = self.photo(out["rgb"], target, mask)
+            else:  # the heads see the view through its grid; out["rgb"] stays the raw render
+                loss = self.bilagrid.add_regulariser(self.photo(self.bilagrid.apply(out["rgb"], v), target, mask))
             if self.mcfg is not None:
                 loss = _add_mcmc_regulariser(loss, self.model, self.mcfg)
             loss.backward()
@@ -1259,6 +1327,7 @@ class SeparateStep:
         self.marks = []  # (downscale factor, 5 events, depth loss on) per sampled step
         self.camera_opt = None  # a camera_opt.CameraOptimizer: its regulariser joins the loss (get_loss_dict)
         self.mcfg = None  # a gs_fused.MCMCConfig: the opacity / scale regularisers join the loss
+        self.bilagrid = None  # a BilagridGroup: the heads see the view through its grid, its TV term joins the loss
 
     def __call__(self, step, v, d, cam, deg, bg, target, mask):
         _zero_grads(self.model)
@@ -1268,7 +1337,10 @@ class SeparateStep:
         out = self.model.render(cam, bg, deg, **self.render_kw)
         if ph:
             ph[1].record()
-        loss = self.photo(out["rgb"], target, mask)
+        if self.bilagrid is None:
+            loss = self.photo(out["rgb"], target, mask)
+        else:  # the heads see the view through its grid; out["rgb"] stays the raw render
+            loss = self.bilagrid.add_regulariser(self.photo(self.bilagrid.apply(out["rgb"], v), target, mask))
         if self.cogs:
             self.depth_on = step > self.depth_after
             # (a dataset: the integer depth resized by the cache's kernel, so nothing is left to downscale)
@@ -1319,6 +1391,52 @@ class CameraGroup:
 
 def make_camera_optimiser(cfg: TrainConfig, data: TrainData, device) -> Optional[CameraGroup]:
     return None if cfg.camera_optimizer == "off" else CameraGroup(cfg, data, device)
+
+
+class BilagridGroup:
+    """The eighth parameter group: `gs_fused.BilateralGrids` over the training views and its own gs_fused.FusedAdam
+    with gsplat's schedule (`gs_fused.bilagrid.lr_schedule` over `cfg.iters`)."""
+
+    def __init__(self, cfg: TrainConfig, device):
+        from gs_fused import BilateralGrids, FusedAdam
+
+        self.cfg = cfg
+        gw, gh, gl = (int(s) for s in cfg.bilagrid_shape)
+        self.grids = BilateralGrids(cfg.num_views, gw, gh, gl, device=device)
+        self.adam = FusedAdam([self.grids.grids], lr=self.lr(0), eps=1e-15)
+
+    def lr(self, step: int) -> float:
+        from gs_fused.bilagrid import lr_schedule
+
+        return lr_schedule(step, self.cfg.bilagrid_lr, self.cfg.iters)
+
+    def begin_step(self, step: int) -> None:
+        """Zero the group's gradient and set this step's learning rate."""
+        self.adam.zero_grad(set_to_none=True)
+        self.adam.param_groups[0]["lr"] = self.lr(step)
+
+    def apply(self, rgb: torch.Tensor, v: int) -> torch.Tensor:
+        """What the loss heads see of view `v`'s render."""
+        return self.grids.slice(rgb, int(v))
+
+    def add_regulariser(self, loss: torch.Tensor) -> torch.Tensor:
+        return loss + self.cfg.bilagrid_tv_weight * self.grids.tv_loss()
+
+    def record(self) -> Dict:
+        from gs_fused.bilagrid import IDENTITY
+
+        with torch.no_grad():
+            g = self.grids.grids
+            eye = torch.tensor(IDENTITY, dtype=g.dtype, device=g.device)
+            away = (g - eye).abs().amax(dim=(1, 2, 3, 4))
+            return {"bilateral_grid": {"shape": list(self.grids.shape), "tv_weight": self.cfg.bilagrid_tv_weight,
+                                       "lr": self.cfg.bilagrid_lr, "tv_end": float(self.grids.tv_loss()),
+                                       "max_abs_from_identity": [float(a) for a in away.cpu()],
+                                       "checksum": float(g.double().sum())}}
+
+
+def make_bilagrid(cfg: TrainConfig, device) -> Optional[BilagridGroup]:
+    return BilagridGroup(cfg, device) if cfg.bilateral_grid else None
 
 
 def pose_errors(cfg: TrainConfig, data: TrainData, camera: Optional[CameraGroup], device):
@@ -1457,7 +1575,7 @@ def result_record(cfg: TrainConfig, device, world: int, model, run: Dict, eval0:
             "densify_grad_thresh": (run["rcfg"].densify_grad_thresh if cfg.densify else None),
             # (only where it was asked for, as above)
             **({"dataset": run["dataset"]} if run.get("dataset") is not None else {}),
-            **run.get("pose", {})}
+            **run.get("pose", {}), **run.get("appearance", {})}
 
 
 def _note_bytes(log: list, step: int, nbytes: int) -> None:
@@ -1472,6 +1590,7 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
     _check_camera_optimizer(cfg, device, world)
     _check_absgrad(cfg, device)
     _check_mcmc(cfg, device, world)
+    _check_bilateral_grid(cfg, device, world)
     cuda = device.type == "cuda"
     mcfg = None
     if cfg.strategy == "mcmc":
@@ -1503,11 +1622,13 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
     n0 = model.num_points
     start_step = 0
     camera = make_camera_optimiser(cfg, data, device)
+    bilagrid = make_bilagrid(cfg, device)
     if cfg.resume_from:
         from .checkpoint import load_checkpoint
 
         start_step = load_checkpoint(cfg.resume_from, model, optims, sharded=sharded,  # resizes the model to the saved N
-                                     camera=None if camera is None else (camera.opt, camera.adam))
+                                     camera=None if camera is None else (camera.opt, camera.adam),
+                                     **({} if bilagrid is None else {"bilagrid": (bilagrid.grids, bilagrid.adam)}))
     use_fused = (cfg.fused_render or cfg.use_graph) and cuda and cfg.split_sh and cfg.fused_loss \
         and cfg.sh_degree in (0, 1, 2, 3)
     kernel = None
@@ -1545,6 +1666,7 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
             run_step = SeparateStep(cfg, model, data, heads, exchange, sh_views, device)
             run_step.camera_opt = None if camera is None else camera.opt
             run_step.mcfg = mcfg
+        run_step.bilagrid = bilagrid
         rebuilds0 = _list_rebuilds()
         for step in range(start_step, cfg.iters):
             v = view_for_rank(step, rank, world, cfg.num_views)
@@ -1557,6 +1679,8 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
             bg_step, target, m_step = inputs(v, d)
             if camera is not None:  # this step's camera, a function of the view's six numbers
                 cam = camera.step_camera(step, v, cam)
+            if bilagrid is not None:
+                bilagrid.begin_step(step)
             loss, out = run_step(step, v, d, cam, deg, bg_step, target, m_step)
             stats.update(out, max_dim, step)
             if dp and sharded is None:
@@ -1571,6 +1695,8 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
                 o.step()
             if camera is not None:
                 camera.adam.step()
+            if bilagrid is not None:
+                bilagrid.adam.step()
             if sharded is not None:
                 _note_bytes(exchanged_bytes, step, sharded.step())
             if run_step.ph:
@@ -1592,7 +1718,8 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
 
                 # (sharded moments are gathered by a collective: every rank calls, rank 0 writes)
                 save_checkpoint(cfg.checkpoint_dir, step, model, optims, sharded=sharded, write=rank == 0,
-                                camera=None if camera is None else (camera.opt, camera.adam))
+                                camera=None if camera is None else (camera.opt, camera.adam),
+                                **({} if bilagrid is None else {"bilagrid": (bilagrid.grids, bilagrid.adam)}))
             if cfg.log_every and step % cfg.log_every == 0:
                 losses.append(float(loss.detach()))
         if dp:
@@ -1625,6 +1752,8 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
            "render": ("hip graph per view" if cfg.use_graph else "one fused op") if use_fused else "separate ops",
            "overflow_views": run_step.overflow_views + (_list_rebuilds() - rebuilds0),
            "pose": pose_record(camera, pose0, pose1),
+           "appearance": {**({} if bilagrid is None else bilagrid.record()),
+                          **({} if data.exposure is None else {"view_exposure": data.exposure})},
            "update": "reduce-scatter + sharded Adam + all-gather" if sharded is not None else
            ("all-reduce (geometry) + all-gathered colour cotangents (SH) + Adam" if sh_views else "all-reduce + Adam")}
     return result_record(cfg, device, world, model, run, eval0, eval1, phase_record(run_step.marks, cfg, data.factors))

@@ -136,6 +136,10 @@ SYMBOLS = (
     "gsr_log_depth_backward",
     "gsr_tv_forward",
     "gsr_tv_backward",
+    "gsr_bilagrid_slice_forward",
+    "gsr_bilagrid_slice_backward",
+    "gsr_bilagrid_tv_forward",
+    "gsr_bilagrid_tv_backward",
     "gsr_knn_workspace_bytes",
     "gsr_knn_build",
     "gsr_knn_query",

@@ -1476,6 +1476,61 @@ int gsr_tv_forward(unsigned img_height, unsigned img_width, const float *pred, c
 int gsr_tv_backward(unsigned img_height, unsigned img_width, const float *upstream,
                     const float *pred, const float *mask, float *v_pred, gsr_stream_t stream);
 
+/* ---- per-view bilateral grids (csrc/bilagrid.hip) ----------------------
+ * Appearance compensation between the render and the loss heads: every training view owns a
+ * small 3-D grid of 3x4 affine colour maps, and a rendered pixel is mapped by the grid's value
+ * at (its position, its brightness) -- what gsplat's `lib_bilagrid.slice` does, i.e.
+ * F.grid_sample(grid[v:v+1], 2 (xyz - 0.5), "bilinear", align_corners=True,
+ * padding_mode="border") followed by the affine map.
+ *   grids  float [V][L][Gh][Gw][12], channel last (a vertex is three 16-byte loads), 16-byte
+ *          aligned; the 12 channels are a row-major 3x4 map; Gw, Gh in [2, GSR_BILAGRID_MAX_XY],
+ *          L in [2, GSR_BILAGRID_MAX_L]; view in [0, V)
+ *   rgb    float [H][W][3];  out, v_out, v_rgb the same shape;  3 H W < 2^31
+ * The rule, for pixel (px, py) with colour (r, g, b):
+ *   x = (px + 0.5) / W          y = (py + 0.5) / H
+ *   guide = 0.299 r + 0.587 g + 0.114 b
+ *   ix = x (Gw - 1)   iy = y (Gh - 1)   iz = clamp(guide, 0, 1) (L - 1)
+ *   M  = trilinear interpolation of grids[view] at (iz, iy, ix)      (12 values, 8 corners)
+ *   out[k] = M[4k] r + M[4k+1] g + M[4k+2] b + M[4k+3]               k = 0, 1, 2
+ * Backward, from v_out:
+ *   v_grids[view][corner][4k+j] = sum over the pixels of weight(pixel, corner) v_out[k] (r, g, b, 1)[j]
+ *   v_grids[other views]        = exact zeros; so are vertices that no pixel reaches (an image
+ *                                 smaller than the grid).  Every element of v_grids is written.
+ *   v_rgb[c] = sum_k M[4k+c] v_out[k]
+ *              + [0 < guide < 1] (L - 1) (0.299, 0.587, 0.114)[c] sum_k v_out[k] (dM/diz)[4k..4k+3] . (r, g, b, 1)
+ *   (the path through the guide is zero where the guide is clamped: grid_sample's border rule).
+ * Per-pixel arithmetic is float32; every sum over pixels is float64 in a fixed order, without
+ * atomics: two runs are bit-equal.  NaN and inf in rgb propagate into out; a NaN guide reads
+ * level 0.
+ *   workspace  double [GSR_BILAGRID_WORKSPACE_DOUBLES(Gw, Gh, L)] (backward); needs no zeroing
+ * Total variation over all views:
+ *   tv = sum over the axes L, Gh, Gw of mean((A[.. i+1 ..] - A[.. i ..])^2), each mean over all
+ *        difference elements of that axis across views and channels
+ *   v_grids = upstream * d tv / d A (every element written), float64 arithmetic
+ *   partial  double [GSR_BILAGRID_TV_WORKSPACE_DOUBLES]; needs no zeroing
+ * The identity map is (1,0,0,0, 0,1,0,0, 0,0,1,0) at every vertex. */
+#define GSR_BILAGRID_CHANNELS 12
+#define GSR_BILAGRID_MAX_XY 64
+#define GSR_BILAGRID_MAX_L 16
+/* row strips a vertex's pixel rectangle is cut into (one workgroup each) */
+#define GSR_BILAGRID_STRIPS(gw, gh) \
+  ((gw) * (gh) >= 2048 ? 1 : ((gw) * (gh) <= 32 ? 64 : 2048 / ((gw) * (gh))))
+#define GSR_BILAGRID_WORKSPACE_DOUBLES(gw, gh, gl) \
+  ((size_t)GSR_BILAGRID_STRIPS(gw, gh) * (size_t)(gw) * (size_t)(gh) * (size_t)(gl) * GSR_BILAGRID_CHANNELS)
+#define GSR_BILAGRID_TV_WORKSPACE_DOUBLES 3072
+int gsr_bilagrid_slice_forward(unsigned img_height, unsigned img_width, int num_views, int view,
+                               int grid_w, int grid_h, int grid_l, const float *grids,
+                               const float *rgb, float *out, gsr_stream_t stream);
+int gsr_bilagrid_slice_backward(unsigned img_height, unsigned img_width, int num_views, int view,
+                                int grid_w, int grid_h, int grid_l, const float *grids,
+                                const float *rgb, const float *v_out, double *workspace,
+                                float *v_rgb, float *v_grids, gsr_stream_t stream);
+int gsr_bilagrid_tv_forward(int num_views, int grid_w, int grid_h, int grid_l, const float *grids,
+                            double *partial, float *loss_out, gsr_stream_t stream);
+int gsr_bilagrid_tv_backward(int num_views, int grid_w, int grid_h, int grid_l,
+                             const float *upstream, const float *grids, float *v_grids,
+                             gsr_stream_t stream);
+
 /* ---- k nearest neighbours: points against a point cloud ----------------
  * What the toolkit's models ask scikit-learn for when they turn seed points into initial scales
  * (`k_nearest_sklearn`, vanilla_gs.py:136-140, 260-280), as a general query.  Reference points P

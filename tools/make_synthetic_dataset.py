@@ -56,9 +56,13 @@ def to_u8(x: torch.Tensor) -> np.ndarray:
 def make_synthetic_dataset(out: str, views: int = 12, width: int = 64, height: int = 48, alpha: bool = True,
                            depth: bool = True, mask: bool = True, device="cpu", scene: str = "ball",
                            num_gaussians: int = 600, seed_points: int = 200, seed: int = 0, per_frame: bool = False,
-                           scene_scale=(0.03, 0.15), extra_meta=None) -> dict:
+                           scene_scale=(0.03, 0.15), extra_meta=None, view_exposure=(0.0, 0.0),
+                           view_exposure_seed: int = 20241020) -> dict:
     """Writes the directory and returns the transforms.json dict.  `device` "cpu" needs the stand-ins wired
-    (`use_cpu_standins`), as every CPU run of the harness does."""
+    (`use_cpu_standins`), as every CPU run of the harness does.  `view_exposure` (sigma of the log-gain, sigma of the
+    bias): every image's colour is disturbed per view and channel before it is quantised, as
+    `TrainConfig.view_exposure` disturbs the trainer's targets (`harness.train.disturb_exposure`); the gains and biases
+    go into transforms.json under "view_exposure"."""
     from PIL import Image
 
     import harness.train as HT
@@ -71,6 +75,10 @@ def make_synthetic_dataset(out: str, views: int = 12, width: int = 64, height: i
                          background_color="random" if alpha else "fixed", model="co-gs" if depth else "gaussian-splatting",
                          mask="alpha" if mask else "none")
     data = HT.make_data(cfg, device)
+    colour = [g[..., :3] for g in (data.gt_rgba if alpha else data.gt)]
+    exposure = None
+    if tuple(view_exposure) != (0.0, 0.0):
+        colour, exposure = HT.disturb_exposure(colour, view_exposure[0], view_exposure[1], view_exposure_seed)
     for sub in ("images", "depths", "masks"):
         os.makedirs(os.path.join(out, sub), exist_ok=True)
     cam0 = data.true_cams_np[0]
@@ -82,7 +90,7 @@ def make_synthetic_dataset(out: str, views: int = 12, width: int = 64, height: i
     frames = []
     for v, cam in enumerate(data.true_cams_np):
         name = f"frame_{v:05d}.png"
-        img = to_u8(data.gt_rgba[v] if alpha else data.gt[v])
+        img = to_u8(torch.cat((colour[v], data.gt_rgba[v][..., 3:]), dim=-1) if alpha else colour[v])
         Image.fromarray(img, "RGBA" if alpha else "RGB").save(os.path.join(out, "images", name))
         fr = {"file_path": f"images/{name}", "transform_matrix": camera_to_world_gl(cam.viewmat).astype(float).tolist()}
         if per_frame:
@@ -105,6 +113,8 @@ def make_synthetic_dataset(out: str, views: int = 12, width: int = 64, height: i
     write_point_cloud_ply(os.path.join(out, "sparse_pc.ply"), truth["means"][pick], rgb)
     meta["ply_file_path"] = "sparse_pc.ply"
     meta["frames"] = frames
+    if exposure is not None:
+        meta["view_exposure"] = exposure
     meta.update(extra_meta or {})
     with open(os.path.join(out, "transforms.json"), "w", encoding="utf-8") as f:
         json.dump(meta, f, indent=1)
@@ -125,13 +135,15 @@ def main():
     ap.add_argument("--gaussians", type=int, default=600)
     ap.add_argument("--seed-points", type=int, default=200)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--view-exposure", type=float, nargs=2, default=[0.0, 0.0], metavar=("G", "B"),
+                    help="per-view, per-channel gain exp(N(0, G)) and bias N(0, B) on every image")
     ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu", choices=["cpu", "cuda"])
     args = ap.parse_args()
     if args.device == "cpu":
         use_cpu_standins()
     meta = make_synthetic_dataset(args.out, args.views, args.width, args.height, args.alpha, not args.no_depth,
                                   not args.no_mask, args.device, args.scene, args.gaussians, args.seed_points,
-                                  args.seed, args.per_frame)
+                                  args.seed, args.per_frame, view_exposure=tuple(args.view_exposure))
     print(json.dumps({"out": args.out, "frames": len(meta["frames"]), "width": args.width, "height": args.height}))
 
 

@@ -3,7 +3,7 @@
 
     python tools/train_dataset.py DATA [--model gaussian-splatting|co-gs] [--iters 30000] [--output-dir outputs]
         [--eval-mode fraction|filename|interval|all] [--fused-render] [--use-graph] [--camera-optimizer SO3xR3]
-        [--strategy default|mcmc [--cap-max 1000000]] ...
+        [--strategy default|mcmc [--cap-max 1000000]] [--bilateral-grid [--bilagrid-shape X Y L]] ...
 
 `harness.train.train` with `TrainConfig.dataset`: the files are uploaded as integers into a
 gs_fused.ImageCache and every step's target comes from one kernel.  Writes `OUTPUT_DIR/step-*.ckpt` (the toolkit's
@@ -39,6 +39,10 @@ def parse_args(argv=None):
     ap.add_argument("--fused-render", action="store_true")
     ap.add_argument("--use-graph", action="store_true")
     ap.add_argument("--camera-optimizer", default="off", choices=["off", "SO3xR3", "SE3"])
+    ap.add_argument("--bilateral-grid", action="store_true",
+                    help="per-view bilateral grids between the render and the loss (exposure, white balance); not with "
+                         "--use-graph")
+    ap.add_argument("--bilagrid-shape", type=int, nargs=3, default=[16, 16, 8], metavar=("X", "Y", "L"))
     ap.add_argument("--depth-loss-start-iteration", type=int, default=6000)
     ap.add_argument("--save-every", type=int, default=2000)
     ap.add_argument("--seed", type=int, default=0)
@@ -73,6 +77,7 @@ def main(argv=None):
         dataset=a.data, model=a.model, iters=a.iters, sh_degree=a.sh_degree, num_downscales=a.num_downscales,
         resolution_schedule=a.resolution_schedule, background_color=a.background_color, densify=not a.no_densify,
         fused_render=a.fused_render, use_graph=a.use_graph, camera_optimizer=a.camera_optimizer,
+        bilateral_grid=a.bilateral_grid, bilagrid_shape=tuple(a.bilagrid_shape),
         depth_loss_start_iteration=a.depth_loss_start_iteration, checkpoint_dir=a.output_dir, save_every=save_every,
         seed=a.seed, means_lr_schedule=True, log_every=max(a.iters // 100, 1),
         dataset_eval_mode=a.eval_mode, dataset_train_split_fraction=a.train_split_fraction,
