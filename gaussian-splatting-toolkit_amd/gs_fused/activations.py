@@ -10,14 +10,13 @@ as ~9 small launches forward and ~12 backward per iteration.  `activate_gaussian
 returns the same four tensors from one kernel (`gsr_activate_forward`) and
 back-propagates through the first three with one kernel (`gsr_activate_backward`).
 """
-import ctypes as C
 from typing import Optional, Tuple
 
 import torch
 from torch import Tensor
 from torch.autograd import Function
 
-from rasterizer.cuda import _call, _check, _ptr, _stream
+from rasterizer.cuda import _call, _check, _stream
 
 _f32 = torch.float32
 
@@ -38,9 +37,8 @@ class _Activate(Function):
             quats = torch.empty_like(raw_quats)
             opac = torch.empty_like(opacity_logits)
             dirs = torch.empty((n, 3), dtype=_f32, device=dev) if want_dirs else None
-            _call("gsr_activate_forward", C.c_int(n), _ptr(means) if want_dirs else None, _ptr(log_scales),
-                  _ptr(raw_quats), _ptr(opacity_logits), _ptr(campos) if want_dirs else None, _ptr(scales),
-                  _ptr(quats), _ptr(opac), _ptr(dirs) if want_dirs else None, _stream(dev))
+            _call("gsr_activate_forward", n, means if want_dirs else None, log_scales, raw_quats, opacity_logits,
+                  campos if want_dirs else None, scales, quats, opac, dirs if want_dirs else None, _stream(dev))
         ctx.save_for_backward(raw_quats, scales, quats, opac)
         ctx.set_materialize_grads(False)
         from rasterizer.ahead import announce_opacity
@@ -62,8 +60,8 @@ class _Activate(Function):
             g_s = torch.empty_like(scales)
             g_q = torch.empty_like(quats)
             g_o = torch.empty_like(opac)
-            _call("gsr_activate_backward", C.c_int(n), _ptr(raw_quats), _ptr(scales), _ptr(quats), _ptr(opac),
-                  *[None if t is None else _ptr(t) for t in cot], _ptr(g_s), _ptr(g_q), _ptr(g_o), _stream(dev))
+            _call("gsr_activate_backward", n, raw_quats, scales, quats, opac, *cot, g_s, g_q, g_o,
+                  _stream(dev))
         return None, g_s, g_q, g_o, None
 
 
@@ -111,11 +109,9 @@ def densify_stats_(xys_grad: Optional[Tensor], radii: Tensor, image_size: int, x
             raise ValueError("a device-side `first` is one int32 element on the device of radii")
         _check(first, "first", torch.int32)
         with torch.cuda.device(dev):
-            _call("gsr_densify_stats_dev", C.c_int(n), _ptr(xys_grad) if xys_grad is not None else None, _ptr(radii),
-                  C.c_float(1.0 / float(image_size)), _ptr(first), _ptr(xys_grad_norm), _ptr(vis_counts),
-                  _ptr(max_2dsize), _stream(dev))
+            _call("gsr_densify_stats_dev", n, xys_grad, radii, 1.0 / float(image_size), first, xys_grad_norm,
+                  vis_counts, max_2dsize, _stream(dev))
         return
     with torch.cuda.device(dev):
-        _call("gsr_densify_stats", C.c_int(n), _ptr(xys_grad) if xys_grad is not None else None, _ptr(radii),
-              C.c_float(1.0 / float(image_size)), C.c_int(1 if first else 0), _ptr(xys_grad_norm),
-              _ptr(vis_counts), _ptr(max_2dsize), _stream(dev))
+        _call("gsr_densify_stats", n, xys_grad, radii, 1.0 / float(image_size), 1 if first else 0, xys_grad_norm,
+              vis_counts, max_2dsize, _stream(dev))

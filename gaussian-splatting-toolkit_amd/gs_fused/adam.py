@@ -73,6 +73,5 @@ class FusedAdam(torch.optim.Optimizer):
                     arr = (_AdamTensor * len(chunk))()
                     for j, (p, g, m, v, lr) in enumerate(chunk):
                         arr[j] = _AdamTensor(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr)
-                    _call("gsr_adam_step", C.c_int(len(chunk)), arr, C.c_double(b1), C.c_double(b2),
-                          C.c_double(eps), C.c_longlong(step), _stream(dev))
+                    _call("gsr_adam_step", len(chunk), arr, b1, b2, eps, step, _stream(dev))
         return loss

@@ -10,13 +10,12 @@ mapped by the grid's value at (its position, its brightness), and a total-variat
 `grids` is [V,L,Gh,Gw,12] float32, channel last (gsplat stores [V,12,L,Gh,Gw]: `to_gsplat` / `from_gsplat`).  float32
 per-pixel arithmetic, float64 sums over pixels in a fixed order without atomics: two runs are bit-equal.  CUDA tensors
 only; no CPU fallback."""
-import ctypes as C
 
 import torch
 from torch import Tensor
 from torch.autograd import Function
 
-from rasterizer.cuda import _call, _check, _ptr, _stream
+from rasterizer.cuda import _call, _check, _stream
 
 _f32 = torch.float32
 CHANNELS = 12               # GSR_BILAGRID_CHANNELS (include/gsraster.h)
@@ -83,8 +82,7 @@ class _Slice(Function):
         dev = g.device
         with torch.cuda.device(dev):
             out = torch.empty_like(x)
-            _call("gsr_bilagrid_slice_forward", C.c_uint(H), C.c_uint(W), C.c_int(V), C.c_int(view), C.c_int(gw),
-                  C.c_int(gh), C.c_int(gl), _ptr(g), _ptr(x), _ptr(out), _stream(dev))
+            _call("gsr_bilagrid_slice_forward", H, W, V, view, gw, gh, gl, g, x, out, _stream(dev))
         ctx.save_for_backward(g, x)
         ctx.view = view
         return out
@@ -100,8 +98,7 @@ class _Slice(Function):
             work = torch.empty((workspace_doubles(gw, gh, gl),), dtype=torch.float64, device=dev)
             v_rgb = torch.empty_like(x)
             v_grids = torch.empty_like(g)
-            _call("gsr_bilagrid_slice_backward", C.c_uint(H), C.c_uint(W), C.c_int(V), C.c_int(ctx.view), C.c_int(gw),
-                  C.c_int(gh), C.c_int(gl), _ptr(g), _ptr(x), _ptr(v_out), _ptr(work), _ptr(v_rgb), _ptr(v_grids),
+            _call("gsr_bilagrid_slice_backward", H, W, V, ctx.view, gw, gh, gl, g, x, v_out, work, v_rgb, v_grids,
                   _stream(dev))
         return v_grids, v_rgb, None
 
@@ -125,8 +122,7 @@ class _TV(Function):
         with torch.cuda.device(dev):
             work = torch.empty((TV_WORKSPACE_DOUBLES,), dtype=torch.float64, device=dev)
             loss = torch.empty((), dtype=_f32, device=dev)
-            _call("gsr_bilagrid_tv_forward", C.c_int(V), C.c_int(gw), C.c_int(gh), C.c_int(gl), _ptr(g), _ptr(work),
-                  _ptr(loss), _stream(dev))
+            _call("gsr_bilagrid_tv_forward", V, gw, gh, gl, g, work, loss, _stream(dev))
         ctx.save_for_backward(g)
         return loss
 
@@ -138,8 +134,7 @@ class _TV(Function):
         up = v_loss.to(_f32).reshape(1).contiguous()
         with torch.cuda.device(dev):
             v_grids = torch.empty_like(g)
-            _call("gsr_bilagrid_tv_backward", C.c_int(V), C.c_int(gw), C.c_int(gh), C.c_int(gl), _ptr(up), _ptr(g),
-                  _ptr(v_grids), _stream(dev))
+            _call("gsr_bilagrid_tv_backward", V, gw, gh, gl, up, g, v_grids, _stream(dev))
         return v_grids
 
 

@@ -12,20 +12,19 @@ the co-gs model with `use_depth_regularization`.  Here the image stays on the de
 defaults (aperture 3, L1 gradient), restated -- is the specification in `include/gsraster.h`; `tests/canny_reference.py`
 restates it in NumPy + SciPy.  All arithmetic is integer: results are exact and the same on every run.
 """
-import ctypes as C
 from typing import Optional
 
 import torch
 from torch import Tensor
 
-from rasterizer.cuda import _call, _check, _lib, _ptr, _stream
+from rasterizer.cuda import _call, _check, _stream, _typed
 
 _f32, _u8 = torch.float32, torch.uint8
 
 
 def canny_workspace_bytes(height: int, width: int) -> int:
     """Bytes of scratch `canny` needs for an H x W image (6 per pixel; nothing in it has to be zeroed)."""
-    return int(_lib().gsr_canny_workspace_bytes(C.c_int(int(height)), C.c_int(int(width))))
+    return int(_typed().gsr_canny_workspace_bytes(int(height), int(width)))
 
 
 def canny(image: Tensor, thres1: float = 50, thres2: float = 150, out: Optional[Tensor] = None,
@@ -55,8 +54,7 @@ def canny(image: Tensor, thres1: float = 50, thres2: float = 150, out: Optional[
             workspace = torch.empty((need,), dtype=_u8, device=dev)
         else:
             _check(workspace, "workspace", _u8)
-        _call("gsr_canny", C.c_int(H), C.c_int(W), _ptr(image), C.c_float(float(thres1)), C.c_float(float(thres2)),
-              _ptr(workspace), C.c_size_t(workspace.numel()), _ptr(out), _stream(dev))
+        _call("gsr_canny", H, W, image, float(thres1), float(thres2), workspace, workspace.numel(), out, _stream(dev))
     return out
 
 

@@ -4,15 +4,13 @@ through scikit-learn's `NearestNeighbors` in `k_nearest_sklearn`, :260-280).  Th
 (DESIGN.md section 4.9); HIP kernels behind `gsr_knn_build` / `gsr_knn_query` (csrc/knn.hip); torch for memory and
 streams only; no CPU path.
 """
-import ctypes as C
 from typing import Optional, Tuple
 
 import numpy as np
 import torch
 from torch import Tensor
 
-from rasterizer.cuda import _check, _on, _stream
-from rasterizer.cuda._backend import lib as _lib
+from rasterizer.cuda import _check, _on, _stream, _typed
 
 _f32, _i32 = torch.float32, torch.int32
 GSR_ERANGE = -4
@@ -21,12 +19,8 @@ MAX_K = 16
 BYTES_TREE, BYTES_BUILD, BYTES_QUERY = range(3)
 
 
-def _ptr(t: Optional[Tensor]) -> C.c_void_p:
-    return C.c_void_p(None if t is None or t.numel() == 0 else t.data_ptr())
-
-
 def _bytes(what: int, n: int, m: int, k: int = 1) -> int:
-    b = _lib().gsr_knn_workspace_bytes(C.c_int(what), C.c_int(n), C.c_int(m), C.c_int(k))
+    b = _typed().gsr_knn_workspace_bytes(what, n, m, k)
     if b == 0:
         raise ValueError(f"{n} points / {m} queries / k = {k}: too large, or a size query failed (no device?)")
     return b
@@ -66,9 +60,8 @@ class KNN:
             self._tree = _space(_tree, _bytes(BYTES_TREE, n, 0), dev)
             ws = _space(_workspace, _bytes(BYTES_BUILD, n, 0), dev)
             state = torch.empty(4, dtype=_i32, device=dev)
-            L = _lib()
-            rc = L.gsr_knn_build(C.c_int(n), _ptr(points), _ptr(self._tree), C.c_size_t(self._tree.numel()), _ptr(ws),
-                                 C.c_size_t(ws.numel()), C.c_void_p(state.data_ptr()), _stream(dev))
+            L = _typed()
+            rc = L.gsr_knn_build(n, points, self._tree, self._tree.numel(), ws, ws.numel(), state, _stream(dev))
             if rc != 0:
                 raise RuntimeError(f"gsr_knn_build failed ({rc}): {L.gsr_last_error().decode()}")
             self.usable, self.skipped_points = (int(v) for v in state[:2].tolist())
@@ -97,11 +90,12 @@ class KNN:
                 idx = torch.empty((m, k), dtype=_i32, device=dev)
             ws = None if exhaustive or m == 0 else _space(_workspace, _bytes(BYTES_QUERY, 0, m, k), dev)
             state = torch.zeros(4, dtype=_i32, device=dev)
-            L = _lib()
-            rc = L.gsr_knn_query(C.c_int(self.num_points), _ptr(self._tree), C.c_size_t(self._tree.numel()),
-                                 C.c_int(self.usable), C.c_int(m), _ptr(q), C.c_int(k), C.c_int(flags), _ptr(ws),
-                                 C.c_size_t(0 if ws is None else ws.numel()), _ptr(dist), _ptr(idx),
-                                 C.c_void_p(state.data_ptr()), _stream(dev))
+            L = _typed()
+            # (no queries: the three [m, ...] tensors are empty and go as NULL)
+            rc = L.gsr_knn_query(self.num_points, self._tree, self._tree.numel(), self.usable, m,
+                                 None if q.numel() == 0 else q, k, flags, ws, 0 if ws is None else ws.numel(),
+                                 None if dist.numel() == 0 else dist, None if idx.numel() == 0 else idx, state,
+                                 _stream(dev))
             if rc == GSR_ERANGE:
                 raise ValueError(L.gsr_last_error().decode())
             if rc != 0:

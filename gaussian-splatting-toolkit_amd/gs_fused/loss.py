@@ -22,13 +22,12 @@ loss (vanilla_gs.py:915-924, surface_gs.py:917-925, depth_gs.py:424-437):
 products inside the same two kernels: the mask is multiplied in, nothing is selected, and
 the means stay over all pixels (the reference does not renormalise by the mask's area).
 """
-import ctypes as C
 
 import torch
 from torch import Tensor
 from torch.autograd import Function
 
-from rasterizer.cuda import _call, _check, _ptr, _stream
+from rasterizer.cuda import _call, _check, _stream
 
 _f32 = torch.float32
 WORKSPACE_DOUBLES = 2 * 64  # GSR_LOSS_WORKSPACE_DOUBLES (include/gsraster.h)
@@ -69,13 +68,11 @@ class _L1SSIM(Function):
             loss = torch.empty((), dtype=_f32, device=dev)
             terms = torch.empty((2,), dtype=_f32, device=dev)  # L1 mean, SSIM mean
             if mask is None:
-                _call("gsr_l1_ssim_forward", C.c_uint(H), C.c_uint(W), C.c_float(ssim_lambda),
-                      C.c_int(1 if clamp_pred else 0), _ptr(pred), _ptr(gt), _ptr(maps), _ptr(work), _ptr(loss),
-                      _ptr(terms), _stream(dev))
+                _call("gsr_l1_ssim_forward", H, W, ssim_lambda, 1 if clamp_pred else 0, pred, gt, maps, work, loss,
+                      terms, _stream(dev))
             else:
-                _call("gsr_l1_ssim_masked_forward", C.c_uint(H), C.c_uint(W), C.c_float(ssim_lambda),
-                      C.c_int(1 if clamp_pred else 0), _ptr(pred), _ptr(gt), _ptr(mask), _ptr(maps), _ptr(work),
-                      _ptr(loss), _ptr(terms), _stream(dev))
+                _call("gsr_l1_ssim_masked_forward", H, W, ssim_lambda, 1 if clamp_pred else 0, pred, gt, mask, maps,
+                      work, loss, terms, _stream(dev))
         if mask is None:
             ctx.save_for_backward(pred, gt, maps)
         else:
@@ -95,13 +92,11 @@ class _L1SSIM(Function):
         with torch.cuda.device(dev):
             v_pred = torch.empty_like(pred)
             if not masks:
-                _call("gsr_l1_ssim_backward", C.c_uint(H), C.c_uint(W), C.c_float(ctx.ssim_lambda),
-                      C.c_int(1 if ctx.clamp_pred else 0), _ptr(up), _ptr(pred), _ptr(gt), _ptr(maps), _ptr(v_pred),
-                      _stream(dev))
+                _call("gsr_l1_ssim_backward", H, W, ctx.ssim_lambda, 1 if ctx.clamp_pred else 0, up, pred, gt, maps,
+                      v_pred, _stream(dev))
             else:
-                _call("gsr_l1_ssim_masked_backward", C.c_uint(H), C.c_uint(W), C.c_float(ctx.ssim_lambda),
-                      C.c_int(1 if ctx.clamp_pred else 0), _ptr(up), _ptr(pred), _ptr(gt), _ptr(masks[0]), _ptr(maps),
-                      _ptr(v_pred), _stream(dev))
+                _call("gsr_l1_ssim_masked_backward", H, W, ctx.ssim_lambda, 1 if ctx.clamp_pred else 0, up, pred, gt,
+                      masks[0], maps, v_pred, _stream(dev))
         return v_pred, None, None, None, None
 
 
@@ -150,11 +145,10 @@ class _L1(Function):
             work = torch.empty((64,), dtype=torch.float64, device=dev)
             loss = torch.empty((), dtype=_f32, device=dev)
             if mask is None:
-                _call("gsr_l1_forward", C.c_longlong(pred.numel()), C.c_float(weight), C.c_int(1 if clamp_pred else 0),
-                      _ptr(pred), _ptr(gt), _ptr(work), _ptr(loss), _stream(dev))
+                _call("gsr_l1_forward", pred.numel(), weight, 1 if clamp_pred else 0, pred, gt, work, loss,
+                      _stream(dev))
             else:
-                _call("gsr_l1_masked_forward", C.c_longlong(pred.numel()), C.c_float(weight),
-                      C.c_int(1 if clamp_pred else 0), _ptr(pred), _ptr(gt), _ptr(mask), _ptr(work), _ptr(loss),
+                _call("gsr_l1_masked_forward", pred.numel(), weight, 1 if clamp_pred else 0, pred, gt, mask, work, loss,
                       _stream(dev))
         if mask is None:
             ctx.save_for_backward(pred, gt)
@@ -171,12 +165,11 @@ class _L1(Function):
         with torch.cuda.device(dev):
             v_pred = torch.empty_like(pred)
             if not masks:
-                _call("gsr_l1_backward", C.c_longlong(pred.numel()), C.c_float(ctx.weight),
-                      C.c_int(1 if ctx.clamp_pred else 0), _ptr(up), _ptr(pred), _ptr(gt), _ptr(v_pred), _stream(dev))
+                _call("gsr_l1_backward", pred.numel(), ctx.weight, 1 if ctx.clamp_pred else 0, up, pred, gt, v_pred,
+                      _stream(dev))
             else:
-                _call("gsr_l1_masked_backward", C.c_longlong(pred.numel()), C.c_float(ctx.weight),
-                      C.c_int(1 if ctx.clamp_pred else 0), _ptr(up), _ptr(pred), _ptr(gt), _ptr(masks[0]),
-                      _ptr(v_pred), _stream(dev))
+                _call("gsr_l1_masked_backward", pred.numel(), ctx.weight, 1 if ctx.clamp_pred else 0, up, pred, gt,
+                      masks[0], v_pred, _stream(dev))
         return v_pred, None, None, None, None
 
 
@@ -209,11 +202,9 @@ class _DepthL1(Function):
             work = torch.empty((64,), dtype=torch.float64, device=dev)
             loss = torch.empty((), dtype=_f32, device=dev)
             if mask is None:
-                _call("gsr_depth_l1_forward", C.c_longlong(d.numel()), _ptr(d), _ptr(a), _ptr(g), _ptr(far),
-                      _ptr(work), _ptr(loss), _stream(dev))
+                _call("gsr_depth_l1_forward", d.numel(), d, a, g, far, work, loss, _stream(dev))
             else:
-                _call("gsr_depth_l1_masked_forward", C.c_longlong(d.numel()), _ptr(d), _ptr(a), _ptr(g), _ptr(mask),
-                      _ptr(far), _ptr(work), _ptr(loss), _stream(dev))
+                _call("gsr_depth_l1_masked_forward", d.numel(), d, a, g, mask, far, work, loss, _stream(dev))
         if mask is None:
             ctx.save_for_backward(d, a, g, far)
         else:
@@ -230,11 +221,9 @@ class _DepthL1(Function):
             v_d = torch.empty_like(d)
             v_a = torch.empty_like(a)
             if not masks:
-                _call("gsr_depth_l1_backward", C.c_longlong(d.numel()), _ptr(up), _ptr(d), _ptr(a), _ptr(g),
-                      _ptr(far), _ptr(v_d), _ptr(v_a), _stream(dev))
+                _call("gsr_depth_l1_backward", d.numel(), up, d, a, g, far, v_d, v_a, _stream(dev))
             else:
-                _call("gsr_depth_l1_masked_backward", C.c_longlong(d.numel()), _ptr(up), _ptr(d), _ptr(a), _ptr(g),
-                      _ptr(masks[0]), _ptr(far), _ptr(v_d), _ptr(v_a), _stream(dev))
+                _call("gsr_depth_l1_masked_backward", d.numel(), up, d, a, g, masks[0], far, v_d, v_a, _stream(dev))
         return v_d.view(ctx.shapes[0]), v_a.view(ctx.shapes[1]), None, None
 
 
@@ -270,8 +259,7 @@ class _DepthReg(Function):
             scratch = torch.empty((2, H, W), dtype=_f32, device=dev)
             work = torch.empty((DEPTH_REG_WORKSPACE_DOUBLES,), dtype=torch.float64, device=dev)
             loss = torch.empty((), dtype=_f32, device=dev)
-            _call("gsr_depth_reg_forward", C.c_uint(H), C.c_uint(W), _ptr(p), _ptr(m), _ptr(scratch), _ptr(work),
-                  _ptr(loss), _stream(dev))
+            _call("gsr_depth_reg_forward", H, W, p, m, scratch, work, loss, _stream(dev))
         ctx.save_for_backward(p, m, scratch)
         ctx.shape = shape
         return loss
@@ -284,8 +272,7 @@ class _DepthReg(Function):
         up = v_loss.to(_f32).reshape(1).contiguous()
         with torch.cuda.device(dev):
             v_pred = torch.empty_like(p)
-            _call("gsr_depth_reg_backward", C.c_uint(H), C.c_uint(W), _ptr(up), _ptr(p), _ptr(m), _ptr(scratch),
-                  _ptr(v_pred), _stream(dev))
+            _call("gsr_depth_reg_backward", H, W, up, p, m, scratch, v_pred, _stream(dev))
         return v_pred.view(ctx.shape), None
 
 

@@ -8,14 +8,13 @@ phase is a plan (opacities, integer sampling weights, their uint64 prefix sums, 
 over all tensors.  Nothing is read back: how many rows were dead stays in a device tensor that ``info`` reads when
 asked.  fp32 CUDA tensors only; no CPU fallback.
 """
-import ctypes as C
 from dataclasses import dataclass
 from typing import Dict, Optional, Tuple
 
 import torch
 from torch import Tensor
 
-from rasterizer.cuda import _call, _check, _lib, _ptr, _stream
+from rasterizer.cuda import _call, _check, _stream, _typed
 
 from .refine import KIND_COPY, KIND_LOG_SCALES, KIND_MOMENT, MAX_TENSORS, PARAM_NAMES, _RefineTensor
 
@@ -110,14 +109,12 @@ def _phase(params, moments, cfg: MCMCConfig, step: int, seed: int, phase: int, n
                 "dead_index": torch.empty(n, **i32), "draw_source": torch.empty(n if phase == RELOCATE else n_new, **i32),
                 "row_source": torch.empty(n, **i32), "counts": torch.empty(n, **i32),
                 "totals": torch.empty(2, dtype=torch.int64, device=dev)}
-        wbytes = int(_lib().gsr_mcmc_workspace_bytes(C.c_int(n)))
+        wbytes = int(_typed().gsr_mcmc_workspace_bytes(n))
         work = torch.empty(wbytes, dtype=torch.uint8, device=dev)
         scratch = torch.empty(4 * n, dtype=_f32, device=dev)
-        _call("gsr_mcmc_plan", C.c_int(n), C.c_int(n_new if phase == ADD else 0), C.c_int(phase),
-              _ptr(params["opacities"]), C.c_float(cfg.min_opacity), C.c_uint(int(step) & 0xFFFFFFFF),
-              C.c_ulonglong(int(seed) & (2**64 - 1)), _ptr(plan["opac"]), _ptr(plan["prefix"]), _ptr(plan["dead_index"]),
-              _ptr(plan["draw_source"]), _ptr(plan["row_source"]), _ptr(plan["counts"]), _ptr(plan["totals"]),
-              _ptr(work), C.c_size_t(wbytes), _stream(dev))
+        _call("gsr_mcmc_plan", n, n_new if phase == ADD else 0, phase, params["opacities"], cfg.min_opacity,
+              int(step) & 0xFFFFFFFF, int(seed) & (2**64 - 1), plan["opac"], plan["prefix"], plan["dead_index"],
+              plan["draw_source"], plan["row_source"], plan["counts"], plan["totals"], work, wbytes, _stream(dev))
         items = []  # (in, out, width, kind)
         kinds = {"scales": KIND_LOG_SCALES, "opacities": KIND_OPACITIES}
         for k in PARAM_NAMES:
@@ -139,9 +136,8 @@ def _phase(params, moments, cfg: MCMCConfig, step: int, seed: int, phase: int, n
         arr = (_RefineTensor * len(items))()
         for j, (a, b, w, kind) in enumerate(items):
             arr[j] = _RefineTensor(a.data_ptr(), b.data_ptr(), w, kind)
-        _call("gsr_mcmc_apply", C.c_int(n), C.c_int(n_out), _ptr(plan["opac"]), _ptr(params["scales"]),
-              C.c_float(cfg.min_opacity), _ptr(plan["row_source"]), _ptr(plan["draw_source"]), _ptr(plan["counts"]),
-              _ptr(scratch), C.c_int(len(items)), arr, _stream(dev))
+        _call("gsr_mcmc_apply", n, n_out, plan["opac"], params["scales"], cfg.min_opacity, plan["row_source"],
+              plan["draw_source"], plan["counts"], scratch, len(items), arr, _stream(dev))
     info.plans["relocate" if phase == RELOCATE else "add"] = plan
     info.n_out = n_out
     if phase == ADD:
@@ -194,8 +190,8 @@ def relocation(opacities: Tensor, scales: Tensor, ratios: Tensor, min_opacity: f
         raise ValueError("expected opacities [n], scales [n,3], ratios [n]")
     out_o, out_s = torch.empty_like(opacities), torch.empty_like(scales)
     with torch.cuda.device(opacities.device):
-        _call("gsr_mcmc_relocation", C.c_int(n), _ptr(opacities), _ptr(scales), _ptr(ratios), C.c_float(min_opacity),
-              C.c_int(int(raw)), _ptr(out_o), _ptr(out_s), _stream(opacities.device))
+        _call("gsr_mcmc_relocation", n, opacities, scales, ratios, min_opacity, int(raw), out_o, out_s,
+              _stream(opacities.device))
     return out_o, out_s
 
 
@@ -215,9 +211,8 @@ def mcmc_inject_noise_(means: Tensor, log_scales: Tensor, raw_quats: Tensor, log
         if noise.shape != (n, 3):
             raise ValueError("noise must be [N,3]")
     with torch.cuda.device(means.device):
-        _call("gsr_mcmc_noise", C.c_int(n), _ptr(means), _ptr(log_scales), _ptr(raw_quats), _ptr(logits),
-              C.c_float(scaler), C.c_uint(int(step) & 0xFFFFFFFF), C.c_ulonglong(int(seed) & (2**64 - 1)),
-              None if noise is None else _ptr(noise), _stream(means.device))
+        _call("gsr_mcmc_noise", n, means, log_scales, raw_quats, logits, scaler, int(step) & 0xFFFFFFFF,
+              int(seed) & (2**64 - 1), noise, _stream(means.device))
     return means
 
 
@@ -231,10 +226,10 @@ class _MCMCRegularizer(torch.autograd.Function):
         dev = logits.device
         with torch.cuda.device(dev):
             out = torch.empty(3, dtype=torch.float64, device=dev)
-            wbytes = int(_lib().gsr_mcmc_reg_workspace_bytes())
+            wbytes = int(_typed().gsr_mcmc_reg_workspace_bytes())
             work = torch.empty(wbytes, dtype=torch.uint8, device=dev)
-            _call("gsr_mcmc_reg_forward", C.c_int(n), _ptr(logits), _ptr(log_scales), C.c_double(opacity_reg),
-                  C.c_double(scale_reg), _ptr(out), _ptr(work), C.c_size_t(wbytes), _stream(dev))
+            _call("gsr_mcmc_reg_forward", n, logits, log_scales, opacity_reg, scale_reg, out, work, wbytes,
+                  _stream(dev))
         ctx.save_for_backward(logits, log_scales)
         ctx.regs = (float(opacity_reg), float(scale_reg))
         return out[0].clone()
@@ -245,9 +240,8 @@ class _MCMCRegularizer(torch.autograd.Function):
         v = v.to(torch.float64).contiguous()
         v_logits, v_log_scales = torch.empty_like(logits), torch.empty_like(log_scales)
         with torch.cuda.device(logits.device):
-            _call("gsr_mcmc_reg_backward", C.c_int(logits.numel()), _ptr(logits), _ptr(log_scales),
-                  C.c_double(ctx.regs[0]), C.c_double(ctx.regs[1]), _ptr(v), _ptr(v_logits), _ptr(v_log_scales),
-                  _stream(logits.device))
+            _call("gsr_mcmc_reg_backward", logits.numel(), logits, log_scales, ctx.regs[0], ctx.regs[1], v, v_logits,
+                  v_log_scales, _stream(logits.device))
         return v_logits, v_log_scales, None, None
 
 

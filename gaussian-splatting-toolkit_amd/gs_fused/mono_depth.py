@@ -10,19 +10,16 @@ order without atomics (two runs are bit-equal, the local-Pearson gradient over o
 differentiable w.r.t. the predicted depth only, CUDA tensors only.  `mask` follows the other heads (`loss._mask_arg`):
 ``pred * mask`` and ``gt * mask`` are formed inside the kernels, nothing is selected, the means stay over all pixels
 and the cotangent is scaled by the mask."""
-import ctypes as C
-
 import torch
 from torch import Tensor
 from torch.autograd import Function
 
-from rasterizer.cuda import _call, _check, _ptr, _stream
+from rasterizer.cuda import _call, _check, _stream
 
 from .loss import _mask_arg
 
 _f32 = torch.float32
 WORKSPACE_DOUBLES = 2048  # GSR_MONO_DEPTH_WORKSPACE_DOUBLES (include/gsraster.h)
-_NULL = C.c_void_p(None)
 
 
 def _depth_arg(t, name: str) -> Tensor:
@@ -46,10 +43,6 @@ def _pair(pred, gt, mask):
     H, W = int(p.shape[0]), int(p.shape[1])
     m = None if mask is None else _mask_arg(mask, H, W, p)
     return p, g, m, H, W
-
-
-def _mp(mask):
-    return _NULL if mask is None else _ptr(mask)
 
 
 def _upstream(v_loss: Tensor) -> Tensor:
@@ -85,8 +78,7 @@ class _LocalPearson(Function):
         with torch.cuda.device(dev):
             stats = torch.empty((max(n_corr, 1), 5), dtype=torch.float64, device=dev)
             loss = torch.empty((), dtype=_f32, device=dev)
-            _call("gsr_local_pearson_forward", C.c_uint(H), C.c_uint(W), C.c_int(box_p), C.c_int(n_corr), _ptr(p),
-                  _ptr(g), _mp(m), _ptr(rows), _ptr(cols), C.c_int(i64), _ptr(stats), _ptr(loss), _stream(dev))
+            _call("gsr_local_pearson_forward", H, W, box_p, n_corr, p, g, m, rows, cols, i64, stats, loss, _stream(dev))
         saved = (p, g, rows, cols, stats) + (() if m is None else (m,))
         ctx.save_for_backward(*saved)
         ctx.args = (H, W, box_p, n_corr, i64)
@@ -101,9 +93,8 @@ class _LocalPearson(Function):
         up = _upstream(v_loss)
         with torch.cuda.device(dev):
             v_pred = torch.empty_like(p)
-            _call("gsr_local_pearson_backward", C.c_uint(H), C.c_uint(W), C.c_int(box_p), C.c_int(n_corr), _ptr(up),
-                  _ptr(p), _ptr(g), _mp(masks[0] if masks else None), _ptr(rows), _ptr(cols), C.c_int(i64),
-                  _ptr(stats), _ptr(v_pred), _stream(dev))
+            _call("gsr_local_pearson_backward", H, W, box_p, n_corr, up, p, g, masks[0] if masks else None, rows, cols,
+                  i64, stats, v_pred, _stream(dev))
         return v_pred.view(ctx.shape), None, None, None, None, None
 
 
@@ -164,8 +155,7 @@ class _LogDepth(Function):
             ss = _scale_shift_arg(scale, shift, dev)
             work = torch.empty((WORKSPACE_DOUBLES,), dtype=torch.float64, device=dev)
             loss = torch.empty((), dtype=_f32, device=dev)
-            _call("gsr_log_depth_forward", C.c_uint(H), C.c_uint(W), _ptr(p), _ptr(g), _ptr(img), _ptr(ss), _mp(m),
-                  _ptr(work), _ptr(loss), _stream(dev))
+            _call("gsr_log_depth_forward", H, W, p, g, img, ss, m, work, loss, _stream(dev))
         ctx.save_for_backward(*((p, g, img, ss) + (() if m is None else (m,))))
         ctx.shape = shape
         return loss
@@ -178,8 +168,7 @@ class _LogDepth(Function):
         up = _upstream(v_loss)
         with torch.cuda.device(dev):
             v_pred = torch.empty_like(p)
-            _call("gsr_log_depth_backward", C.c_uint(H), C.c_uint(W), _ptr(up), _ptr(p), _ptr(g), _ptr(img), _ptr(ss),
-                  _mp(masks[0] if masks else None), _ptr(v_pred), _stream(dev))
+            _call("gsr_log_depth_backward", H, W, up, p, g, img, ss, masks[0] if masks else None, v_pred, _stream(dev))
         return v_pred.view(ctx.shape), None, None, None, None, None
 
 
@@ -204,7 +193,7 @@ class _TV(Function):
         with torch.cuda.device(dev):
             work = torch.empty((WORKSPACE_DOUBLES,), dtype=torch.float64, device=dev)
             loss = torch.empty((), dtype=_f32, device=dev)
-            _call("gsr_tv_forward", C.c_uint(H), C.c_uint(W), _ptr(p), _mp(m), _ptr(work), _ptr(loss), _stream(dev))
+            _call("gsr_tv_forward", H, W, p, m, work, loss, _stream(dev))
         ctx.save_for_backward(*((p,) + (() if m is None else (m,))))
         ctx.shape = shape
         return loss
@@ -217,8 +206,7 @@ class _TV(Function):
         up = _upstream(v_loss)
         with torch.cuda.device(dev):
             v_pred = torch.empty_like(p)
-            _call("gsr_tv_backward", C.c_uint(H), C.c_uint(W), _ptr(up), _ptr(p), _mp(masks[0] if masks else None),
-                  _ptr(v_pred), _stream(dev))
+            _call("gsr_tv_backward", H, W, up, p, masks[0] if masks else None, v_pred, _stream(dev))
         return v_pred.view(ctx.shape), None
 
 

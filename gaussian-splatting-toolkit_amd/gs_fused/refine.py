@@ -22,7 +22,7 @@ from typing import Dict, Optional, Tuple
 import torch
 from torch import Tensor
 
-from rasterizer.cuda import _call, _check, _lib, _ptr, _stream
+from rasterizer.cuda import _call, _check, _stream, _typed
 
 PARAM_NAMES = ("means", "scales", "quats", "features_dc", "features_rest", "opacities")
 _f32 = torch.float32
@@ -154,16 +154,14 @@ def _compact(params, moments, stats, cfg, step, densify, max_dim, samples, seed,
     c = _Config(cfg.densify_grad_thresh, cfg.densify_size_thresh, cfg.split_screen_size, cfg.cull_alpha_thresh,
                 cfg.cull_scale_thresh, cfg.cull_screen_size, 0.5 * float(max_dim), S, int(densify),
                 int(split_by_screen), int(cull_big), int(cull_by_screen))
-    opt = lambda t: None if t is None else _ptr(t)
     with torch.cuda.device(dev):
         flags = torch.empty(n, dtype=torch.uint8, device=dev)
         offsets = torch.empty((n, 4), dtype=torch.int32, device=dev)
         counts = torch.empty(4, dtype=torch.int32, device=dev)
-        wbytes = int(_lib().gsr_refine_workspace_bytes(C.c_int(n)))
+        wbytes = int(_typed().gsr_refine_workspace_bytes(n))
         work = torch.empty(wbytes, dtype=torch.uint8, device=dev)
-        _call("gsr_refine_plan", C.c_int(n), _ptr(params["scales"]), _ptr(params["opacities"]), opt(gn), opt(vc),
-              opt(m2), C.byref(c), _ptr(flags), _ptr(offsets), _ptr(counts), _ptr(work), C.c_size_t(wbytes),
-              _stream(dev))
+        _call("gsr_refine_plan", n, params["scales"], params["opacities"], gn, vc, m2, C.byref(c), flags, offsets,
+              counts, work, wbytes, _stream(dev))
         k0, ks, kd, nsplit = (int(v) for v in counts.tolist())  # the one host read-back
         n_out = k0 + S * ks + kd
         info.update(n_out=n_out, kept=k0, split=ks, dup=kd, split_sources=nsplit)
@@ -200,9 +198,8 @@ def _compact(params, moments, stats, cfg, step, densify, max_dim, samples, seed,
             arr = (_RefineTensor * len(chunk))()
             for j, (a, b, w, kind) in enumerate(chunk):
                 arr[j] = _RefineTensor(a.data_ptr(), b.data_ptr(), w, kind)
-            _call("gsr_refine_apply", C.c_int(n), C.c_int(S), _ptr(flags), _ptr(offsets), _ptr(counts),
-                  _ptr(params["scales"]), _ptr(params["quats"]), opt(samples), C.c_ulonglong(int(seed) & (2**64 - 1)),
-                  C.c_int(len(chunk)), arr, _stream(dev))
+            _call("gsr_refine_apply", n, S, flags, offsets, counts, params["scales"], params["quats"], samples,
+                  int(seed) & (2**64 - 1), len(chunk), arr, _stream(dev))
     return new_params, new_moments
 
 

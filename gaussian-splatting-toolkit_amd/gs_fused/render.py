@@ -33,7 +33,7 @@ from torch import Tensor
 from torch.autograd import Function
 
 import rasterizer.cuda as _C
-from rasterizer.cuda import _call, _ptr, _stream
+from rasterizer.cuda import _call, _stream
 
 _f32, _i32 = torch.float32, torch.int32
 BLOCK = 16
@@ -102,9 +102,9 @@ def _workspace_bytes(n, capacity, tb):
     key = (n, capacity, tb[0], tb[1])
     v = _ws_bytes_cache.get(key)
     if v is None:
-        lib = _C._lib()
-        v = (int(lib.gsr_depth_order_workspace_bytes(C.c_int(n), C.c_int(1))),
-             int(lib.gsr_bin_sorted_workspace_bytes(C.c_int(n), C.c_int(capacity), C.c_int(tb[0]), C.c_int(tb[1]))),
+        lib = _C._typed()
+        v = (int(lib.gsr_depth_order_workspace_bytes(n, 1)),
+             int(lib.gsr_bin_sorted_workspace_bytes(n, capacity, tb[0], tb[1])),
              int(lib.gsr_reach_record_bytes()),
              not _C.lists_need_counts(n, capacity, tb, device_sized=True))
         if len(_ws_bytes_cache) > 64:
@@ -216,7 +216,7 @@ class _Render(Function):
             if crop is None:
                 _call("gsr_view_forward", C.byref(desc), _stream(dev))
             else:  # the crop box rides next to the descriptor (whose layout is unchanged)
-                _call("gsr_view_forward_crop", C.byref(desc), _ptr(crop), _stream(dev))
+                _call("gsr_view_forward_crop", C.byref(desc), crop, _stream(dev))
             del seg
             ctx.det = None
             if det:

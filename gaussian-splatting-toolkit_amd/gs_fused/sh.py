@@ -12,13 +12,12 @@ SH kernels themselves.  `spherical_harmonics_split(n, viewdirs, features_dc,
 features_rest)` returns the same colours and writes the two gradients in place
 (`gsr_sh_forward_split` / `gsr_sh_backward_split`, include/gsraster.h).
 """
-import ctypes as C
 
 import torch
 from torch import Tensor
 from torch.autograd import Function
 
-from rasterizer.cuda import _call, _check, _ptr, _stream
+from rasterizer.cuda import _call, _check, _stream
 from rasterizer.sh import deg_from_sh, num_sh_bases, spherical_harmonics
 
 _f32 = torch.float32
@@ -35,9 +34,8 @@ class _SplitSH(Function):
         dev = dc.device
         with torch.cuda.device(dev):
             colors = torch.empty((n, 3), dtype=_f32, device=dev)
-            _call("gsr_sh_forward_split", C.c_uint(n), C.c_uint(degree), C.c_uint(degrees_to_use),
-                  _ptr(viewdirs), _ptr(dc), _ptr(rest), _ptr(colors), C.c_float(shift),
-                  C.c_int(1 if clamp_zero else 0), _stream(dev))
+            _call("gsr_sh_forward_split", n, degree, degrees_to_use, viewdirs, dc, rest, colors, shift,
+                  1 if clamp_zero else 0, _stream(dev))
         ctx.degree, ctx.degrees_to_use = degree, degrees_to_use
         ctx.shapes = (dc.shape, rest.shape)
         ctx.clamped = bool(clamp_zero)
@@ -53,9 +51,8 @@ class _SplitSH(Function):
         with torch.cuda.device(dev):
             v_dc = torch.empty(ctx.shapes[0], dtype=_f32, device=dev)
             v_rest = torch.empty(ctx.shapes[1], dtype=_f32, device=dev)
-            _call("gsr_sh_backward_split", C.c_uint(n), C.c_uint(ctx.degree), C.c_uint(ctx.degrees_to_use),
-                  _ptr(viewdirs), _ptr(v_colors), _ptr(colors) if ctx.clamped else None, _ptr(v_dc),
-                  _ptr(v_rest), _stream(dev))
+            _call("gsr_sh_backward_split", n, ctx.degree, ctx.degrees_to_use, viewdirs, v_colors,
+                  colors if ctx.clamped else None, v_dc, v_rest, _stream(dev))
         return None, None, v_dc, v_rest, None, None
 
 
@@ -110,9 +107,8 @@ def sh_backward_views(degree: int, degrees_to_use: int, means3d: Tensor, camera_
             v_rest = torch.empty((n, K - 1, 3), dtype=_f32, device=dev)
         else:
             v_coeffs = torch.empty((n, K, 3), dtype=_f32, device=dev)
-        _call("gsr_sh_backward_views", C.c_uint(n), C.c_uint(degree), C.c_uint(degrees_to_use), C.c_uint(V),
-              _ptr(means3d), _ptr(camera_positions), C.c_size_t(camera_positions.stride(0) if V > 1 else 3),
-              _ptr(v_colors), C.c_size_t(v_colors.stride(0) if V > 1 else 3 * n), C.c_float(scale),
-              _ptr(v_dc) if split else None, _ptr(v_rest) if split and K > 1 else None,
-              _ptr(v_coeffs) if not split else None, _stream(dev))
+        _call("gsr_sh_backward_views", n, degree, degrees_to_use, V, means3d, camera_positions,
+              camera_positions.stride(0) if V > 1 else 3, v_colors, v_colors.stride(0) if V > 1 else 3 * n, scale,
+              v_dc if split else None, v_rest if split and K > 1 else None, v_coeffs if not split else None,
+              _stream(dev))
     return (v_dc, v_rest) if split else v_coeffs

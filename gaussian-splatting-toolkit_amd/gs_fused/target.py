@@ -4,14 +4,12 @@ resizes and composites it every step; here the images stay uint8 (3-4 B per pixe
 (csrc/target.hip, `gsr_target_from_u8` / `gsr_plane_from_int`; the rule is stated in include/gsraster.h) forms the
 step's target from them.  torch for memory and streams only; no CPU path; nothing is differentiated.
 """
-import ctypes as C
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
 
-from rasterizer.cuda import _on, _stream
-from rasterizer.cuda._backend import lib as _lib
+from rasterizer.cuda import _call, _on, _stream
 
 _f32, _u8 = torch.float32, torch.uint8
 _u16 = getattr(torch, "uint16", None)
@@ -52,12 +50,6 @@ def _out(out: Optional[Tensor], shape: Tuple[int, ...], dev) -> Tensor:
     return out
 
 
-def _call(name: str, *args) -> None:
-    rc = getattr(_lib(), name)(*args)
-    if rc != 0:
-        raise RuntimeError(f"{name} failed ({rc}): {_lib().gsr_last_error().decode()}")
-
-
 def target_from_u8(image_u8: Tensor, background: Optional[Tensor], out_hw: Sequence[int],
                    out: Optional[Tensor] = None) -> Tensor:
     """uint8 [H,W,C], C in (3, 4) -> float32 [h,w,3]: `u8 / 255`, bilinear resize to `out_hw` = (h, w) (no
@@ -83,9 +75,7 @@ def target_from_u8(image_u8: Tensor, background: Optional[Tensor], out_hw: Seque
     h, w = _out_hw(out_hw, H, W)
     with _on(dev):
         out = _out(out, (h, w, 3), dev)
-        _call("gsr_target_from_u8", C.c_void_p(img.data_ptr()), C.c_int(H), C.c_int(W), C.c_int(Cn),
-              C.c_void_p(None if background is None else background.data_ptr()), C.c_int(h), C.c_int(w),
-              C.c_void_p(out.data_ptr()), _stream(dev))
+        _call("gsr_target_from_u8", img, H, W, Cn, background, h, w, out, _stream(dev))
     return out
 
 
@@ -102,8 +92,7 @@ def plane_from_int(plane: Tensor, unit: float, out_hw: Sequence[int], out: Optio
     dev = p.device
     with _on(dev):
         out = _out(out, (h, w), dev)
-        _call("gsr_plane_from_int", C.c_void_p(p.data_ptr()), C.c_int(size), C.c_int(H), C.c_int(W),
-              C.c_float(float(unit)), C.c_int(h), C.c_int(w), C.c_void_p(out.data_ptr()), _stream(dev))
+        _call("gsr_plane_from_int", p, size, H, W, float(unit), h, w, out, _stream(dev))
     return out
 
 

@@ -4,14 +4,12 @@ as `Average Error`) computes, one BVH query per point.  The rule is stated in in
 4.7); HIP kernels behind `gsr_mesh_bvh_build` / `gsr_mesh_distance_*` (csrc/mesh_distance.hip); torch for memory and
 streams only; no CPU path.
 """
-import ctypes as C
 from typing import Dict, Optional
 
 import torch
 from torch import Tensor
 
-from rasterizer.cuda import _call, _check, _on, _stream
-from rasterizer.cuda._backend import lib as _lib
+from rasterizer.cuda import _call, _check, _on, _stream, _typed
 
 _f32, _i32 = torch.float32, torch.int32
 GSR_ERANGE = -4
@@ -20,12 +18,8 @@ BYTES_TREE, BYTES_BUILD, BYTES_QUERY, BYTES_STATS = range(4)
 STAT_NAMES = ("count", "invalid", "mean", "rms", "max", "within_threshold", "sum", "sum_squares")
 
 
-def _ptr(t: Optional[Tensor]) -> C.c_void_p:
-    return C.c_void_p(None if t is None or t.numel() == 0 else t.data_ptr())
-
-
 def _bytes(what: int, num_faces: int, num_points: int) -> int:
-    n = _lib().gsr_mesh_distance_workspace_bytes(C.c_int(what), C.c_int(num_faces), C.c_int(num_points))
+    n = _typed().gsr_mesh_distance_workspace_bytes(what, num_faces, num_points)
     if n == 0:
         raise ValueError(f"{num_faces} faces / {num_points} points: too large, or a size query failed (no device?)")
     return n
@@ -64,10 +58,9 @@ class MeshDistance:
             self._tree = _space(_tree, _bytes(BYTES_TREE, F, 0), dev)
             ws = _space(_workspace, _bytes(BYTES_BUILD, F, 0), dev)
             state = torch.empty(4, dtype=_i32, device=dev)
-            L = _lib()
-            rc = L.gsr_mesh_bvh_build(C.c_int(V), C.c_int(F), _ptr(vertices), _ptr(triangles), _ptr(self._tree),
-                                      C.c_size_t(self._tree.numel()), _ptr(ws), C.c_size_t(ws.numel()),
-                                      C.c_void_p(state.data_ptr()), _stream(dev))
+            L = _typed()
+            rc = L.gsr_mesh_bvh_build(V, F, None if vertices.numel() == 0 else vertices, triangles, self._tree,
+                                      self._tree.numel(), ws, ws.numel(), state, _stream(dev))
             if rc == GSR_ERANGE:
                 raise ValueError(L.gsr_last_error().decode())
             if rc != 0:
@@ -96,9 +89,8 @@ class MeshDistance:
                 closest = torch.empty((n, 3), dtype=_f32, device=dev) if return_closest else None
             if n:
                 ws = None if exhaustive else _space(_workspace, _bytes(BYTES_QUERY, 0, n), dev)
-                _call("gsr_mesh_distance_query", C.c_int(self.num_faces), _ptr(self._tree),
-                      C.c_size_t(self._tree.numel()), C.c_int(n), _ptr(points), C.c_int(EXHAUSTIVE if exhaustive else 0),
-                      _ptr(ws), C.c_size_t(0 if ws is None else ws.numel()), _ptr(dist), _ptr(face), _ptr(closest),
+                _call("gsr_mesh_distance_query", self.num_faces, self._tree, self._tree.numel(), n, points,
+                      EXHAUSTIVE if exhaustive else 0, ws, 0 if ws is None else ws.numel(), dist, face, closest,
                       _stream(dev))
         return (dist, face, closest) if return_closest else (dist, face)
 
@@ -121,8 +113,9 @@ def distance_stats(distance: Tensor, threshold: Optional[float] = None,
     with _on(dev):
         ws = _space(_workspace, _bytes(BYTES_STATS, 0, n), dev) if n else None
         out = torch.empty(8, dtype=torch.float64, device=dev)
-        _call("gsr_mesh_distance_stats", C.c_int(n), _ptr(distance), C.c_float(-1.0 if threshold is None else threshold),
-              _ptr(ws), C.c_size_t(0 if ws is None else ws.numel()), C.c_void_p(out.data_ptr()), _stream(dev))
+        _call("gsr_mesh_distance_stats", n, None if distance.numel() == 0 else distance,
+              -1.0 if threshold is None else threshold, ws,
+              0 if ws is None else ws.numel(), out, _stream(dev))
         row = out.cpu().tolist()
     res = dict(zip(STAT_NAMES, row))
     for k in ("count", "invalid", "within_threshold"):

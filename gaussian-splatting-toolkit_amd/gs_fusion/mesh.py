@@ -4,14 +4,12 @@
 (DESIGN.md section 4.6); HIP kernels behind `gsr_mesh_*` (csrc/mesh_clean.hip); torch for memory and streams only; no
 CPU fallback.
 """
-import ctypes as C
 from typing import Dict, Optional, Tuple
 
 import torch
 from torch import Tensor
 
-from rasterizer.cuda import _call, _check, _on, _stream
-from rasterizer.cuda._backend import lib as _lib
+from rasterizer.cuda import _call, _check, _on, _stream, _typed
 
 _f32, _i32 = torch.float32, torch.int32
 GSR_ERANGE = -4
@@ -19,8 +17,9 @@ GSR_ERANGE = -4
 ST_BAD, ST_NULL, ST_DUP, ST_COMPONENTS, ST_COMPONENTS_KEPT, ST_FACES_KEPT, ST_VERTICES_KEPT, ST_UNCONVERGED = range(8)
 
 
-def _opt(t: Optional[Tensor]) -> C.c_void_p:
-    return C.c_void_p(None if t is None or t.numel() == 0 else t.data_ptr())
+def _opt(t: Optional[Tensor]) -> Optional[Tensor]:
+    """(an absent or empty tensor goes to the library as NULL)"""
+    return None if t is None or t.numel() == 0 else t
 
 
 def _check_mesh(triangles, num_vertices, vertices, vertex_colors) -> int:
@@ -46,7 +45,7 @@ def _label(triangles: Tensor, V: int, vertices: Optional[Tensor], min_faces: int
     """The label call and its one read-back -> (state as a list of 8 ints, workspace).  `workspace`: a uint8 tensor
     of at least the queried size to use instead of a fresh one (the tests hand in a pre-filled one)."""
     dev, F = triangles.device, triangles.size(0)
-    n = _lib().gsr_mesh_clean_workspace_bytes(C.c_int(V), C.c_int(F)) if F else 0
+    n = _typed().gsr_mesh_clean_workspace_bytes(V, F) if F else 0
     if F and n == 0:
         raise ValueError(f"mesh of {V} vertices and {F} faces: too large, or the workspace size query failed (no device?)")
     if workspace is None:
@@ -54,10 +53,9 @@ def _label(triangles: Tensor, V: int, vertices: Optional[Tensor], min_faces: int
     elif workspace.numel() < n or workspace.device != dev or workspace.dtype != torch.uint8:
         raise RuntimeError(f"workspace must hold {n} bytes on {dev}")
     state = torch.empty(8, dtype=_i32, device=dev)
-    L = _lib()
-    rc = L.gsr_mesh_label(C.c_int(V), C.c_int(F), _opt(vertices), _opt(triangles), C.c_int(min_faces),
-                          C.c_void_p(state.data_ptr()), _opt(workspace), C.c_size_t(workspace.numel()), _opt(labels),
-                          _opt(sizes), _stream(dev))
+    L = _typed()
+    rc = L.gsr_mesh_label(V, F, _opt(vertices), _opt(triangles), min_faces, state, _opt(workspace), workspace.numel(),
+                          _opt(labels), _opt(sizes), _stream(dev))
     if rc == GSR_ERANGE:
         raise ValueError(L.gsr_last_error().decode())
     if rc != 0:
@@ -108,9 +106,8 @@ def _clean_mesh(vertices, triangles, vertex_colors, min_component_faces, return_
         out_c = None if vertex_colors is None else torch.empty((nv, ncol), dtype=_f32, device=dev)
         out_t = torch.empty((nf, 3), dtype=_i32, device=dev)
         if nf:
-            _call("gsr_mesh_emit", C.c_int(V), C.c_int(F), C.c_int(ncol), _opt(vertices), _opt(vertex_colors),
-                  _opt(triangles), _opt(ws), C.c_size_t(ws.numel()), C.c_int(nv), C.c_int(nf), _opt(out_v), _opt(out_c),
-                  _opt(out_t), _stream(dev))
+            _call("gsr_mesh_emit", V, F, ncol, _opt(vertices), _opt(vertex_colors), _opt(triangles), _opt(ws),
+                  ws.numel(), nv, nf, _opt(out_v), _opt(out_c), _opt(out_t), _stream(dev))
     if not return_info:
         return out_v, out_c, out_t
     info: Dict[str, int] = {

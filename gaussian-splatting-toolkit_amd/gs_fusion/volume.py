@@ -12,8 +12,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from rasterizer.cuda import _call, _check, _on, _stream
-from rasterizer.cuda._backend import lib as _lib
+from rasterizer.cuda import _call, _check, _on, _stream, _typed
 
 _f32 = torch.float32
 # rows of the `state` tensor (csrc/tsdf.hip)
@@ -66,9 +65,9 @@ class TSDFVolume:
             self.device = torch.device("cuda", torch.cuda.current_device())
         Bx, By, Bz = self.blocks
         self.num_blocks = Bx * By * Bz
-        L = _lib()
-        ws_alloc = L.gsr_tsdf_allocate_workspace_bytes(C.c_int(self.num_blocks))
-        if ws_alloc == 0 or L.gsr_tsdf_extract_mesh_workspace_bytes(C.c_int(self.num_blocks), C.c_int(self.capacity)) == 0:
+        L = _typed()
+        ws_alloc = L.gsr_tsdf_allocate_workspace_bytes(self.num_blocks)
+        if ws_alloc == 0 or L.gsr_tsdf_extract_mesh_workspace_bytes(self.num_blocks, self.capacity) == 0:
             raise ValueError("too many blocks or too large a pool")
         dev = self.device
         with _on(dev):
@@ -135,13 +134,11 @@ class TSDFVolume:
 
     # (the two halves of a view, apart: tools/fusion_bench.py times them separately)
     def _touch_allocate(self, vol: _Volume, view: _View, s) -> None:
-        _call("gsr_tsdf_touch", C.byref(vol), C.byref(view), C.c_void_p(self._flags.data_ptr()), s)
-        _call("gsr_tsdf_allocate", C.byref(vol), C.c_void_p(self._flags.data_ptr()),
-              C.c_void_p(self._list.data_ptr()), C.c_void_p(self._ws_alloc.data_ptr()),
-              C.c_size_t(self._ws_alloc.numel()), s)
+        _call("gsr_tsdf_touch", C.byref(vol), C.byref(view), self._flags, s)
+        _call("gsr_tsdf_allocate", C.byref(vol), self._flags, self._list, self._ws_alloc, self._ws_alloc.numel(), s)
 
     def _integrate_listed(self, vol: _Volume, view: _View, s) -> None:
-        _call("gsr_tsdf_integrate", C.byref(vol), C.byref(view), C.c_void_p(self._list.data_ptr()), s)
+        _call("gsr_tsdf_integrate", C.byref(vol), C.byref(view), self._list, s)
 
     # ---- extraction -------------------------------------------------------------------------------------------------
     def _read_state(self) -> np.ndarray:
@@ -158,15 +155,13 @@ class TSDFVolume:
         vol = self._desc()
         with _on(dev):
             s = _stream(dev)
-            n = _lib().gsr_tsdf_extract_points_workspace_bytes(C.c_int(self.num_blocks))
+            n = _typed().gsr_tsdf_extract_points_workspace_bytes(self.num_blocks)
             ws = torch.empty(n, dtype=torch.uint8, device=dev)
-            _call("gsr_tsdf_extract_points_count", C.byref(vol), C.c_void_p(ws.data_ptr()), C.c_size_t(n), s)
+            _call("gsr_tsdf_extract_points_count", C.byref(vol), ws, n, s)
             m = int(self._read_state()[ST_POINTS])
             points, colors, normals = (torch.empty((m, 3), dtype=_f32, device=dev) for _ in range(3))
             axis = torch.empty(m, dtype=torch.int32, device=dev)
-            _call("gsr_tsdf_extract_points_emit", C.byref(vol), C.c_void_p(ws.data_ptr()), C.c_size_t(n), C.c_int(m),
-                  C.c_void_p(points.data_ptr()), C.c_void_p(colors.data_ptr()), C.c_void_p(normals.data_ptr()),
-                  C.c_void_p(axis.data_ptr()), s)
+            _call("gsr_tsdf_extract_points_emit", C.byref(vol), ws, n, m, points, colors, normals, axis, s)
         return (points, colors, normals, axis) if return_axis else (points, colors, normals)
 
     def extract_mesh(self) -> Tuple[Tensor, Tensor, Tensor]:
@@ -175,16 +170,14 @@ class TSDFVolume:
         vol = self._desc()
         with _on(dev):
             s = _stream(dev)
-            n = _lib().gsr_tsdf_extract_mesh_workspace_bytes(C.c_int(self.num_blocks), C.c_int(self.capacity))
+            n = _typed().gsr_tsdf_extract_mesh_workspace_bytes(self.num_blocks, self.capacity)
             ws = torch.empty(n, dtype=torch.uint8, device=dev)
-            _call("gsr_tsdf_extract_mesh_count", C.byref(vol), C.c_void_p(ws.data_ptr()), C.c_size_t(n), s)
+            _call("gsr_tsdf_extract_mesh_count", C.byref(vol), ws, n, s)
             st = self._read_state()
             nv, nt = int(st[ST_VERTICES]), int(st[ST_TRIANGLES])
             vertices, vcolors = (torch.empty((nv, 3), dtype=_f32, device=dev) for _ in range(2))
             triangles = torch.empty((nt, 3), dtype=torch.int32, device=dev)
-            _call("gsr_tsdf_extract_mesh_emit", C.byref(vol), C.c_void_p(ws.data_ptr()), C.c_size_t(n), C.c_int(nv),
-                  C.c_int(nt), C.c_void_p(vertices.data_ptr()), C.c_void_p(vcolors.data_ptr()),
-                  C.c_void_p(triangles.data_ptr()), s)
+            _call("gsr_tsdf_extract_mesh_emit", C.byref(vol), ws, n, nv, nt, vertices, vcolors, triangles, s)
         return vertices, vcolors, triangles
 
     # ---- state ------------------------------------------------------------------------------------------------------

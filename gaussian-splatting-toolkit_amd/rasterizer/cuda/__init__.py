@@ -20,7 +20,7 @@ import torch
 from torch import Tensor
 
 from . import _tuning
-from ._backend import lib as _lib
+from ._backend import lib as _lib, typed as _typed
 
 _f32, _i32, _i64 = torch.float32, torch.int32, torch.int64
 
@@ -39,6 +39,7 @@ def _check(t: Tensor, name: str, dtype=None) -> Tensor:
 
 
 def _ptr(t: Tensor) -> C.c_void_p:
+    """(for callers of the raw handle `_backend.lib()`, which marshal for themselves; `_call` takes the tensor)"""
     return C.c_void_p(t.data_ptr())
 
 
@@ -75,12 +76,16 @@ def _stream(device) -> C.c_void_p:
 
 
 def _call(fn_name: str, *args) -> None:
-    rc = getattr(_lib(), fn_name)(*args)
+    """One native entry through the typed handle (`_backend.typed`): `args` are the header's parameters as plain
+    values -- a tensor, None or an address for a pointer, Python numbers for the scalars; values already wrapped in
+    the parameter's own ctypes type pass as they are.  A wrong count or kind raises before the library is entered."""
+    rc = getattr(_typed(), fn_name)(*args)
     if rc != 0:
         raise RuntimeError(f"{fn_name} failed ({rc}): {_lib().gsr_last_error().decode()}")
 
 
 def _cf(v) -> C.c_float:
+    """(as `_ptr`: for callers of the raw handle)"""
     return C.c_float(float(v))
 
 
@@ -107,7 +112,6 @@ def project_gaussians_forward(
             or (precomp and cov3d_precomp.numel() != 6 * n):
         raise RuntimeError("means3d/scales/quats do not match num_points")
     dev = means3d.device
-    _opt0 = lambda t: None if t is None else _ptr(t)
     with _on(dev):
         # seven outputs, seven allocations (the caching allocator hands each out in ~1 us): in round 4 they were carved
         # out of ONE allocation, which made them views sharing a storage and a version counter (a caller's
@@ -117,13 +121,9 @@ def project_gaussians_forward(
         xys, depths, conics, compensation = e((n, 2)), e((n,)), e((n, 3)), e((n,))
         radii, num_tiles_hit = e((n,), _i32), e((n,), _i32)
         cov3d = cov3d_precomp if precomp else e((n, 6))
-        _call(
-            "gsr_project_forward", C.c_int(n), _ptr(means3d), _opt0(scales), _cf(glob_scale),
-            _opt0(quats), _ptr(viewmat), _ptr(projmat), _cf(fx), _cf(fy), _cf(cx), _cf(cy),
-            C.c_uint(img_height), C.c_uint(img_width), C.c_uint(block_width), _cf(clip_thresh),
-            _ptr(cov3d), _ptr(xys), _ptr(depths), _ptr(radii), _ptr(conics), _ptr(compensation),
-            _ptr(num_tiles_hit), _stream(dev),
-        )
+        _call("gsr_project_forward", n, means3d, scales, glob_scale, quats, viewmat, projmat, fx, fy, cx, cy,
+              img_height, img_width, block_width, clip_thresh, cov3d, xys, depths, radii, conics, compensation,
+              num_tiles_hit, _stream(dev))
     return cov3d, xys, depths, radii, conics, compensation, num_tiles_hit
 
 
@@ -153,20 +153,14 @@ def project_gaussians_backward(
         for t, nm in ((v_xy, "v_xy"), (v_depth, "v_depth"), (v_conic, "v_conic"),
                       (v_compensation, "v_compensation"))
     )
-    _opt = lambda t: None if t is None else _ptr(t)
     with _on(dev):
         e = lambda shape: torch.empty(shape, dtype=_f32, device=dev)  # noqa: E731
         v_cov2d, v_cov3d, v_mean3d = e((n, 3)), e((n, 6)), e((n, 3))
         v_scale = None if precomp else e((n, 3))
         v_quat = None if precomp else e((n, 4))
-        _call(
-            "gsr_project_backward", C.c_int(n), _ptr(means3d), _opt(scales), _cf(glob_scale),
-            _opt(quats), _ptr(viewmat), _ptr(projmat), _cf(fx), _cf(fy), _cf(cx), _cf(cy),
-            C.c_uint(img_height), C.c_uint(img_width), _ptr(cov3d), _ptr(radii), _ptr(conics),
-            _ptr(compensation), _opt(v_xy), _opt(v_depth), _opt(v_conic), _opt(v_compensation),
-            _ptr(v_cov2d), _ptr(v_cov3d), _ptr(v_mean3d), _opt(v_scale), _opt(v_quat),
-            _stream(dev),
-        )
+        _call("gsr_project_backward", n, means3d, scales, glob_scale, quats, viewmat, projmat, fx, fy, cx, cy,
+              img_height, img_width, cov3d, radii, conics, compensation, v_xy, v_depth, v_conic, v_compensation,
+              v_cov2d, v_cov3d, v_mean3d, v_scale, v_quat, _stream(dev))
     return v_cov2d, v_cov3d, v_mean3d, v_scale, v_quat
 
 
@@ -192,13 +186,9 @@ def project_gaussians_forward_aa(
         xys, depths, conics, compensation, cov3d = e((n, 2)), e((n,)), e((n, 3)), e((n,)), e((n, 6))
         radii, num_tiles_hit = e((n,), _i32), e((n,), _i32)
         opacities_aa = e(tuple(opacities.shape))
-        _call(
-            "gsr_project_forward_aa", C.c_int(n), _ptr(means3d), _ptr(scales), _cf(glob_scale),
-            _ptr(quats), _ptr(viewmat), _ptr(projmat), _cf(fx), _cf(fy), _cf(cx), _cf(cy),
-            C.c_uint(img_height), C.c_uint(img_width), C.c_uint(block_width), _cf(clip_thresh), _ptr(opacities),
-            _ptr(cov3d), _ptr(xys), _ptr(depths), _ptr(radii), _ptr(conics), _ptr(compensation),
-            _ptr(num_tiles_hit), _ptr(opacities_aa), _stream(dev),
-        )
+        _call("gsr_project_forward_aa", n, means3d, scales, glob_scale, quats, viewmat, projmat, fx, fy, cx, cy,
+              img_height, img_width, block_width, clip_thresh, opacities, cov3d, xys, depths, radii, conics,
+              compensation, num_tiles_hit, opacities_aa, _stream(dev))
     return cov3d, xys, depths, radii, conics, compensation, num_tiles_hit, opacities_aa
 
 
@@ -235,14 +225,9 @@ def project_gaussians_forward_crop(
         xys, depths, conics, compensation, cov3d = e((n, 2)), e((n,)), e((n, 3)), e((n,)), e((n, 6))
         radii, num_tiles_hit = e((n,), _i32), e((n,), _i32)
         opacities_aa = None if opacities is None else e(tuple(opacities.shape))
-        _call(
-            "gsr_project_forward_crop", C.c_int(n), _ptr(means3d), _ptr(scales), _cf(glob_scale),
-            _ptr(quats), _ptr(viewmat), _ptr(projmat), _cf(fx), _cf(fy), _cf(cx), _cf(cy),
-            C.c_uint(img_height), C.c_uint(img_width), C.c_uint(block_width), _cf(clip_thresh), _ptr(crop),
-            None if opacities is None else _ptr(opacities), _ptr(cov3d), _ptr(xys), _ptr(depths), _ptr(radii),
-            _ptr(conics), _ptr(compensation), _ptr(num_tiles_hit),
-            None if opacities_aa is None else _ptr(opacities_aa), _stream(dev),
-        )
+        _call("gsr_project_forward_crop", n, means3d, scales, glob_scale, quats, viewmat, projmat, fx, fy, cx, cy,
+              img_height, img_width, block_width, clip_thresh, crop, opacities, cov3d, xys, depths, radii, conics,
+              compensation, num_tiles_hit, opacities_aa, _stream(dev))
     return cov3d, xys, depths, radii, conics, compensation, num_tiles_hit, opacities_aa
 
 
@@ -258,8 +243,7 @@ def crop_mask(means3d: Tensor, crop: Tensor, want_count: bool = True) -> Tuple[T
     with _on(dev):
         mask = torch.empty((n,), dtype=torch.uint8, device=dev)
         count = torch.empty((1,), dtype=_i32, device=dev) if want_count else None
-        _call("gsr_crop_mask", C.c_int(n), _ptr(means3d), _ptr(crop), _ptr(mask),
-              None if count is None else _ptr(count), _stream(dev))
+        _call("gsr_crop_mask", n, means3d, crop, mask, count, _stream(dev))
     return mask, count
 
 
@@ -291,7 +275,6 @@ def project_gaussians_backward_aa(
         for t, nm in ((v_xy, "v_xy"), (v_depth, "v_depth"), (v_conic, "v_conic"),
                       (v_compensation, "v_compensation"))
     )
-    _opt = lambda t: None if t is None else _ptr(t)
     with _on(dev):
         e = lambda shape: torch.empty(shape, dtype=_f32, device=dev)  # noqa: E731
         if v_opacities_aa is None:
@@ -306,14 +289,10 @@ def project_gaussians_backward_aa(
         v_cov2d, v_cov3d, v_mean3d, v_scale, v_quat = e((n, 3)), e((n, 6)), e((n, 3)), e((n, 3)), e((n, 4))
         v_opacities = v_opacities_aa if in_place else e(tuple(opacities.shape))
         v_comp_out = e((n,)) if want_v_compensation else None
-        _call(
-            "gsr_project_backward_aa", C.c_int(n), _ptr(means3d), _ptr(scales), _cf(glob_scale),
-            _ptr(quats), _ptr(viewmat), _ptr(projmat), _cf(fx), _cf(fy), _cf(cx), _cf(cy),
-            C.c_uint(img_height), C.c_uint(img_width), _ptr(cov3d), _ptr(radii), _ptr(conics),
-            _ptr(compensation), _ptr(opacities), _opt(v_xy), _opt(v_depth), _opt(v_conic), _opt(v_compensation),
-            _ptr(v_opacities_aa), _ptr(v_cov2d), _ptr(v_cov3d), _ptr(v_mean3d), _ptr(v_scale), _ptr(v_quat),
-            _ptr(v_opacities), _opt(v_comp_out), _stream(dev),
-        )
+        _call("gsr_project_backward_aa", n, means3d, scales, glob_scale, quats, viewmat, projmat, fx, fy, cx, cy,
+              img_height, img_width, cov3d, radii, conics, compensation, opacities, v_xy, v_depth, v_conic,
+              v_compensation, v_opacities_aa, v_cov2d, v_cov3d, v_mean3d, v_scale, v_quat, v_opacities, v_comp_out,
+              _stream(dev))
     return v_cov2d, v_cov3d, v_mean3d, v_scale, v_quat, v_opacities, v_comp_out
 
 
@@ -351,18 +330,13 @@ def project_gaussians_backward_pose(
             if t.numel() != width * n:
                 raise RuntimeError(f"{nm} does not match num_points")
         cots.append(t)
-    _opt = lambda t: None if t is None else _ptr(t)
     with _on(dev):
-        nbytes = int(_lib().gsr_project_backward_pose_workspace(C.c_int(n)))
+        nbytes = int(_typed().gsr_project_backward_pose_workspace(n))
         workspace = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=dev)
         v_viewmat = torch.empty((3, 4), dtype=_f32, device=dev)
         v_projmat = torch.empty((4, 4), dtype=_f32, device=dev)
-        _call(
-            "gsr_project_backward_pose", C.c_int(n), _ptr(means3d), _ptr(viewmat), _ptr(projmat), _cf(fx), _cf(fy),
-            C.c_uint(img_height), C.c_uint(img_width), _ptr(cov3d), _ptr(radii), _ptr(conics), _ptr(compensation),
-            *(_opt(t) for t in cots), _ptr(workspace), C.c_size_t(nbytes), _ptr(v_viewmat), _ptr(v_projmat),
-            _stream(dev),
-        )
+        _call("gsr_project_backward_pose", n, means3d, viewmat, projmat, fx, fy, img_height, img_width, cov3d, radii,
+              conics, compensation, *cots, workspace, nbytes, v_viewmat, v_projmat, _stream(dev))
     return v_viewmat, v_projmat
 
 
@@ -382,8 +356,7 @@ def compute_sh_forward(num_points: int, degree: int, degrees_to_use: int, viewdi
     dev = coeffs.device
     with _on(dev):
         colors = torch.empty((n, 3), dtype=_f32, device=dev)
-        _call("gsr_sh_forward", C.c_uint(n), C.c_uint(degree), C.c_uint(degrees_to_use),
-              _ptr(viewdirs), _ptr(coeffs), _ptr(colors), _stream(dev))
+        _call("gsr_sh_forward", n, degree, degrees_to_use, viewdirs, coeffs, colors, _stream(dev))
     return colors
 
 
@@ -401,8 +374,7 @@ def compute_sh_backward(num_points: int, degree: int, degrees_to_use: int, viewd
     dev = viewdirs.device
     with _on(dev):
         v_coeffs = torch.empty((n, _num_sh_bases(degree), 3), dtype=_f32, device=dev)
-        _call("gsr_sh_backward", C.c_uint(n), C.c_uint(degree), C.c_uint(degrees_to_use),
-              _ptr(viewdirs), _ptr(v_colors), _ptr(v_coeffs), _stream(dev))
+        _call("gsr_sh_backward", n, degree, degrees_to_use, viewdirs, v_colors, v_coeffs, _stream(dev))
     return v_coeffs
 
 
@@ -414,10 +386,9 @@ def cumsum_tiles(num_tiles_hit: Tensor) -> Tensor:
     dev = num_tiles_hit.device
     with _on(dev):
         cum = torch.empty_like(num_tiles_hit)
-        nbytes = int(_lib().gsr_cumsum_workspace_bytes(C.c_int(n)))
+        nbytes = int(_typed().gsr_cumsum_workspace_bytes(n))
         ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
-        _call("gsr_cumsum_tiles", C.c_int(n), _ptr(num_tiles_hit), _ptr(cum), _ptr(ws),
-              C.c_size_t(nbytes), _stream(dev))
+        _call("gsr_cumsum_tiles", n, num_tiles_hit, cum, ws, nbytes, _stream(dev))
     return cum
 
 
@@ -437,9 +408,8 @@ def map_gaussian_to_intersects(
         # zero-filled like the reference: slots not claimed by any splat stay 0
         isect_ids = torch.zeros((I,), dtype=_i64, device=dev)
         gaussian_ids = torch.zeros((I,), dtype=_i32, device=dev)
-        _call("gsr_map_intersects", C.c_int(int(num_points)), C.c_int(I), _ptr(xys), _ptr(depths),
-              _ptr(radii), _ptr(cum_tiles_hit), C.c_int(tile_bounds[0]), C.c_int(tile_bounds[1]),
-              C.c_uint(block_width), _ptr(isect_ids), _ptr(gaussian_ids), _stream(dev))
+        _call("gsr_map_intersects", int(num_points), I, xys, depths, radii, cum_tiles_hit, tile_bounds[0],
+              tile_bounds[1], block_width, isect_ids, gaussian_ids, _stream(dev))
     return isect_ids, gaussian_ids
 
 
@@ -453,10 +423,10 @@ def sort_intersects(isect_ids: Tensor, gaussian_ids: Tensor, num_tiles: int) -> 
     with _on(dev):
         keys = torch.empty_like(isect_ids)
         vals = torch.empty_like(gaussian_ids)
-        nbytes = int(_lib().gsr_sort_workspace_bytes(C.c_int(I)))
+        nbytes = int(_typed().gsr_sort_workspace_bytes(I))
         ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
-        _call("gsr_sort_intersects", C.c_int(I), C.c_int(max(int(num_tiles), 1)), _ptr(isect_ids),
-              _ptr(gaussian_ids), _ptr(keys), _ptr(vals), _ptr(ws), C.c_size_t(nbytes), _stream(dev))
+        _call("gsr_sort_intersects", I, max(int(num_tiles), 1), isect_ids, gaussian_ids, keys, vals, ws, nbytes,
+              _stream(dev))
     return keys, vals
 
 
@@ -468,8 +438,7 @@ def get_tile_bin_edges(num_intersects: int, isect_ids_sorted: Tensor,
     nt = int(tile_bounds[0]) * int(tile_bounds[1])
     with _on(dev):
         tile_bins = alloc_tile_bins(tile_bounds, dev)
-        _call("gsr_tile_bin_edges", C.c_int(int(num_intersects)), _ptr(isect_ids_sorted),
-              C.c_int(nt), _ptr(tile_bins), _stream(dev))
+        _call("gsr_tile_bin_edges", int(num_intersects), isect_ids_sorted, nt, tile_bins, _stream(dev))
     return tile_bins
 
 
@@ -492,11 +461,9 @@ def depth_order(depths: Tensor, radii: Tensor, num_tiles_hit: Optional[Tensor]) 
     with _on(dev):
         order = torch.empty((n,), dtype=_i32, device=dev)
         cum = torch.empty((bands * n,), dtype=_i32, device=dev) if num_tiles_hit is not None else None
-        nbytes = int(_lib().gsr_depth_order_workspace_bytes(C.c_int(n), C.c_int(bands)))
+        nbytes = int(_typed().gsr_depth_order_workspace_bytes(n, bands))
         ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
-        _call("gsr_depth_order", C.c_int(n), _ptr(depths), _ptr(radii),
-              _ptr(num_tiles_hit) if num_tiles_hit is not None else None, C.c_int(bands),
-              _ptr(order), _ptr(cum) if cum is not None else None, _ptr(ws), C.c_size_t(nbytes), _stream(dev))
+        _call("gsr_depth_order", n, depths, radii, num_tiles_hit, bands, order, cum, ws, nbytes, _stream(dev))
     return order, cum
 
 
@@ -506,15 +473,14 @@ def lists_need_counts(num_points: int, num_intersects: int, tile_bounds: Tuple[i
     band) will take the two-level partition for these sizes -- the caller may then skip
     the counts: ``count_reach(..., counts=False)``, ``depth_order(depths, radii, None)``,
     ``bin_sorted(..., cum_sorted=None)``."""
-    return bool(_lib().gsr_bin_sorted_needs_counts(C.c_int(int(num_points)), C.c_int(int(num_intersects)),
-                                                   C.c_int(tile_bounds[0]), C.c_int(tile_bounds[1]),
-                                                   C.c_int(1 if device_sized else 0), C.c_int(1 if want_slots else 0)))
+    return bool(_typed().gsr_bin_sorted_needs_counts(int(num_points), int(num_intersects), tile_bounds[0], tile_bounds[1],
+                                                   1 if device_sized else 0, 1 if want_slots else 0))
 
 
 def tile_bands(tile_bounds: Tuple[int, int, int]) -> int:
     """``gsr_tile_bands``: 1 up to 16384 tiles; above, the number of tile-row bands the
     fused binning works in (4K at 16 px: 4)."""
-    return int(_lib().gsr_tile_bands(C.c_int(tile_bounds[0]), C.c_int(tile_bounds[1])))
+    return int(_typed().gsr_tile_bands(tile_bounds[0], tile_bounds[1]))
 
 
 def publish_int32(src: Tensor, dst: Tensor) -> None:
@@ -525,7 +491,7 @@ def publish_int32(src: Tensor, dst: Tensor) -> None:
         raise RuntimeError("publish_int32: dst must be int32")
     dev = src.device
     with _on(dev):
-        _call("gsr_publish_int32", _ptr(src), _ptr(dst), _stream(dev))
+        _call("gsr_publish_int32", src, dst, _stream(dev))
 
 
 def count_reach(xys: Tensor, radii: Tensor, conics: Tensor, opacities: Tensor,
@@ -547,12 +513,11 @@ def count_reach(xys: Tensor, radii: Tensor, conics: Tensor, opacities: Tensor,
     dev = xys.device
     with _on(dev):
         cnt = torch.empty((int(bands) * n,), dtype=_i32, device=dev) if counts else None
-        recs = torch.empty((n + int(extra_rows), int(_lib().gsr_reach_record_bytes())), dtype=torch.uint8, device=dev)
+        recs = torch.empty((n + int(extra_rows), int(_typed().gsr_reach_record_bytes())), dtype=torch.uint8, device=dev)
         if extra_rows:
             recs[n:].zero_()  # all-zero records are culled ones (empty tile box): `saturation_filter`'s dummy
-        _call("gsr_count_reach", C.c_int(n), _ptr(xys), _ptr(radii), _ptr(conics), _ptr(opacities),
-              C.c_int(tile_bounds[0]), C.c_int(tile_bounds[1]), C.c_int(int(bands)),
-              _ptr(cnt) if cnt is not None else None, _ptr(recs), _stream(dev))
+        _call("gsr_count_reach", n, xys, radii, conics, opacities, tile_bounds[0], tile_bounds[1], int(bands), cnt,
+              recs, _stream(dev))
     return cnt, recs
 
 
@@ -570,15 +535,14 @@ def reach_records_depth_order(xys: Tensor, radii: Tensor, conics: Tensor, opacit
         raise RuntimeError("reach_records_depth_order: xys [N,2], conics [N,3], opacities [N,1], depths [N] expected")
     dev = xys.device
     with _on(dev):
-        recs = torch.empty((n + int(extra_rows), int(_lib().gsr_reach_record_bytes())), dtype=torch.uint8, device=dev)
+        recs = torch.empty((n + int(extra_rows), int(_typed().gsr_reach_record_bytes())), dtype=torch.uint8, device=dev)
         if extra_rows:
             recs[n:].zero_()  # (as in count_reach: the dummy culled record)
         order = torch.empty((n,), dtype=_i32, device=dev)
-        nbytes = int(_lib().gsr_depth_order_workspace_bytes(C.c_int(n), C.c_int(1)))
+        nbytes = int(_typed().gsr_depth_order_workspace_bytes(n, 1))
         ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
-        _call("gsr_reach_records_depth_order", C.c_int(n), _ptr(xys), _ptr(radii), _ptr(conics), _ptr(opacities),
-              _ptr(depths), C.c_int(tile_bounds[0]), C.c_int(tile_bounds[1]), _ptr(recs), _ptr(order), _ptr(ws),
-              C.c_size_t(nbytes), _stream(dev))
+        _call("gsr_reach_records_depth_order", n, xys, radii, conics, opacities, depths, tile_bounds[0], tile_bounds[1],
+              recs, order, ws, nbytes, _stream(dev))
     return recs, order
 
 
@@ -610,7 +574,7 @@ def bin_sorted(num_points: int, num_intersects: int, order: Tensor, cum_sorted: 
     _check(radii, "radii", _i32)
     if reach_records is not None:
         _check(reach_records, "reach_records", torch.uint8)
-        if reach_records.numel() != int(num_points) * int(_lib().gsr_reach_record_bytes()):
+        if reach_records.numel() != int(num_points) * int(_typed().gsr_reach_record_bytes()):
             raise RuntimeError("bin_sorted: reach_records has the wrong size")
     I = int(num_intersects)
     nt = int(tile_bounds[0]) * int(tile_bounds[1])
@@ -618,16 +582,13 @@ def bin_sorted(num_points: int, num_intersects: int, order: Tensor, cum_sorted: 
     with _on(dev):
         ids = torch.empty((I,), dtype=_i32, device=dev)
         tile_bins = alloc_tile_bins(tile_bounds, dev)
-        nbytes = int(_lib().gsr_bin_sorted_workspace_bytes(C.c_int(int(num_points)), C.c_int(I),
-                                                           C.c_int(tile_bounds[0]), C.c_int(tile_bounds[1])))
+        nbytes = int(_typed().gsr_bin_sorted_workspace_bytes(int(num_points), I, tile_bounds[0], tile_bounds[1]))
         bands = cum_sorted.numel() // max(int(num_points), 1) if int(num_points) and cum_sorted is not None else 1
         ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
         slots = torch.empty((I,), dtype=_i32, device=dev) if want_slots else None
-        head = (C.c_int(int(num_points)), C.c_int(I), _ptr(order),
-                _ptr(cum_sorted) if cum_sorted is not None else None, _ptr(xys), _ptr(radii),
-                _ptr(reach_records) if reach_records is not None else None, C.c_int(tile_bounds[0]),
-                C.c_int(tile_bounds[1]), C.c_uint(block_width), C.c_int(bands), _ptr(ids), _ptr(tile_bins))
-        tail = (_ptr(slots) if want_slots else None, _ptr(ws), C.c_size_t(nbytes), _stream(dev))
+        head = (int(num_points), I, order, cum_sorted, xys, radii, reach_records, tile_bounds[0], tile_bounds[1],
+                block_width, bands, ids, tile_bins)
+        tail = (slots, ws, nbytes, _stream(dev))
         if device_sized:
             # the two job orders of the compositing launches that will walk these lists ride in the list build's last
             # launch where it can carry them (the two-level partition): the words `forward_orders` would compute
@@ -635,13 +596,12 @@ def bin_sorted(num_points: int, num_intersects: int, order: Tensor, cum_sorted: 
                 _list_build_orders(tile_bins, I, nt, tile_bounds) if job_orders is None else job_orders)
             if fwd:
                 built = C.c_int(0)
-                _call("gsr_bin_sorted_dev_jobs", *head, _ptr(count_out) if count_out is not None else None, *tail[:-1],
-                      C.c_int(fwd), C.c_int(second), C.byref(built), tail[-1])
+                _call("gsr_bin_sorted_dev_jobs", *head, count_out, *tail[:-1], fwd, second, C.byref(built), tail[-1])
                 if built.value and second:  # (as view.hip and rasterize_gaussians_forward leave them)
                     tile_bins._gsr_jobs_bwd, tile_bins._gsr_jobs_fwd = second, fwd
                     tile_bins._gsr_jobs_by_list_build = True
             else:
-                _call("gsr_bin_sorted_dev", *head, _ptr(count_out) if count_out is not None else None, *tail)
+                _call("gsr_bin_sorted_dev", *head, count_out, *tail)
         else:
             _call("gsr_bin_sorted", *head, *tail)
     if want_slots:
@@ -664,12 +624,10 @@ def tile_lists_subrange(order_sub: Tensor, capacity: int, reach_records: Tensor,
     dev = ids_out.device
     with _on(dev):
         bins = alloc_tile_bins(tile_bounds, dev)
-        nbytes = int(_lib().gsr_tile_lists_subrange_workspace_bytes(C.c_int(n), C.c_int(int(capacity)),
-                                                                   C.c_int(tile_bounds[0]), C.c_int(tile_bounds[1])))
+        nbytes = int(_typed().gsr_tile_lists_subrange_workspace_bytes(n, int(capacity), tile_bounds[0], tile_bounds[1]))
         ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
-        _call("gsr_tile_lists_subrange", C.c_int(n), C.c_int(int(capacity)), _ptr(order_sub), _ptr(reach_records),
-              C.c_int(tile_bounds[0]), C.c_int(tile_bounds[1]), _ptr(ids_out), _ptr(bins),
-              _ptr(count_out) if count_out is not None else None, _ptr(ws), C.c_size_t(nbytes), _stream(dev))
+        _call("gsr_tile_lists_subrange", n, int(capacity), order_sub, reach_records, tile_bounds[0], tile_bounds[1],
+              ids_out, bins, count_out, ws, nbytes, _stream(dev))
     return bins
 
 
@@ -683,11 +641,10 @@ def saturation_filter(order_sub: Tensor, reach_records: Tensor, dummy_index: int
     dev = tile_flags.device
     with _on(dev):
         out = torch.empty_like(order_sub)
-        nbytes = int(_lib().gsr_saturation_filter_workspace_bytes(C.c_int(tile_bounds[0]), C.c_int(tile_bounds[1])))
+        nbytes = int(_typed().gsr_saturation_filter_workspace_bytes(tile_bounds[0], tile_bounds[1]))
         ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        _call("gsr_saturation_filter", C.c_int(order_sub.numel()), _ptr(order_sub), _ptr(reach_records),
-              C.c_int(int(dummy_index)), _ptr(tile_flags), C.c_int(tile_bounds[0]), C.c_int(tile_bounds[1]), _ptr(out),
-              _ptr(ws), C.c_size_t(nbytes), _ptr(stats_out) if stats_out is not None else None, _stream(dev))
+        _call("gsr_saturation_filter", order_sub.numel(), order_sub, reach_records, int(dummy_index), tile_flags,
+              tile_bounds[0], tile_bounds[1], out, ws, nbytes, stats_out, _stream(dev))
     return out
 
 
@@ -702,14 +659,10 @@ def rasterize_forward_round(rnd: int, tile_bounds, img_size, gaussian_ids_sorted
     dev = xys.device
     nt = tile_bounds[0] * tile_bounds[1]
     with _on(dev):
-        _call("gsr_rasterize_forward_round", C.c_int(int(rnd)), C.c_int(tile_bounds[0]), C.c_int(tile_bounds[1]),
-              C.c_uint(W), C.c_uint(H), _ptr(gaussian_ids_sorted), _ptr(tile_bins), C.c_int(int(idx_base)), _ptr(xys),
-              _ptr(conics), _ptr(colors), _ptr(extra) if extra is not None else None, _ptr(opacities),
-              _ptr(background), C.c_float(extra_background), _ptr(out_img),
-              _ptr(out_extra) if out_extra is not None else None, _ptr(final_Ts), _ptr(final_idx),
-              _ptr(tile_flags), C.c_int(deep_tile_threshold(tile_bins.shape[0] * 400, nt)),
-              _ptr(out_alpha) if out_alpha is not None else None, _ptr(zero) if zero is not None else None,
-              C.c_size_t(zero.numel() * 4 if zero is not None else 0), _stream(dev))
+        _call("gsr_rasterize_forward_round", int(rnd), tile_bounds[0], tile_bounds[1], W, H, gaussian_ids_sorted,
+              tile_bins, int(idx_base), xys, conics, colors, extra, opacities, background, extra_background, out_img,
+              out_extra, final_Ts, final_idx, tile_flags, deep_tile_threshold(tile_bins.shape[0] * 400, nt), out_alpha,
+              zero, zero.numel() * 4 if zero is not None else 0, _stream(dev))
 
 
 def rasterize_backward_two(img_height, img_width, gaussian_ids_sorted, tile_bins, tile_bins2, idx_base2: int, xys,
@@ -731,15 +684,12 @@ def rasterize_backward_two(img_height, img_width, gaussian_ids_sorted, tile_bins
         v_xy, v_conic, v_colors, v_opacity, v_extra = _carve_accumulators(accumulators, n, 3, extra is not None, dev)
         nt = ((img_width + 15) // 16) * ((img_height + 15) // 16)
         v_xy_abs = _check_absgrad(v_xy_abs, n, dev)
-        _call("gsr_rasterize_backward_two" if v_xy_abs is None else "gsr_rasterize_backward_two_abs", C.c_uint(img_height), C.c_uint(img_width), C.c_int(n),
-              _ptr(gaussian_ids_sorted), _ptr(tile_bins), _ptr(tile_bins2), C.c_int(int(idx_base2)), _ptr(xys),
-              _ptr(conics), _ptr(colors), _ptr(extra) if extra is not None else None, _ptr(opacities),
-              _ptr(background), C.c_float(extra_background), _ptr(final_Ts), _ptr(final_idx), _ptr(v_output),
-              _ptr(v_output_extra) if extra is not None else None,
-              _ptr(v_output_alpha) if v_output_alpha is not None else None, _ptr(v_xy), _ptr(v_conic), _ptr(v_colors),
-              _ptr(v_extra) if v_extra is not None else None, _ptr(v_opacity),
-              C.c_int(deep_tile_threshold(tile_bins.shape[0] * 400, nt, backward=True)), C.c_int(1 if zeroed else 0),
-              *(() if v_xy_abs is None else (_ptr(v_xy_abs),)), _stream(dev))
+        _call("gsr_rasterize_backward_two" if v_xy_abs is None else "gsr_rasterize_backward_two_abs", img_height,
+              img_width, n, gaussian_ids_sorted, tile_bins, tile_bins2, int(idx_base2), xys, conics, colors, extra,
+              opacities, background, extra_background, final_Ts, final_idx, v_output,
+              v_output_extra if extra is not None else None, v_output_alpha, v_xy, v_conic, v_colors, v_extra,
+              v_opacity, deep_tile_threshold(tile_bins.shape[0] * 400, nt, backward=True), 1 if zeroed else 0,
+              *(() if v_xy_abs is None else (v_xy_abs,)), _stream(dev))
     if extra is not None:
         return v_xy, v_conic, v_colors, v_extra, v_opacity
     return v_xy, v_conic, v_colors, v_opacity
@@ -803,7 +753,7 @@ def _forward_segments(list_entries: int, num_tiles: int, H: int, W: int, dev):
         segs = min(segs, cap)
     if segs < 2:
         return 0, 0, None
-    nbytes = int(_lib().gsr_rasterize_forward_seg_workspace_bytes(C.c_uint(H), C.c_uint(W), C.c_int(segs)))
+    nbytes = int(_typed().gsr_rasterize_forward_seg_workspace_bytes(H, W, segs))
     return segs, seg_min, torch.empty((nbytes,), dtype=torch.uint8, device=dev)
 
 
@@ -864,7 +814,7 @@ _DEEP_TAIL_SHIFT, _DEEP_THRESHOLD_MASK = 22, 0x3FFFFF
 
 
 def tile_jobs_ints(tile_bounds) -> int:
-    return int(_lib().gsr_tile_jobs_ints(C.c_int(int(tile_bounds[0])), C.c_int(int(tile_bounds[1]))))
+    return int(_typed().gsr_tile_jobs_ints(int(tile_bounds[0]), int(tile_bounds[1])))
 
 
 _jobs_ints_cache = {}
@@ -948,8 +898,7 @@ def forward_orders(tile_bins: Optional[Tensor], list_entries: int, num_tiles: in
         # the list build wrote orders for other words (another list count, a changed tuning row): build them again
         order_counters["orders_prebuilt_fallbacks"] += 1
         tile_bins._gsr_jobs_by_list_build = False
-    _call("gsr_tile_jobs_build", C.c_int(int(tile_bounds[0])), C.c_int(int(tile_bounds[1])), _ptr(tile_bins), C.c_int(fwd),
-          C.c_int(second), _stream(dev))
+    _call("gsr_tile_jobs_build", int(tile_bounds[0]), int(tile_bounds[1]), tile_bins, fwd, second, _stream(dev))
     try:
         tile_bins._gsr_jobs_bwd, tile_bins._gsr_jobs_fwd = second, (fwd if second else 0)
     except AttributeError:
@@ -1023,12 +972,12 @@ def _raster_plan(n: int, capacity: int, tb, have_order: bool):
     key = (n, capacity, tb[0], tb[1], have_order)
     plan = _raster_plan_cache.get(key)
     if plan is None:
-        lib = _lib()
+        lib = _typed()
         lean = not lists_need_counts(n, capacity, tb, device_sized=True)
         al = lambda b: (int(b) + 255) & ~255
         rec_b = al(n * int(lib.gsr_reach_record_bytes()))
-        sort_b = 0 if (have_order and lean) else int(lib.gsr_depth_order_workspace_bytes(C.c_int(n), C.c_int(1)))
-        bin_b = int(lib.gsr_bin_sorted_workspace_bytes(C.c_int(n), C.c_int(capacity), C.c_int(tb[0]), C.c_int(tb[1])))
+        sort_b = 0 if (have_order and lean) else int(lib.gsr_depth_order_workspace_bytes(n, 1))
+        bin_b = int(lib.gsr_bin_sorted_workspace_bytes(n, capacity, tb[0], tb[1]))
         off, o = {}, 0
         for name, size in (("records", rec_b), ("order", 0 if (have_order and lean) else al(4 * n)),
                            ("counts", 0 if lean else al(4 * n)), ("cum", 0 if lean else al(4 * n)),
@@ -1124,13 +1073,10 @@ def _composite16_forward(tile_bounds, W: int, H: int, gaussian_ids_sorted, tile_
         deep = forward_orders(tile_bins, entries, tiles, tile_bounds, dev)
     segs, seg_min, seg_ws = _forward_segments(entries, tiles, H, W, dev)
     zero_bytes = zero.numel() * 4 if zero is not None else 0
-    _call("gsr_rasterize_forward_seg", C.c_int(tile_bounds[0]), C.c_int(tile_bounds[1]), C.c_uint(W), C.c_uint(H),
-          _ptr(gaussian_ids_sorted), _ptr(tile_bins), _ptr(xys), _ptr(conics), _ptr(colors),
-          _ptr(extra) if extra is not None else None, _ptr(opacities), _ptr(background), C.c_float(extra_background),
-          _ptr(out_img), _ptr(out_extra) if out_extra is not None else None, _ptr(final_Ts), _ptr(final_idx),
-          C.c_int(deep), _ptr(alpha) if alpha is not None else None, _ptr(zero) if zero_bytes else None,
-          C.c_size_t(zero_bytes), C.c_int(segs), C.c_int(seg_min), _ptr(seg_ws) if seg_ws is not None else None,
-          C.c_size_t(seg_ws.numel() if seg_ws is not None else 0), _stream(dev))
+    _call("gsr_rasterize_forward_seg", tile_bounds[0], tile_bounds[1], W, H, gaussian_ids_sorted, tile_bins, xys,
+          conics, colors, extra, opacities, background, extra_background, out_img, out_extra, final_Ts, final_idx, deep,
+          alpha, zero if zero_bytes else None, zero_bytes, segs, seg_min, seg_ws,
+          seg_ws.numel() if seg_ws is not None else 0, _stream(dev))
 
 
 def composite_prepared(tile_bounds, img_width: int, img_height: int, gaussian_ids_sorted, tile_bins, xys, conics, colors,
@@ -1181,14 +1127,14 @@ def _rasterize_forward(tile_bounds, block, img_size, gaussian_ids_sorted, tile_b
         else:
             if alpha is not None or (ex and zero is not None):  # (the generic kernel writes neither)
                 raise RuntimeError("rasterize_forward_ex: out_alpha / zero_ptr need block_width 16")
-            sizes = (C.c_int(tile_bounds[0]), C.c_int(tile_bounds[1]), C.c_uint(block[0]), C.c_uint(W), C.c_uint(H))
-            args = (_ptr(gaussian_ids_sorted), _ptr(tile_bins), _ptr(xys), _ptr(conics), _ptr(colors), _ptr(opacities),
-                    _ptr(background), _ptr(out_img), _ptr(final_Ts), _ptr(final_idx))
+            sizes = (tile_bounds[0], tile_bounds[1], block[0], W, H)
+            args = (gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, background, out_img, final_Ts,
+                    final_idx)
             if nd:
-                _call("gsr_rasterize_forward_nd", *sizes, C.c_uint(channels), *args, _stream(dev))
+                _call("gsr_rasterize_forward_nd", *sizes, channels, *args, _stream(dev))
             else:
                 deep = deep_tile_threshold(gaussian_ids_sorted.numel(), tile_bounds[0] * tile_bounds[1])
-                _call("gsr_rasterize_forward", *sizes, *args, C.c_int(deep), _stream(dev))
+                _call("gsr_rasterize_forward", *sizes, *args, deep, _stream(dev))
     return (out_img, final_Ts, final_idx, alpha) if ex else (out_img, final_Ts, final_idx)
 
 
@@ -1211,9 +1157,8 @@ def rasterize_forward_scan(tile_bounds, img_size, gaussian_ids_sorted, tile_bins
         img = torch.empty((H, W, 3), dtype=_f32, device=dev)
         Ts = torch.empty((H, W), dtype=_f32, device=dev)
         idx = torch.empty((H, W), dtype=_i32, device=dev)
-        _call("gsr_rasterize_forward_scan", C.c_int(tile_bounds[0]), C.c_int(tile_bounds[1]), C.c_uint(W), C.c_uint(H),
-              _ptr(gaussian_ids_sorted), _ptr(tile_bins), _ptr(xys), _ptr(conics), _ptr(colors), _ptr(opacities),
-              _ptr(background), _ptr(img), _ptr(Ts), _ptr(idx), _stream(dev))
+        _call("gsr_rasterize_forward_scan", tile_bounds[0], tile_bounds[1], W, H, gaussian_ids_sorted, tile_bins, xys,
+              conics, colors, opacities, background, img, Ts, idx, _stream(dev))
     return img, Ts, idx
 
 
@@ -1302,22 +1247,20 @@ def rasterize_backward_det(img_height, img_width, gaussian_ids_sorted, tile_bins
         raise RuntimeError("rasterize_backward_det: order / cum_sorted / slot_of_entry do not match the lists")
     bands = cum_sorted.numel() // n if n else 1
     dev = xys.device
-    _o = lambda t: None if t is None else _ptr(t)
     with _on(dev):
         v_xy = torch.empty((n, 2), dtype=_f32, device=dev)
         v_conic = torch.empty((n, 3), dtype=_f32, device=dev)
         v_colors = torch.empty((n, 3), dtype=_f32, device=dev)
         v_opacity = torch.empty((n, 1), dtype=_f32, device=dev)
         v_extra = torch.empty((n,), dtype=_f32, device=dev) if rgbd else None
-        nbytes = int(_lib().gsr_rasterize_backward_det_workspace_bytes(C.c_int(L)))
+        nbytes = int(_typed().gsr_rasterize_backward_det_workspace_bytes(L))
         ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
         v_xy_abs = _check_absgrad(v_xy_abs, n, dev)
-        _call("gsr_rasterize_backward_det" if v_xy_abs is None else "gsr_rasterize_backward_det_abs", C.c_uint(img_height), C.c_uint(img_width), C.c_int(n), C.c_int(L),
-              _ptr(gaussian_ids_sorted), _ptr(tile_bins), _ptr(xys), _ptr(conics), _ptr(colors), _o(extra),
-              _ptr(opacities), _ptr(background), C.c_float(extra_background), _ptr(final_Ts), _ptr(final_idx),
-              _ptr(v_output), _o(v_output_extra), _o(v_output_alpha), _ptr(order), _ptr(cum_sorted), C.c_int(bands),
-              _ptr(slot_of_entry), _ptr(ws), C.c_size_t(nbytes), _ptr(v_xy), _ptr(v_conic), _ptr(v_colors),
-              _o(v_extra), _ptr(v_opacity), *(() if v_xy_abs is None else (_ptr(v_xy_abs),)), _stream(dev))
+        _call("gsr_rasterize_backward_det" if v_xy_abs is None else "gsr_rasterize_backward_det_abs", img_height,
+              img_width, n, L, gaussian_ids_sorted, tile_bins, xys, conics, colors, extra, opacities, background,
+              extra_background, final_Ts, final_idx, v_output, v_output_extra, v_output_alpha, order, cum_sorted, bands,
+              slot_of_entry, ws, nbytes, v_xy, v_conic, v_colors, v_extra, v_opacity,
+              *(() if v_xy_abs is None else (v_xy_abs,)), _stream(dev))
     if rgbd:
         return v_xy, v_conic, v_colors, v_extra, v_opacity
     return v_xy, v_conic, v_colors, v_opacity
@@ -1354,20 +1297,16 @@ def _composite16_backward(img_height, img_width, n: int, gaussian_ids_sorted, ti
     and is ``gsr_rasterize_backward_ex`` / ``_rgbd`` where not.  ``zeroed``: the accumulators are cleared already.
     ``v_xy_abs`` ([n,2]): ``gsr_rasterize_backward_abs`` instead -- the same call, which also overwrites it with the
     absgrad."""
-    _o = lambda t: None if t is None else _ptr(t)  # noqa: E731
     tb = ((int(img_width) + 15) // 16, (int(img_height) + 15) // 16)
     entries, tiles = gaussian_ids_sorted.numel(), tb[0] * tb[1]
     segs, seg_min = depth_segments(entries, tiles)
     ws = torch.empty(((segs - 1) * int(img_height) * int(img_width), 2), dtype=_f32, device=dev) if segs > 1 else None
     v_xy_abs = _check_absgrad(v_xy_abs, n, dev)
-    _call("gsr_rasterize_backward_seg" if v_xy_abs is None else "gsr_rasterize_backward_abs", C.c_uint(img_height),
-          C.c_uint(img_width), C.c_int(n), _ptr(gaussian_ids_sorted), _ptr(tile_bins), _ptr(xys), _ptr(conics), _ptr(colors), _o(extra), _ptr(opacities),
-          _ptr(background), C.c_float(extra_background), _ptr(final_Ts), _ptr(final_idx), _ptr(v_output),
-          _o(v_output_extra), _o(v_output_alpha), _ptr(v_xy), _ptr(v_conic), _ptr(v_colors), _o(v_extra), _ptr(v_opacity),
-          C.c_int(backward_order(tile_bins, entries, tiles, tb)), C.c_int(1 if zeroed else 0),
-          C.c_int(segs if ws is not None else 0), C.c_int(seg_min), _o(ws),
-          C.c_size_t(ws.numel() * 4 if ws is not None else 0), *(() if v_xy_abs is None else (_ptr(v_xy_abs),)),
-          _stream(dev))
+    _call("gsr_rasterize_backward_seg" if v_xy_abs is None else "gsr_rasterize_backward_abs", img_height, img_width, n,
+          gaussian_ids_sorted, tile_bins, xys, conics, colors, extra, opacities, background, extra_background, final_Ts,
+          final_idx, v_output, v_output_extra, v_output_alpha, v_xy, v_conic, v_colors, v_extra, v_opacity,
+          backward_order(tile_bins, entries, tiles, tb), 1 if zeroed else 0, segs if ws is not None else 0, seg_min, ws,
+          ws.numel() * 4 if ws is not None else 0, *(() if v_xy_abs is None else (v_xy_abs,)), _stream(dev))
 
 
 def _rasterize_backward(img_height, img_width, block_width, gaussian_ids_sorted, tile_bins, xys,
@@ -1397,17 +1336,15 @@ def _rasterize_backward(img_height, img_width, block_width, gaussian_ids_sorted,
                                   background, final_Ts, final_idx, v_output, v_output_alpha, v_xy, v_conic, v_colors,
                                   v_opacity, zeroed, dev, v_xy_abs=v_xy_abs)
         else:
-            sizes = (C.c_uint(img_height), C.c_uint(img_width), C.c_uint(block_width))
-            args = (C.c_int(n), _ptr(gaussian_ids_sorted), _ptr(tile_bins), _ptr(xys), _ptr(conics), _ptr(colors),
-                    _ptr(opacities), _ptr(background), _ptr(final_Ts), _ptr(final_idx), _ptr(v_output),
-                    _ptr(v_output_alpha) if v_output_alpha is not None else None, _ptr(v_xy), _ptr(v_conic), _ptr(v_colors),
-                    _ptr(v_opacity))
+            sizes = (img_height, img_width, block_width)
+            args = (n, gaussian_ids_sorted, tile_bins, xys, conics, colors, opacities, background, final_Ts, final_idx,
+                    v_output, v_output_alpha, v_xy, v_conic, v_colors, v_opacity)
             if nd:
-                _call("gsr_rasterize_backward_nd", *sizes, C.c_uint(channels), *args, _stream(dev))
+                _call("gsr_rasterize_backward_nd", *sizes, channels, *args, _stream(dev))
             else:
                 tiles = ((img_width + block_width - 1) // block_width) * ((img_height + block_width - 1) // block_width)
-                _call("gsr_rasterize_backward", *sizes, *args,
-                      C.c_int(deep_tile_threshold(gaussian_ids_sorted.numel(), tiles, backward=True)), _stream(dev))
+                deep = deep_tile_threshold(gaussian_ids_sorted.numel(), tiles, backward=True)
+                _call("gsr_rasterize_backward", *sizes, *args, deep, _stream(dev))
     return v_xy, v_conic, v_colors, v_opacity
 
 
@@ -1443,5 +1380,5 @@ def compute_cov2d_bounds(num_pts: int, cov2d: Tensor) -> Tuple[Tensor, Tensor]:
     with _on(dev):
         conics = torch.empty((n, cov2d.size(1)), dtype=_f32, device=dev)
         radii = torch.empty((n, 1), dtype=_f32, device=dev)
-        _call("gsr_cov2d_bounds", C.c_int(n), _ptr(cov2d), _ptr(conics), _ptr(radii), _stream(dev))
+        _call("gsr_cov2d_bounds", n, cov2d, conics, radii, _stream(dev))
     return conics, radii

@@ -10,146 +10,39 @@ import ctypes as C
 import os
 import subprocess
 
+from torch import Tensor
+
+from ._prototypes import PROTOTYPES
+
 PATH = os.path.dirname(os.path.abspath(__file__))
 # (GSR_LIBRARY: another build of the same library, for A/B measurements of compile-time variants -- tools/r05/)
 LIB_PATH = os.environ.get("GSR_LIBRARY") or os.path.join(PATH, "libgsraster.so")
 CSRC = os.path.normpath(os.path.join(PATH, "..", "..", "csrc"))
 
-# every symbol include/gsraster.h declares
-SYMBOLS = (
-    "gsr_version",
-    "gsr_last_error",
-    "gsr_project_forward",
-    "gsr_project_backward",
-    "gsr_project_forward_aa",
-    "gsr_project_backward_aa",
-    "gsr_project_forward_crop",
-    "gsr_crop_mask",
-    "gsr_project_backward_pose_workspace",
-    "gsr_project_backward_pose",
-    "gsr_sh_forward",
-    "gsr_sh_backward",
-    "gsr_cumsum_workspace_bytes",
-    "gsr_cumsum_tiles",
-    "gsr_map_intersects",
-    "gsr_sort_workspace_bytes",
-    "gsr_sort_intersects",
-    "gsr_tile_bin_edges",
-    "gsr_reach_record_bytes",
-    "gsr_tile_bands",
-    "gsr_count_reach",
-    "gsr_depth_order_workspace_bytes",
-    "gsr_depth_order",
-    "gsr_reach_records_depth_order",
-    "gsr_bin_sorted_workspace_bytes",
-    "gsr_bin_sorted_needs_counts",
-    "gsr_bin_sorted",
-    "gsr_bin_sorted_dev",
-    "gsr_bin_sorted_dev_jobs",
-    "gsr_publish_int32",
-    "gsr_rasterize_forward",
-    "gsr_rasterize_backward",
-    "gsr_rasterize_forward_ex",
-    "gsr_rasterize_backward_ex",
-    "gsr_rasterize_forward_seg",
-    "gsr_rasterize_forward_seg_workspace_bytes",
-    "gsr_rasterize_backward_seg",
-    "gsr_rasterize_backward_seg_workspace_bytes",
-    "gsr_rasterize_backward_abs",
-    "gsr_rasterize_backward_two_abs",
-    "gsr_rasterize_backward_det_abs",
-    "gsr_rasterize_forward_nd",
-    "gsr_rasterize_backward_nd",
-    "gsr_cov2d_bounds",
-    "gsr_l1_ssim_forward",
-    "gsr_l1_ssim_backward",
-    "gsr_l1_forward",
-    "gsr_l1_backward",
-    "gsr_depth_l1_forward",
-    "gsr_depth_l1_backward",
-    "gsr_l1_ssim_masked_forward",
-    "gsr_l1_ssim_masked_backward",
-    "gsr_l1_masked_forward",
-    "gsr_l1_masked_backward",
-    "gsr_depth_l1_masked_forward",
-    "gsr_depth_l1_masked_backward",
-    "gsr_sh_forward_split",
-    "gsr_sh_backward_split",
-    "gsr_sh_backward_views",
-    "gsr_rasterize_forward_rgbd",
-    "gsr_rasterize_forward_scan",
-    "gsr_tile_lists_subrange_workspace_bytes",
-    "gsr_tile_lists_subrange",
-    "gsr_saturation_filter_workspace_bytes",
-    "gsr_saturation_filter",
-    "gsr_rasterize_forward_round",
-    "gsr_rasterize_backward_two",
-    "gsr_view_forward",
-    "gsr_view_forward_crop",
-    "gsr_rasterize_gaussians_forward",
-    "gsr_view_backward",
-    "gsr_rasterize_backward_rgbd",
-    "gsr_activate_forward",
-    "gsr_activate_backward",
-    "gsr_densify_stats",
-    "gsr_densify_stats_dev",
-    "gsr_refine_workspace_bytes",
-    "gsr_refine_plan",
-    "gsr_refine_apply",
-    "gsr_mcmc_relocation",
-    "gsr_mcmc_workspace_bytes",
-    "gsr_mcmc_plan",
-    "gsr_mcmc_apply",
-    "gsr_mcmc_noise",
-    "gsr_mcmc_reg_workspace_bytes",
-    "gsr_mcmc_reg_forward",
-    "gsr_mcmc_reg_backward",
-    "gsr_adam_step",
-    "gsr_rasterize_backward_det_workspace_bytes",
-    "gsr_rasterize_backward_det",
-    "gsr_tile_jobs_ints",
-    "gsr_tile_jobs_build",
-    "gsr_tsdf_touch",
-    "gsr_tsdf_allocate_workspace_bytes",
-    "gsr_tsdf_allocate",
-    "gsr_tsdf_integrate",
-    "gsr_tsdf_extract_points_workspace_bytes",
-    "gsr_tsdf_extract_points_count",
-    "gsr_tsdf_extract_points_emit",
-    "gsr_tsdf_extract_mesh_workspace_bytes",
-    "gsr_tsdf_extract_mesh_count",
-    "gsr_tsdf_extract_mesh_emit",
-    "gsr_mesh_clean_workspace_bytes",
-    "gsr_mesh_label",
-    "gsr_mesh_emit",
-    "gsr_mesh_distance_workspace_bytes",
-    "gsr_mesh_bvh_build",
-    "gsr_mesh_distance_query",
-    "gsr_mesh_distance_stats",
-    "gsr_canny_workspace_bytes",
-    "gsr_canny",
-    "gsr_depth_reg_forward",
-    "gsr_depth_reg_backward",
-    "gsr_local_pearson_forward",
-    "gsr_local_pearson_backward",
-    "gsr_log_depth_forward",
-    "gsr_log_depth_backward",
-    "gsr_tv_forward",
-    "gsr_tv_backward",
-    "gsr_bilagrid_slice_forward",
-    "gsr_bilagrid_slice_backward",
-    "gsr_bilagrid_tv_forward",
-    "gsr_bilagrid_tv_backward",
-    "gsr_knn_workspace_bytes",
-    "gsr_knn_build",
-    "gsr_knn_query",
-    "gsr_target_from_u8",
-    "gsr_plane_from_int",
-    "gsr_debug_count_staged",
-    "gsr_debug_wave_trace",
-    "gsr_calibrate_valu",
-    "gsr_calibrate_copy",
-)
+# every entry include/gsraster.h declares, with its prototype (generated: tools/gen_prototypes.py)
+SYMBOLS = tuple(PROTOTYPES)
+
+
+class Pointer(C.c_void_p):
+    """What the typed handle takes for a pointer parameter (any ``T *``, ``void *``, ``gsr_stream_t``): a tensor
+    (its ``data_ptr()``, whatever the device and dtype), None (NULL), an int (an address or a stream handle) or what
+    ``c_void_p`` itself converts -- a ``c_void_p``, ``byref(struct)``, a ctypes array.  Anything else, a float or a
+    str for instance, is a ``ctypes.ArgumentError`` at the call."""
+
+    @classmethod
+    def from_param(cls, value):
+        if isinstance(value, Tensor):
+            # (c_void_p's own converter on the address: ~60 ns less per pointer than building a c_void_p, which on
+            #  the host-bound 480 x 270 step is what keeps this path no slower than hand-wrapped arguments)
+            return _void_p_from_param(value.data_ptr())
+        if isinstance(value, (str, bytes)):  # (c_void_p would pass the characters' address)
+            raise TypeError("tensor, None, address or ctypes pointer expected")
+        return _void_p_from_param(value)
+
+
+_void_p_from_param = C.c_void_p.from_param
+_KINDS = {"p": Pointer, "i": C.c_int, "I": C.c_uint, "f": C.c_float, "d": C.c_double, "z": C.c_size_t,
+          "q": C.c_longlong, "Q": C.c_ulonglong, "s": C.c_char_p}
 
 
 def build(verbose: bool = False) -> str:
@@ -159,7 +52,7 @@ def build(verbose: bool = False) -> str:
     return LIB_PATH
 
 
-def _load():
+def _load(typed: bool):
     if not os.path.exists(LIB_PATH):
         raise ImportError(
             f"rasterizer: native library {LIB_PATH} not found. Build it with "
@@ -169,42 +62,34 @@ def _load():
     missing = [s for s in SYMBOLS if not hasattr(lib, s)]
     if missing:
         raise ImportError(f"rasterizer: {LIB_PATH} lacks symbols {missing}")
-    lib.gsr_last_error.restype = C.c_char_p
-    lib.gsr_version.restype = C.c_int
-    lib.gsr_calibrate_valu.restype = C.c_longlong
-    lib.gsr_tile_jobs_ints.restype = C.c_size_t
-    lib.gsr_project_backward_pose_workspace.restype = C.c_size_t
-    lib.gsr_cumsum_workspace_bytes.restype = C.c_size_t
-    lib.gsr_sort_workspace_bytes.restype = C.c_size_t
-    lib.gsr_reach_record_bytes.restype = C.c_size_t
-    lib.gsr_depth_order_workspace_bytes.restype = C.c_size_t
-    lib.gsr_bin_sorted_workspace_bytes.restype = C.c_size_t
-    lib.gsr_refine_workspace_bytes.restype = C.c_size_t
-    lib.gsr_mcmc_workspace_bytes.restype = C.c_size_t
-    lib.gsr_mcmc_reg_workspace_bytes.restype = C.c_size_t
-    lib.gsr_tile_lists_subrange_workspace_bytes.restype = C.c_size_t
-    lib.gsr_saturation_filter_workspace_bytes.restype = C.c_size_t
-    lib.gsr_rasterize_forward_seg_workspace_bytes.restype = C.c_size_t
-    lib.gsr_rasterize_backward_seg_workspace_bytes.restype = C.c_size_t
-    lib.gsr_rasterize_backward_det_workspace_bytes.restype = C.c_size_t
-    lib.gsr_tsdf_allocate_workspace_bytes.restype = C.c_size_t
-    lib.gsr_tsdf_extract_points_workspace_bytes.restype = C.c_size_t
-    lib.gsr_tsdf_extract_mesh_workspace_bytes.restype = C.c_size_t
-    lib.gsr_mesh_clean_workspace_bytes.restype = C.c_size_t
-    lib.gsr_mesh_distance_workspace_bytes.restype = C.c_size_t
-    lib.gsr_canny_workspace_bytes.restype = C.c_size_t
-    lib.gsr_knn_workspace_bytes.restype = C.c_size_t
+    for name, (ret, params) in PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype = _KINDS[ret]
+        if typed:
+            fn.argtypes = [_KINDS[k] for k in params]
     return lib
 
 
-_lib = None
+_lib = _typed = None
 
 
 def lib():
+    """The raw handle: return types only.  A call through it marshals every argument itself and nothing checks it."""
     global _lib
     if _lib is None:
-        _lib = _load()
+        _lib = _load(typed=False)
     return _lib
 
 
-__all__ = ["lib", "build", "LIB_PATH", "SYMBOLS"]
+def typed():
+    """The handle the package calls through: a second ``CDLL`` of the same file (the same loaded library and
+    thread-local ``gsr_last_error``, its own function objects) on which every entry has the header's ``argtypes``.
+    Call sites pass tensors, None, ints and floats; a wrong count is a ``TypeError``, a wrong kind a
+    ``ctypes.ArgumentError``, before anything reaches the library."""
+    global _typed
+    if _typed is None:
+        _typed = _load(typed=True)
+    return _typed
+
+
+__all__ = ["lib", "typed", "build", "LIB_PATH", "SYMBOLS", "PROTOTYPES", "Pointer"]
