@@ -18,3 +18,4 @@ from .crop import CropBox, crop_gaussians, project_gaussians_cropped  # noqa: F4
 from .knn import KNN, initial_log_scales, k_nearest, knn, knn_mean_distance  # noqa: F401
 from .target import DeferredTarget, ImageCache, plane_from_int, target_from_u8  # noqa: F401
 from .bilagrid import BilateralGrids, bilagrid_slice, bilagrid_tv_loss  # noqa: F401
+from .normals import depth_to_normal, gaussian_normals, normal_consistency_loss  # noqa: F401

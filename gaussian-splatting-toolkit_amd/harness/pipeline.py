@@ -78,6 +78,12 @@ def render_view(
     absgrad: bool = False,  # the compositing backward also leaves `out["xys"].absgrad` [N,2] (rasterize_gaussians /
                             # rasterize_gaussians_rgbd, `absgrad=True`); with two passes (depth not fused) it is the
                             # RGB pass's: the colour image's share of the per-pixel gradient
+    render_normals: bool = False,  # together with `render_depth`: `out["normals"]` [H,W,3], the alpha-blended,
+                                   # un-normalised camera-space normals (gs_fused.gaussian_normals composited over a
+                                   # zero background) -- a third compositing pass over the tile lists the rasterizer's
+                                   # cache holds for this view.  Its gradient reaches `quats`, the opacities, the
+                                   # conics and -- like every loss in 2DGS -- `xys`: it JOINS `xys.grad`, so the
+                                   # densification statistics see the normal term as well.  CUDA tensors only
 ) -> Dict[str, Optional[torch.Tensor]]:
     H, W = cam.height, cam.width
     if caller_syncs == "camera" and cam.scalars is not None:
@@ -111,7 +117,8 @@ def render_view(
         #  None)
         return {"rgb": rgb, "alpha": background.new_zeros(H, W, 1), "depth": background.new_ones(H, W, 1) * 10,
                 "depth_acc": background.new_zeros(H, W, 1), "xys": xys, "radii": radii, "depths": depths, "conics": conics,
-                "num_tiles_hit": num_tiles_hit, "rgbs": None}
+                "num_tiles_hit": num_tiles_hit, "rgbs": None,
+                **({"normals": background.new_zeros(H, W, 3)} if render_normals and render_depth else {})}
     if retain_xys_grad and xys.requires_grad:
         xys.retain_grad()  # densification reads xys.grad (vanilla_gs.py:352-353,797-798)
 
@@ -178,5 +185,12 @@ def render_view(
             )[..., 0:1]
         depth_acc = depth_im
         depth_im = torch.where(alpha > 0, depth_im / alpha, depth_im.detach().max()) if normalise_depth else None
+    normals_kw = {}  # (only where asked for: the default call returns the dictionary it always did)
+    if render_normals and render_depth:
+        from gs_fused import gaussian_normals
+
+        normals_kw["normals"] = rasterize_gaussians(
+            xys, depths, radii, conics, num_tiles_hit, gaussian_normals(quats, scales, means3d, cam.viewmat[:3, :]), opac,
+            H, W, BLOCK_WIDTH, background=torch.zeros(3, device=means3d.device))
     return {"rgb": rgb, "alpha": alpha, "depth": depth_im, "depth_acc": depth_acc, "xys": xys, "radii": radii,
-            "depths": depths, "conics": conics, "num_tiles_hit": num_tiles_hit, "rgbs": rgbs}
+            "depths": depths, "conics": conics, "num_tiles_hit": num_tiles_hit, "rgbs": rgbs, **normals_kw}

@@ -298,7 +298,7 @@ class GaussianParams(torch.nn.Module):
 
     def render(self, cam: CameraTensors, background, sh_degree_to_use: int, render_depth=False,
                retain_xys_grad=False, clamp_rgb=True, sh_exchange=None, caller_syncs=False, fused_depth=False,
-               normalise_depth=True, rasterize_mode="classic", absgrad=False):
+               normalise_depth=True, rasterize_mode="classic", absgrad=False, render_normals=False):
         g = self.gauss
         if self.split_sh and g["features_dc"].is_cuda and g["features_rest"].shape[1] in (3, 8, 15):
             coeffs = (g["features_dc"], g["features_rest"])  # gs_fused.spherical_harmonics_split
@@ -317,6 +317,7 @@ class GaussianParams(torch.nn.Module):
                            render_depth=render_depth, retain_xys_grad=retain_xys_grad, viewdirs=dirs,
                            clamp_rgb=clamp_rgb, caller_syncs=caller_syncs, fused_depth=fused_depth,
                            normalise_depth=normalise_depth, rasterize_mode=rasterize_mode, absgrad=absgrad,
+                           **({"render_normals": True} if render_normals else {}),
                            sh_exchange=None if sh_exchange is None else (
                                sh_exchange, ("features_dc", "features_rest"), (g["features_dc"], g["features_rest"])))
 
@@ -540,6 +541,20 @@ class TrainConfig:
     bilagrid_shape: tuple = (16, 16, 8)
     bilagrid_lr: float = 2e-3
     bilagrid_tv_weight: float = 10.0
+    # depth-normal consistency (gs_fused.normal_consistency_loss; what 2DGS, GOF, RaDe-GS, PGSR
+    # and gsplat's `normal_lambda` add to colour-only training): every Gaussian's normal -- the axis of its smallest
+    # scale, turned towards the camera (gs_fused.gaussian_normals) -- is composited into a normal image by a third
+    # compositing pass, a second normal image is derived from the rendered depth inside the loss kernels, and
+    # `normal_lambda` times the mean of 1 - alpha <normals, depth normals> joins the loss from
+    # `step > normal_start_iteration`, with the view's mask.  The two defaults are gsplat's simple_trainer_2dgs.py
+    # (`normal_lambda`, `normal_start_iter`) as recalled -- gsplat was not at hand to check them against; they are the
+    # defaults of an opt-in, not claims.  A step that has the term renders the depth image as well (gaussian-splatting:
+    # from the one RGB + depth compositing pass; co-gs renders it anyway and keeps the pass and the depth head it would
+    # take without the option); a step before the start is the step it always was.  The separate ops on one GPU:
+    # `fused_render`, `use_graph`, a world size above 1 and CPU tensors are refused.  Off: nothing changes.
+    normal_consistency: bool = False
+    normal_lambda: float = 0.05
+    normal_start_iteration: int = 7000
     # (sigma of the log-gain, sigma of the bias): every synthetic training target is multiplied once by a per-view,
     # per-channel gain exp(N(0, sigma_gain)) and shifted by N(0, sigma_bias), drawn from `view_exposure_seed`, standing
     # in for auto-exposure and white balance (a random background: the RGBA ground truth's colour is disturbed, its
@@ -690,6 +705,23 @@ def _check_bilateral_grid(cfg: TrainConfig, device, world: int) -> None:
     if len(tuple(cfg.bilagrid_shape)) != 3:
         raise ValueError(f"bilagrid_shape must be (grid_w, grid_h, grid_l), got {cfg.bilagrid_shape!r}")
     check_grid_shape(*(int(s) for s in cfg.bilagrid_shape))
+
+
+def _check_normal_consistency(cfg: TrainConfig, device, world: int) -> None:
+    """What `normal_consistency` refuses, once the device and the world size are known."""
+    if not cfg.normal_consistency:
+        return
+    if cfg.fused_render:
+        raise ValueError("normal_consistency needs the separate-ops path: the one-node view (fused_render) composites "
+                         "no normal image")
+    if cfg.use_graph:
+        raise ValueError("normal_consistency does not run under use_graph: the captured view holds no normal pass, and "
+                         "the term joins at a step of the schedule")
+    if world > 1:
+        raise ValueError("normal_consistency runs on one GPU (world size 1): the normal pass's gradients of a "
+                         "data-parallel run are not exchanged")
+    if device.type != "cuda":
+        raise ValueError("normal_consistency needs CUDA tensors: the normals and the loss head are HIP kernels")
 
 
 def _params(model: GaussianParams) -> Dict[str, torch.nn.Parameter]:
@@ -1328,13 +1360,33 @@ class SeparateStep:
         self.camera_opt = None  # a camera_opt.CameraOptimizer: its regulariser joins the loss (get_loss_dict)
         self.mcfg = None  # a gs_fused.MCMCConfig: the opacity / scale regularisers join the loss
         self.bilagrid = None  # a BilagridGroup: the heads see the view through its grid, its TV term joins the loss
+        self.normal_terms = []  # normal_consistency: the term's value (a device scalar) at its first and latest step
+        # ... and what a step that has the term adds to the render call: the normal pass, and for gaussian-splatting
+        # the depth image it needs, from the one RGB + depth compositing pass (co-gs renders depth anyway and keeps its
+        # own choice of the pass and of `normalise_depth`).  A step without the term renders what it always did
+        self.normal_kw = dict(render_normals=True, **({} if cogs else dict(render_depth=True, fused_depth=cuda)))
+
+    def _normal_term(self, out, cam, mask):
+        """`normal_lambda` times the depth-normal consistency of the view (gs_fused.normal_consistency_loss).  Where the
+        render left "depth" out (co-gs with the fused depth head, which normalises inside its own kernels) the
+        normalised depth is formed here from the accumulated depth and the alpha, by the render's own rule."""
+        from gs_fused import normal_consistency_loss
+
+        depth, alpha = out["depth"], out["alpha"]
+        if depth is None:
+            acc = out["depth_acc"]
+            depth = torch.where(alpha > 0, acc / alpha, acc.detach().max())
+        term = normal_consistency_loss(out["normals"], depth, alpha, cam.fx, cam.fy, cam.cx, cam.cy, mask=mask)
+        self.normal_terms = self.normal_terms[:1] + [term.detach()]
+        return self.cfg.normal_lambda * term
 
     def __call__(self, step, v, d, cam, deg, bg, target, mask):
         _zero_grads(self.model)
         ph = self.ph = _phase_marks(5) if (self.phase_every and step % self.phase_every == 0) else None
         if ph:
             ph[0].record()
-        out = self.model.render(cam, bg, deg, **self.render_kw)
+        normals_on = self.cfg.normal_consistency and step > self.cfg.normal_start_iteration
+        out = self.model.render(cam, bg, deg, **({**self.render_kw, **self.normal_kw} if normals_on else self.render_kw))
         if ph:
             ph[1].record()
         if self.bilagrid is None:
@@ -1352,6 +1404,8 @@ class SeparateStep:
             loss = loss + self.camera_opt.regulariser()
         if self.mcfg is not None:
             loss = _add_mcmc_regulariser(loss, self.model, self.mcfg)
+        if normals_on:
+            loss = loss + self._normal_term(out, cam, mask)
         if ph:
             ph[2].record()
         loss.backward()
@@ -1433,6 +1487,15 @@ class BilagridGroup:
                                        "lr": self.cfg.bilagrid_lr, "tv_end": float(self.grids.tv_loss()),
                                        "max_abs_from_identity": [float(a) for a in away.cpu()],
                                        "checksum": float(g.double().sum())}}
+
+
+def _normal_record(cfg: TrainConfig, run_step) -> Dict:
+    """The record's "normal_consistency" entry: the term (before `normal_lambda`) at the first and the last step that
+    had it; None where the run ended before `normal_start_iteration`."""
+    terms = [float(t) for t in run_step.normal_terms]
+    return {"normal_consistency": {"lambda": cfg.normal_lambda, "start_iteration": cfg.normal_start_iteration,
+                                   "term_first": terms[0] if terms else None,
+                                   "term_last": terms[-1] if terms else None}}
 
 
 def make_bilagrid(cfg: TrainConfig, device) -> Optional[BilagridGroup]:
@@ -1591,6 +1654,7 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
     _check_absgrad(cfg, device)
     _check_mcmc(cfg, device, world)
     _check_bilateral_grid(cfg, device, world)
+    _check_normal_consistency(cfg, device, world)
     cuda = device.type == "cuda"
     mcfg = None
     if cfg.strategy == "mcmc":
@@ -1753,7 +1817,8 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
            "overflow_views": run_step.overflow_views + (_list_rebuilds() - rebuilds0),
            "pose": pose_record(camera, pose0, pose1),
            "appearance": {**({} if bilagrid is None else bilagrid.record()),
-                          **({} if data.exposure is None else {"view_exposure": data.exposure})},
+                          **({} if data.exposure is None else {"view_exposure": data.exposure}),
+                          **(_normal_record(cfg, run_step) if cfg.normal_consistency else {})},
            "update": "reduce-scatter + sharded Adam + all-gather" if sharded is not None else
            ("all-reduce (geometry) + all-gathered colour cotangents (SH) + Adam" if sh_views else "all-reduce + Adam")}
     return result_record(cfg, device, world, model, run, eval0, eval1, phase_record(run_step.marks, cfg, data.factors))

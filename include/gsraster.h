@@ -1531,6 +1531,73 @@ int gsr_bilagrid_tv_backward(int num_views, int grid_w, int grid_h, int grid_l,
                              const float *upstream, const float *grids, float *v_grids,
                              gsr_stream_t stream);
 
+/* ---- normal maps and the depth-normal consistency loss (csrc/normals.hip) ------
+ * What surface-oriented training (2DGS, GOF, RaDe-GS, PGSR, gsplat's `normal_lambda`) adds: a
+ * normal per Gaussian, composited into a normal image; a second normal image derived from the
+ * rendered depth; their disagreement as a loss.  Camera space is the projection's: x right,
+ * y down, z forward.  The centre of pixel (row i, column j) is (j + 0.5, i + 0.5).
+ *
+ * Per-Gaussian normals.  quats float [N,4] as (w,x,y,z), raw (normalised inside), 16-byte
+ * aligned; scales float [N,3], of which only the order is used (log-scales and their exp give
+ * the same result); means float [N,3]; viewmat float [12], row-major 3x4, on the device.
+ *   axis    = the index of the smallest scale; on a tie the lowest index wins
+ *   n_cam   = viewmat[:, :3] . (column `axis` of R(q / |q|))
+ *   p_cam   = viewmat[:, :3] . mean + viewmat[:, 3]
+ *   sign    = -1 where n_cam . p_cam > 0, else +1        (the normal faces the camera)
+ *   normals = sign n_cam            float [N,3];   axis int [N];   sign float [N] (+-1)
+ * Backward, from v_normals: v_quats float [N,4] through the rotation column and the
+ * normalisation, (v - qn (qn . v)) / |q|.  axis and sign are piecewise constant: scales, means
+ * and viewmat get no gradient.  N = 0 launches nothing; 4 N < 2^31.
+ *
+ * Depth normals.  depth, alpha float [H,W]; fx, fy, cx, cy the intrinsics (doubles).
+ *   P(i,j) = ((j + 0.5 - cx) / fx * D, (i + 0.5 - cy) / fy * D, D),  D = depth[i][j]
+ *   u = P(i+1,j) - P(i-1,j)    v = P(i,j+1) - P(i,j-1)    n_d = (u x v) / |u x v|
+ * which is (0,0,-1) for a fronto-parallel plane: it faces the camera like the normals above.  A
+ * pixel is invalid, and its n_d an exact zero, if it is on the image's one-pixel border, or it
+ * or one of its four neighbours has alpha <= 0 or a depth that is not finite (the test is on
+ * alpha: the models fill alpha == 0 pixels with depth.max()), or |u x v|^2 is zero or not finite.
+ *   normals  float [H,W,3]; every element written
+ *
+ * Consistency loss.  normals_img float [H,W,3]: the alpha-blended, un-normalised rendered
+ * normals; mask float [H,W] or NULL.
+ *   loss = (1 / (H W)) sum over ALL pixels p of m(p) (1 - alpha(p) <normals_img(p), n_d(p)>)
+ * (2DGS / gsplat: 1 - (normals * normals_from_depth * alpha.detach()).sum(-1), as a mean; the
+ * mask is multiplied in and the mean stays over all pixels; an invalid pixel adds m(p)).
+ * Backward, with s = -upstream / (H W):
+ *   v_normals_img(p) = s m(p) alpha(p) n_d(p)
+ *   v_depth(q)       = the sum over q's four neighbours p of the term of n_d(p) that holds
+ *                      depth(q): with g = s m alpha normals_img at p, c = u x v,
+ *                      dc = (g - n_d (n_d . g)) / |c|, du = v x dc, dv = dc x u, r_q the ray of q:
+ *                      <du(above q), r_q> - <du(below q), r_q> + <dv(left of q), r_q> - <dv(right of q), r_q>
+ *                      -- a gather, no scatter; an exact zero where no neighbour is valid
+ * alpha is a weight: no gradient.  `upstream` (float [1]) is read on the device.  Arithmetic is
+ * float64 per pixel, rounded to float32 on the way out; the sum over pixels is float64 in a fixed
+ * order (lane, wave, workgroup, then the tiles' partials in one workgroup), without atomics: two
+ * runs are bit-equal.  Every element of every output is written.  3 H W < 2^31.
+ *   partial  double [GSR_NORMAL_WORKSPACE_DOUBLES(H, W)]; needs no zeroing */
+#define GSR_NORMAL_TILE 16
+#define GSR_NORMAL_WORKSPACE_DOUBLES(h, w)                                   \
+  ((size_t)(((h) + GSR_NORMAL_TILE - 1) / GSR_NORMAL_TILE) *                  \
+   (size_t)(((w) + GSR_NORMAL_TILE - 1) / GSR_NORMAL_TILE))
+int gsr_gaussian_normals_forward(int num_points, const float *quats, const float *scales,
+                                 const float *means, const float *viewmat, float *normals,
+                                 int *axis, float *sign, gsr_stream_t stream);
+int gsr_gaussian_normals_backward(int num_points, const float *quats, const float *viewmat,
+                                  const int *axis, const float *sign, const float *v_normals,
+                                  float *v_quats, gsr_stream_t stream);
+int gsr_depth_normals(unsigned img_height, unsigned img_width, double fx, double fy, double cx,
+                      double cy, const float *depth, const float *alpha, float *normals,
+                      gsr_stream_t stream);
+int gsr_normal_consistency_forward(unsigned img_height, unsigned img_width, double fx, double fy,
+                                   double cx, double cy, const float *normals_img,
+                                   const float *depth, const float *alpha, const float *mask,
+                                   double *partial, float *loss_out, gsr_stream_t stream);
+int gsr_normal_consistency_backward(unsigned img_height, unsigned img_width, double fx, double fy,
+                                    double cx, double cy, const float *upstream,
+                                    const float *normals_img, const float *depth,
+                                    const float *alpha, const float *mask, float *v_normals_img,
+                                    float *v_depth, gsr_stream_t stream);
+
 /* ---- k nearest neighbours: points against a point cloud ----------------
  * What the toolkit's models ask scikit-learn for when they turn seed points into initial scales
  * (`k_nearest_sklearn`, vanilla_gs.py:136-140, 260-280), as a general query.  Reference points P

@@ -3,7 +3,8 @@
 
     python tools/train_dataset.py DATA [--model gaussian-splatting|co-gs] [--iters 30000] [--output-dir outputs]
         [--eval-mode fraction|filename|interval|all] [--fused-render] [--use-graph] [--camera-optimizer SO3xR3]
-        [--strategy default|mcmc [--cap-max 1000000]] [--bilateral-grid [--bilagrid-shape X Y L]] ...
+        [--strategy default|mcmc [--cap-max 1000000]] [--bilateral-grid [--bilagrid-shape X Y L]]
+        [--normal-consistency [--normal-lambda 0.05] [--normal-start 7000]] ...
 
 `harness.train.train` with `TrainConfig.dataset`: the files are uploaded as integers into a
 gs_fused.ImageCache and every step's target comes from one kernel.  Writes `OUTPUT_DIR/step-*.ckpt` (the toolkit's
@@ -43,6 +44,11 @@ def parse_args(argv=None):
                     help="per-view bilateral grids between the render and the loss (exposure, white balance); not with "
                          "--use-graph")
     ap.add_argument("--bilagrid-shape", type=int, nargs=3, default=[16, 16, 8], metavar=("X", "Y", "L"))
+    ap.add_argument("--normal-consistency", action="store_true",
+                    help="depth-normal consistency loss (a third compositing pass for the normal image); not with "
+                         "--fused-render or --use-graph")
+    ap.add_argument("--normal-lambda", type=float, default=0.05)
+    ap.add_argument("--normal-start", type=int, default=7000, help="the term joins the loss after this iteration")
     ap.add_argument("--depth-loss-start-iteration", type=int, default=6000)
     ap.add_argument("--save-every", type=int, default=2000)
     ap.add_argument("--seed", type=int, default=0)
@@ -78,6 +84,7 @@ def main(argv=None):
         resolution_schedule=a.resolution_schedule, background_color=a.background_color, densify=not a.no_densify,
         fused_render=a.fused_render, use_graph=a.use_graph, camera_optimizer=a.camera_optimizer,
         bilateral_grid=a.bilateral_grid, bilagrid_shape=tuple(a.bilagrid_shape),
+        normal_consistency=a.normal_consistency, normal_lambda=a.normal_lambda, normal_start_iteration=a.normal_start,
         depth_loss_start_iteration=a.depth_loss_start_iteration, checkpoint_dir=a.output_dir, save_every=save_every,
         seed=a.seed, means_lr_schedule=True, log_every=max(a.iters // 100, 1),
         dataset_eval_mode=a.eval_mode, dataset_train_split_fraction=a.train_split_fraction,
