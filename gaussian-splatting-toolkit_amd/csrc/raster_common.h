@@ -41,12 +41,24 @@ struct Reach {
   float smax;        // sigma bound: +inf = always keep, < 0 = can never reach
 };
 
+// a c - b^2 of a conic to within an ulp or two of its exact value (Kahan's difference of products: the rounding error
+// of b b, exact through one fma, is taken back out).  The plain float32 expression keeps no digit of a needle's
+// determinant -- a c and b^2 agree to 1 part in a c / D, 1e6 and more for a long thin splat at an angle -- and the
+// half extents of {sigma <= smax} go with 1 / sqrt(D): 6 % too large a D put a live tile 3 % of the extent outside
+// its row interval (tile_rows.h row_range), far beyond the interval's 1e-3 margin
+// (tests/test_gpu_reach.py::test_lists_on_a_large_grid).
+__device__ __forceinline__ float conic_det(float a, float b, float c) {
+  const float w = __fmul_rn(b, b);
+  const float e = __fmaf_rn(b, b, -w);  // b b = w + e exactly
+  return __fsub_rn(__fmaf_rn(a, c, -w), e);
+}
+
 __device__ __forceinline__ Reach make_reach(float x, float y, float a, float b, float c, float opac) {
   Reach r{x, y, a, b, c, 0.f, 0.f, 0.f};
   // alpha >= 1/255  <=>  sigma <= log(255*opac)
   r.smax = __logf(255.f * opac) + 0.01f;
   if (!(r.smax >= 0.f)) r.smax = (opac == opac) ? -1.f : INFINITY;  // too faint anywhere (NaN: keep)
-  if (!(a > 0.f && c > 0.f && a * c - b * b > 0.f)) {
+  if (!(a > 0.f && c > 0.f && conic_det(a, b, c) > 0.f)) {
     r.smax = INFINITY;  // not positive definite: no culling
   } else {
     r.nb_c = -b / c;

@@ -86,7 +86,7 @@ struct RowParams {
 __device__ __forceinline__ RowParams make_row_params(const SplatRec &r) {
   RowParams p{1.f, 0.f, 0.f, 0.f};
   if (r.smax >= 0.f && r.smax != INFINITY) {
-    p.D = r.a * r.c - r.b * r.b;  // > 0 (make_reach sets smax = inf otherwise)
+    p.D = gsr::conic_det(r.a, r.b, r.c);  // > 0 (make_reach sets smax = inf otherwise); exact to an ulp or two
     const float t = 2.f * r.smax / p.D;
     p.umax = sqrtf(t * r.c);
     p.vmax = sqrtf(t * r.a);
@@ -104,7 +104,9 @@ __device__ __forceinline__ RowParams make_row_params(const SplatRec &r) {
 // by 1e-3 of the ellipse's extent + 0.05 px against rounding in the square roots.
 // The compositing kernels re-test per sub-tile / pixel, so keeping a dead pair is
 // harmless; dropping a live one is what the margins exclude
-// (tests/test_gpu_kernels.py::test_exact_lists_drop_only_dead_pairs).
+// (tests/test_gpu_kernels.py::test_exact_lists_drop_only_dead_pairs on random scenes; tests/test_gpu_reach.py
+// against float64 on splats built to graze a tile or a sub-tile, tests/test_reach_host.py for what those inputs
+// are worth).  The margins cover rounding, not cancellation: D comes from conic_det.
 __device__ __forceinline__ void row_range(const SplatRec &r, const RowParams &p, int ty, int &t0, int &t1) {
   const int minx = (int)(r.box0 & 0xffffu), bwid = (int)(r.box1 & 0xffffu);
   t0 = minx;
