@@ -19,3 +19,4 @@ from .knn import KNN, initial_log_scales, k_nearest, knn, knn_mean_distance  # n
 from .target import DeferredTarget, ImageCache, plane_from_int, target_from_u8  # noqa: F401
 from .bilagrid import BilateralGrids, bilagrid_slice, bilagrid_tv_loss  # noqa: F401
 from .normals import depth_to_normal, gaussian_normals, normal_consistency_loss  # noqa: F401
+from .distortion import depth_distortion, distortion_loss  # noqa: F401

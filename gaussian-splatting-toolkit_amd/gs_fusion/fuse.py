@@ -68,7 +68,7 @@ def export_mask(mask, bounding_box: bool = False, margin: int = 5) -> Tensor:
 def fuse_views(volume: TSDFVolume, params: Dict[str, Tensor], cameras: Sequence[Camera], background: Tensor,
                sh_degree: int, alpha_min: float = 0.5, depth_trunc: float = 10.0, masks: Optional[Sequence] = None,
                bounding_box: bool = False, mask_margin: int = 5, rasterize_mode: str = "classic",
-               crop_box=None) -> None:
+               crop_box=None, depth_mode: str = "expected") -> None:
     """Render RGB + depth from every camera (`render_view(render_depth=True, fused_depth=True)`: one compositing
     pass) and integrate it into `volume`.  `params`: activated `means3d`, `scales`, `quats`, `opacities`,
     `sh_coeffs` on the volume's device; `cameras`: `harness.scene.Camera` (host arrays).
@@ -85,12 +85,24 @@ def fuse_views(volume: TSDFVolume, params: Dict[str, Tensor], cameras: Sequence[
     that separates an object from what stands behind it, which 2-D masks cannot.  A box that keeps nothing fuses
     nothing.
 
+    `depth_mode`: which depth of a view is fused.  "expected" (the default, what the toolkit fuses): the alpha-blended
+    depth, `depth_acc / alpha`.  At a silhouette that is a blend of foreground and background, which the fusion turns
+    into a skirt of false surface between the two.  "median": the depth of the Gaussian at which the transmittance
+    crosses 0.5 (`render_view(render_distortion=True)`'s "median_depth", gs_fused.depth_distortion) -- one Gaussian's
+    depth or the other's, never a blend; what 2DGS, GOF, RaDe-GS and PGSR fuse.  It is valid where `alpha >= alpha_min`
+    like the expected depth: with the default 0.5 these are exactly the pixels at which the crossing happened
+    (alpha >= 0.5 is final T <= 0.5); with a smaller `alpha_min` the remaining pixels carry the depth of their last
+    contributing Gaussian.  Masks, crop box and `rasterize_mode` apply as before.  Anything else raises ValueError.
+
     Everything stays on the device as float32: there is NO round trip through 8-bit colour PNG and 16-bit millimetre
     depth PNG files as in the toolkit's file-based route, hence none of their quantisation -- a deliberate difference;
     and the host is not synchronised between views."""
     dev = volume.device
     if rasterize_mode not in ("classic", "antialiased"):
         raise ValueError("Unknown rasterize_mode: %s" % rasterize_mode)
+    if depth_mode not in ("expected", "median"):
+        raise ValueError("Unknown depth_mode: %s (expected or median)" % (depth_mode,))
+    median_kw = {"render_distortion": True} if depth_mode == "median" else {}
     # (a CropBox goes to the device once, not once per view; anything else is `render_view`'s to check)
     crop = crop_box.tensor(dev) if isinstance(crop_box, CropBox) else crop_box
     keeps = None
@@ -108,8 +120,11 @@ def fuse_views(volume: TSDFVolume, params: Dict[str, Tensor], cameras: Sequence[
             out = render_view(params["means3d"], params["scales"], params["quats"], params["opacities"],
                               params["sh_coeffs"], CameraTensors.from_numpy(cam, dev), background, sh_degree,
                               rasterize_mode=rasterize_mode, render_depth=True, fused_depth=True,
-                              normalise_depth=False, crop=crop)
+                              normalise_depth=False, crop=crop, **median_kw)
             depth, valid = view_depth(out["depth_acc"], out["alpha"], alpha_min)
+            if median_kw:
+                H, W = valid.shape
+                depth = torch.where(valid.bool(), out["median_depth"].reshape(H, W), torch.zeros_like(depth)).contiguous()
             if keeps is not None:
                 valid = valid & keeps[i]
             volume.integrate(depth, out["rgb"].contiguous(), cam.fx, cam.fy, cam.cx, cam.cy, cam.viewmat, valid=valid,

@@ -84,6 +84,14 @@ def render_view(
                                    # cache holds for this view.  Its gradient reaches `quats`, the opacities, the
                                    # conics and -- like every loss in 2DGS -- `xys`: it JOINS `xys.grad`, so the
                                    # densification statistics see the normal term as well.  CUDA tensors only
+    render_distortion: bool = False,  # together with `render_depth`: `out["distortion"]` and `out["median_depth"]`
+                                      # [H,W,1] (gs_fused.depth_distortion: the Mip-NeRF-360 distortion term per pixel
+                                      # and the value at which the transmittance crosses 0.5) -- one more walk over
+                                      # the cached tile lists.  The distortion's gradient reaches the opacities, the
+                                      # conics, `distortion_values` and `xys` (it JOINS `xys.grad`); the median has
+                                      # none.  CUDA tensors only, not in deterministic mode
+    distortion_values=None,  # the scalar per Gaussian the two are formed from: None, the projection's `depths`; a tensor
+                             # [N]; or a function `depths -> [N]` (a monotone map, whose gradient reaches the depths)
 ) -> Dict[str, Optional[torch.Tensor]]:
     H, W = cam.height, cam.width
     if caller_syncs == "camera" and cam.scalars is not None:
@@ -118,7 +126,9 @@ def render_view(
         return {"rgb": rgb, "alpha": background.new_zeros(H, W, 1), "depth": background.new_ones(H, W, 1) * 10,
                 "depth_acc": background.new_zeros(H, W, 1), "xys": xys, "radii": radii, "depths": depths, "conics": conics,
                 "num_tiles_hit": num_tiles_hit, "rgbs": None,
-                **({"normals": background.new_zeros(H, W, 3)} if render_normals and render_depth else {})}
+                **({"normals": background.new_zeros(H, W, 3)} if render_normals and render_depth else {}),
+                **({"distortion": background.new_zeros(H, W, 1), "median_depth": background.new_zeros(H, W, 1)}
+                   if render_distortion and render_depth else {})}
     if retain_xys_grad and xys.requires_grad:
         xys.retain_grad()  # densification reads xys.grad (vanilla_gs.py:352-353,797-798)
 
@@ -192,5 +202,13 @@ def render_view(
         normals_kw["normals"] = rasterize_gaussians(
             xys, depths, radii, conics, num_tiles_hit, gaussian_normals(quats, scales, means3d, cam.viewmat[:3, :]), opac,
             H, W, BLOCK_WIDTH, background=torch.zeros(3, device=means3d.device))
+    if render_distortion and render_depth:
+        from gs_fused import depth_distortion
+
+        dist, median = depth_distortion(xys, depths, radii, conics, num_tiles_hit,
+                                        depths if distortion_values is None else
+                                        distortion_values(depths) if callable(distortion_values) else distortion_values,
+                                        opac, H, W)
+        normals_kw["distortion"], normals_kw["median_depth"] = dist[..., None], median[..., None]
     return {"rgb": rgb, "alpha": alpha, "depth": depth_im, "depth_acc": depth_acc, "xys": xys, "radii": radii,
             "depths": depths, "conics": conics, "num_tiles_hit": num_tiles_hit, "rgbs": rgbs, **normals_kw}

@@ -298,7 +298,8 @@ class GaussianParams(torch.nn.Module):
 
     def render(self, cam: CameraTensors, background, sh_degree_to_use: int, render_depth=False,
                retain_xys_grad=False, clamp_rgb=True, sh_exchange=None, caller_syncs=False, fused_depth=False,
-               normalise_depth=True, rasterize_mode="classic", absgrad=False, render_normals=False):
+               normalise_depth=True, rasterize_mode="classic", absgrad=False, render_normals=False,
+               render_distortion=False, distortion_values=None):
         g = self.gauss
         if self.split_sh and g["features_dc"].is_cuda and g["features_rest"].shape[1] in (3, 8, 15):
             coeffs = (g["features_dc"], g["features_rest"])  # gs_fused.spherical_harmonics_split
@@ -318,6 +319,8 @@ class GaussianParams(torch.nn.Module):
                            clamp_rgb=clamp_rgb, caller_syncs=caller_syncs, fused_depth=fused_depth,
                            normalise_depth=normalise_depth, rasterize_mode=rasterize_mode, absgrad=absgrad,
                            **({"render_normals": True} if render_normals else {}),
+                           **({"render_distortion": True, "distortion_values": distortion_values}
+                              if render_distortion else {}),
                            sh_exchange=None if sh_exchange is None else (
                                sh_exchange, ("features_dc", "features_rest"), (g["features_dc"], g["features_rest"])))
 
@@ -555,6 +558,22 @@ class TrainConfig:
     normal_consistency: bool = False
     normal_lambda: float = 0.05
     normal_start_iteration: int = 7000
+    # depth distortion (gs_fused.depth_distortion; 2DGS's `lambda_dist`, gsplat's `distloss`):
+    # `distortion_lambda` times the mean over all pixels of sum_i sum_j w_i w_j |z_i - z_j| joins the loss from
+    # `step > distortion_start_iteration`, with the view's mask; it pulls the Gaussians along a ray onto one surface.
+    # z is 2DGS's map of the depth, far / (far - near) (1 - near / depth), formed by torch ops on [N] so that its
+    # gradient reaches the depths (and the means) by autograd; `distortion_near = distortion_far = None` passes the raw
+    # depths.  The four defaults are 2DGS's (`lambda_dist` 100 as its README advises for bounded scenes, the term from
+    # iteration 3000, near 0.2 and far 100 of its rasterizer) as recalled -- 2DGS was not at hand to check them against;
+    # they are the defaults of an opt-in, not claims.  A step that has the term renders the depth image as well, as
+    # with `normal_consistency`; a step before the start is the step it always was.  The separate ops on one GPU:
+    # `fused_render`, `use_graph`, a world size above 1, CPU tensors and deterministic mode are refused.  Off: nothing
+    # changes.
+    depth_distortion: bool = False
+    distortion_lambda: float = 100.0
+    distortion_start_iteration: int = 3000
+    distortion_near: Optional[float] = 0.2
+    distortion_far: Optional[float] = 100.0
     # (sigma of the log-gain, sigma of the bias): every synthetic training target is multiplied once by a per-view,
     # per-channel gain exp(N(0, sigma_gain)) and shifted by N(0, sigma_bias), drawn from `view_exposure_seed`, standing
     # in for auto-exposure and white balance (a random background: the RGBA ground truth's colour is disturbed, its
@@ -722,6 +741,34 @@ def _check_normal_consistency(cfg: TrainConfig, device, world: int) -> None:
                          "data-parallel run are not exchanged")
     if device.type != "cuda":
         raise ValueError("normal_consistency needs CUDA tensors: the normals and the loss head are HIP kernels")
+
+
+def _check_depth_distortion(cfg: TrainConfig, device, world: int) -> None:
+    """What `depth_distortion` refuses, once the device and the world size are known."""
+    if not cfg.depth_distortion:
+        return
+    if cfg.fused_render:
+        raise ValueError("depth_distortion needs the separate-ops path: the one-node view (fused_render) holds no "
+                         "distortion walk")
+    if cfg.use_graph:
+        raise ValueError("depth_distortion does not run under use_graph: the captured view holds no distortion walk, "
+                         "and the term joins at a step of the schedule")
+    if world > 1:
+        raise ValueError("depth_distortion runs on one GPU (world size 1): the walk's gradients of a data-parallel run "
+                         "are not exchanged")
+    if device.type != "cuda":
+        raise ValueError("depth_distortion needs CUDA tensors: the walk is a pair of HIP kernels")
+    if (cfg.distortion_near is None) != (cfg.distortion_far is None):
+        raise ValueError("depth_distortion: distortion_near and distortion_far are both numbers or both None")
+    if cfg.distortion_near is not None and not (0.0 < cfg.distortion_near < cfg.distortion_far):
+        raise ValueError(f"depth_distortion: need 0 < distortion_near < distortion_far, got {cfg.distortion_near} and "
+                         f"{cfg.distortion_far}")
+    import sys
+
+    mod = sys.modules.get("rasterizer.rasterize")  # (absent: CPU stand-ins, refused above)
+    if mod is not None and mod.is_deterministic():
+        raise ValueError("depth_distortion does not run in deterministic mode: the walk's backward sums with float "
+                         "atomics")
 
 
 def _params(model: GaussianParams) -> Dict[str, torch.nn.Parameter]:
@@ -1365,6 +1412,23 @@ class SeparateStep:
         # the depth image it needs, from the one RGB + depth compositing pass (co-gs renders depth anyway and keeps its
         # own choice of the pass and of `normalise_depth`).  A step without the term renders what it always did
         self.normal_kw = dict(render_normals=True, **({} if cogs else dict(render_depth=True, fused_depth=cuda)))
+        self.distortion_terms = []  # depth_distortion: likewise
+        self.distortion_kw = dict(render_distortion=True, distortion_values=self._distortion_values,
+                                  **({} if cogs else dict(render_depth=True, fused_depth=cuda)))
+
+    def _distortion_values(self, depths):
+        """2DGS's map of the depths onto [0, far / (far - near)), differentiable; the raw depths without a range."""
+        near, far = self.cfg.distortion_near, self.cfg.distortion_far
+        if near is None:
+            return depths
+        return (far / (far - near)) * (1.0 - near / depths)
+
+    def _distortion_term(self, out, mask):
+        from gs_fused import distortion_loss
+
+        term = distortion_loss(out["distortion"], mask=mask)
+        self.distortion_terms = self.distortion_terms[:1] + [term.detach()]
+        return self.cfg.distortion_lambda * term
 
     def _normal_term(self, out, cam, mask):
         """`normal_lambda` times the depth-normal consistency of the view (gs_fused.normal_consistency_loss).  Where the
@@ -1386,7 +1450,13 @@ class SeparateStep:
         if ph:
             ph[0].record()
         normals_on = self.cfg.normal_consistency and step > self.cfg.normal_start_iteration
-        out = self.model.render(cam, bg, deg, **({**self.render_kw, **self.normal_kw} if normals_on else self.render_kw))
+        distortion_on = self.cfg.depth_distortion and step > self.cfg.distortion_start_iteration
+        kw = self.render_kw
+        if normals_on:
+            kw = {**kw, **self.normal_kw}
+        if distortion_on:
+            kw = {**kw, **self.distortion_kw}
+        out = self.model.render(cam, bg, deg, **kw)
         if ph:
             ph[1].record()
         if self.bilagrid is None:
@@ -1406,6 +1476,8 @@ class SeparateStep:
             loss = _add_mcmc_regulariser(loss, self.model, self.mcfg)
         if normals_on:
             loss = loss + self._normal_term(out, cam, mask)
+        if distortion_on:
+            loss = loss + self._distortion_term(out, mask)
         if ph:
             ph[2].record()
         loss.backward()
@@ -1496,6 +1568,16 @@ def _normal_record(cfg: TrainConfig, run_step) -> Dict:
     return {"normal_consistency": {"lambda": cfg.normal_lambda, "start_iteration": cfg.normal_start_iteration,
                                    "term_first": terms[0] if terms else None,
                                    "term_last": terms[-1] if terms else None}}
+
+
+def _distortion_record(cfg: TrainConfig, run_step) -> Dict:
+    """The record's "depth_distortion" entry: the term (before `distortion_lambda`) at the first and the last step that
+    had it; None where the run ended before `distortion_start_iteration`."""
+    terms = [float(t) for t in run_step.distortion_terms]
+    return {"depth_distortion": {"lambda": cfg.distortion_lambda, "start_iteration": cfg.distortion_start_iteration,
+                                 "near": cfg.distortion_near, "far": cfg.distortion_far,
+                                 "term_first": terms[0] if terms else None,
+                                 "term_last": terms[-1] if terms else None}}
 
 
 def make_bilagrid(cfg: TrainConfig, device) -> Optional[BilagridGroup]:
@@ -1655,6 +1737,7 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
     _check_mcmc(cfg, device, world)
     _check_bilateral_grid(cfg, device, world)
     _check_normal_consistency(cfg, device, world)
+    _check_depth_distortion(cfg, device, world)
     cuda = device.type == "cuda"
     mcfg = None
     if cfg.strategy == "mcmc":
@@ -1818,7 +1901,8 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
            "pose": pose_record(camera, pose0, pose1),
            "appearance": {**({} if bilagrid is None else bilagrid.record()),
                           **({} if data.exposure is None else {"view_exposure": data.exposure}),
-                          **(_normal_record(cfg, run_step) if cfg.normal_consistency else {})},
+                          **(_normal_record(cfg, run_step) if cfg.normal_consistency else {}),
+                          **(_distortion_record(cfg, run_step) if cfg.depth_distortion else {})},
            "update": "reduce-scatter + sharded Adam + all-gather" if sharded is not None else
            ("all-reduce (geometry) + all-gathered colour cotangents (SH) + Adam" if sh_views else "all-reduce + Adam")}
     return result_record(cfg, device, world, model, run, eval0, eval1, phase_record(run_step.marks, cfg, data.factors))

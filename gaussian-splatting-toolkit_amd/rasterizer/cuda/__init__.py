@@ -1382,3 +1382,72 @@ def compute_cov2d_bounds(num_pts: int, cov2d: Tensor) -> Tuple[Tensor, Tensor]:
         radii = torch.empty((n, 1), dtype=_f32, device=dev)
         _call("gsr_cov2d_bounds", n, cov2d, conics, radii, _stream(dev))
     return conics, radii
+
+
+def _distortion_inputs(gaussian_ids_sorted, tile_bins, xys, conics, opacities, values):
+    _check(gaussian_ids_sorted, "gaussian_ids_sorted", _i32)
+    _check(tile_bins, "tile_bins", _i32)
+    for t, nm in ((xys, "xys"), (conics, "conics"), (opacities, "opacities"), (values, "values")):
+        _check(t, nm, _f32)
+    n = xys.size(0)
+    if xys.dim() != 2 or xys.size(1) != 2:
+        raise RuntimeError("xys must have dimensions (num_points, 2)")
+    if tuple(conics.shape) != (n, 3) or opacities.numel() != n or values.numel() != n:
+        raise RuntimeError("conics, opacities and values must hold 3, 1 and 1 value per point of xys")
+    for t, nm in ((gaussian_ids_sorted, "gaussian_ids_sorted"), (tile_bins, "tile_bins"), (conics, "conics"),
+                  (opacities, "opacities"), (values, "values")):
+        if t.device != xys.device:
+            raise RuntimeError(f"{nm} must be on the device of xys")
+
+
+def distortion_forward(tile_bounds, img_size, gaussian_ids_sorted, tile_bins, xys, conics, opacities, values):
+    """The depth-distortion walk on given single-segment lists of 16 x 16 tiles (``gsr_distortion_forward``)
+    -> (distortion, median, vsum, final_Ts [H,W] float32, final_idx [H,W] int32).  ``values`` [N]: one scalar per
+    Gaussian.  A view without list entries launches nothing: zeros, final_Ts = 1, final_idx = -1."""
+    W, H = int(img_size[0]), int(img_size[1])
+    if W < 1 or H < 1:
+        raise RuntimeError("distortion_forward: empty image")
+    if tuple(int(v) for v in tile_bounds[:2]) != ((W + 15) // 16, (H + 15) // 16):
+        raise RuntimeError(f"distortion_forward: tile bounds {tuple(tile_bounds)} are not those of a {W} x {H} image in "
+                           f"16 x 16 tiles")
+    dev = xys.device
+    if gaussian_ids_sorted is None or gaussian_ids_sorted.numel() == 0:
+        with _on(dev):
+            z = torch.zeros((3, H, W), dtype=_f32, device=dev)
+            return (z[0], z[1], z[2], torch.ones((H, W), dtype=_f32, device=dev),
+                    torch.full((H, W), -1, dtype=_i32, device=dev))
+    _distortion_inputs(gaussian_ids_sorted, tile_bins, xys, conics, opacities, values)
+    if tile_bins.numel() < 2 * tile_bounds[0] * tile_bounds[1]:
+        raise RuntimeError("tile_bins must hold one (start, end) pair per tile")
+    with _on(dev):
+        planes = torch.empty((4, H, W), dtype=_f32, device=dev)
+        final_idx = torch.empty((H, W), dtype=_i32, device=dev)
+        _call("gsr_distortion_forward", tile_bounds[0], tile_bounds[1], W, H, gaussian_ids_sorted, tile_bins, xys, conics,
+              opacities, values, planes[0], planes[1], planes[2], planes[3], final_idx, _stream(dev))
+    return planes[0], planes[1], planes[2], planes[3], final_idx
+
+
+def distortion_backward(img_height, img_width, gaussian_ids_sorted, tile_bins, xys, conics, opacities, values, vsum,
+                        final_Ts, final_idx, v_distortion):
+    """-> (v_xy [N,2], v_conic [N,3], v_opacity [N], v_values [N]) of `distortion_forward` (``gsr_distortion_backward``;
+    float atomics).  A view without list entries launches nothing: zeros."""
+    H, W = int(img_height), int(img_width)
+    n, dev = xys.size(0), xys.device
+    with _on(dev):
+        if gaussian_ids_sorted is None or gaussian_ids_sorted.numel() == 0 or n == 0:
+            flat = torch.zeros((7 * n,), dtype=_f32, device=dev)
+        else:
+            _distortion_inputs(gaussian_ids_sorted, tile_bins, xys, conics, opacities, values)
+            for t, nm, dt in ((vsum, "vsum", _f32), (final_Ts, "final_Ts", _f32), (final_idx, "final_idx", _i32)):
+                if tuple(_check(t, nm, dt).shape) != (H, W) or t.device != dev:
+                    raise RuntimeError(f"{nm} must have dimensions ({H}, {W}) on the device of xys")
+            v_distortion = _check(v_distortion.contiguous(), "v_distortion", _f32)
+            if v_distortion.numel() != H * W or v_distortion.device != dev:
+                raise RuntimeError(f"v_distortion must hold {H} x {W} values on the device of xys")
+            if tile_bins.numel() < 2 * ((W + 15) // 16) * ((H + 15) // 16):
+                raise RuntimeError("tile_bins must hold one (start, end) pair per tile")
+            flat = torch.empty((7 * n,), dtype=_f32, device=dev)  # (cleared by the entry: one fill)
+            _call("gsr_distortion_backward", H, W, n, gaussian_ids_sorted, tile_bins, xys, conics, opacities, values,
+                  vsum, final_Ts, final_idx, v_distortion, flat[:2 * n], flat[2 * n:5 * n], flat[5 * n:6 * n],
+                  flat[6 * n:], _stream(dev))
+    return flat[:2 * n].view(n, 2), flat[2 * n:5 * n].view(n, 3), flat[5 * n:6 * n], flat[6 * n:]

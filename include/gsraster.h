@@ -1598,6 +1598,48 @@ int gsr_normal_consistency_backward(unsigned img_height, unsigned img_width, dou
                                     const float *alpha, const float *mask, float *v_normals_img,
                                     float *v_depth, gsr_stream_t stream);
 
+/* ---- depth distortion and median depth (csrc/distortion.hip) -----------
+ * The Mip-NeRF-360 distortion term per pixel (2DGS, gsplat's `distloss`) and the depth at which
+ * the transmittance crosses 0.5 (`render_mode="...+median"`), from one front-to-back walk of its
+ * own over single-segment tile lists (ids int32 [I], bins int32 [tiles,2]; block width 16).
+ * values float [N]: one scalar per Gaussian -- the depths, or a monotone map of them.
+ *
+ * The walk is the forward compositing's: pixel centre = the integer pixel coordinate,
+ * sigma = (a dx^2 + c dy^2) / 2 + b dx dy, alpha = min(0.999, opac exp(-sigma)); an entry with
+ * sigma < 0 or alpha < 1/255 is skipped; the walk stops BEFORE the entry that would make
+ * T (1 - alpha) <= 1e-4.  For the contributing entries i = 1..n in list order, T_i the
+ * transmittance before entry i, w_i = alpha_i T_i, A_i = 1 - T_{i+1}, B_i = sum_{j<=i} w_j z_j:
+ *   out_distortion = 2 sum_i w_i (z_i A_{i-1} - B_{i-1})
+ *                    (= sum_i sum_j w_i w_j |z_i - z_j| where z does not decrease along the list)
+ *   out_median     = z_i of the last contributing entry with T_i > 0.5; 0 where none contributes
+ *   out_vsum = B_n, final_Ts = T_{n+1}, final_idx = the list index of entry n, or -1
+ * All five are float/int32 [H,W]; every element is written; a tile with an empty list gets
+ * zeros, final_Ts = 1 and final_idx = -1.
+ *
+ * Backward, from v_distortion float [H,W] (the median carries no gradient): the gradient of what
+ * the forward computes -- the same clamp 0.999.  Back to front from final_idx, T_k by division,
+ * B_{k-1} = B_k - w_k z_k, S = sum_{i>k} w_i g_i:
+ *   g_k        = 2 [z_k A_{k-1} - B_{k-1} + (B_n - B_k) - z_k (A_n - A_k)]
+ *   dD/dz_k    = 2 w_k [A_{k-1} - (A_n - A_k)]
+ *   dD/dalpha_k = T_k g_k - S / (1 - alpha_k), and 0 where opac exp(-sigma) > 0.999 (clamped)
+ *   v_sigma = -opac vis dD/dalpha_k v_distortion, into v_xy / v_conic as in the compositing backward;
+ *   v_opacity += vis dD/dalpha_k v_distortion;  v_values += dD/dz_k v_distortion
+ * v_xy float [N,2], v_conic [N,3], v_opacity [N], v_values [N]: cleared by the entry, then summed
+ * with float atomics (not bit-reproducible from run to run). */
+int gsr_distortion_forward(int tiles_x, int tiles_y, unsigned img_width, unsigned img_height,
+                           const int32_t *gaussian_ids_sorted, const int32_t *tile_bins,
+                           const float *xys, const float *conics, const float *opacities,
+                           const float *values, float *out_distortion, float *out_median,
+                           float *out_vsum, float *final_Ts, int32_t *final_idx,
+                           gsr_stream_t stream);
+int gsr_distortion_backward(unsigned img_height, unsigned img_width, int num_points,
+                            const int32_t *gaussian_ids_sorted, const int32_t *tile_bins,
+                            const float *xys, const float *conics, const float *opacities,
+                            const float *values, const float *out_vsum, const float *final_Ts,
+                            const int32_t *final_idx, const float *v_distortion, float *v_xy,
+                            float *v_conic, float *v_opacity, float *v_values,
+                            gsr_stream_t stream);
+
 /* ---- k nearest neighbours: points against a point cloud ----------------
  * What the toolkit's models ask scikit-learn for when they turn seed points into initial scales
  * (`k_nearest_sklearn`, vanilla_gs.py:136-140, 260-280), as a general query.  Reference points P

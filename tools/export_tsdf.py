@@ -120,6 +120,9 @@ def parse_args(argv=None):
     ap.add_argument("--rasterize-mode", default="classic", choices=["classic", "antialiased"],
                     help="the mode the model was trained in: antialiased composites opacities * compensation "
                          "(a model trained that way gives wrong depth and alpha in classic mode)")
+    ap.add_argument("--depth-mode", default="expected", choices=["expected", "median"],
+                    help="the depth of a view that is fused: the alpha-blended depth, or the depth of the Gaussian at "
+                         "which the transmittance crosses 0.5 (no blend of foreground and background at a silhouette)")
     add_obb_arguments(ap)
     a = ap.parse_args(argv)
     a.crop_box = obb_from_args(ap, a)
@@ -167,7 +170,7 @@ def main(argv=None):
     bg = torch.tensor(a.background, dtype=torch.float32, device=vol.device)
     fuse_views(vol, params, cams, bg, {1: 0, 4: 1, 9: 2, 16: 3}.get(K, 4), alpha_min=a.alpha_min,
                depth_trunc=a.depth_trunc, masks=masks, bounding_box=a.bounding_box, rasterize_mode=a.rasterize_mode,
-               crop_box=a.crop_box)
+               crop_box=a.crop_box, depth_mode=a.depth_mode)
     points, colors, normals = vol.extract_point_cloud()
     vertices, vcolors, triangles = vol.extract_mesh()
     os.makedirs(a.out, exist_ok=True)

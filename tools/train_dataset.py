@@ -4,7 +4,8 @@
     python tools/train_dataset.py DATA [--model gaussian-splatting|co-gs] [--iters 30000] [--output-dir outputs]
         [--eval-mode fraction|filename|interval|all] [--fused-render] [--use-graph] [--camera-optimizer SO3xR3]
         [--strategy default|mcmc [--cap-max 1000000]] [--bilateral-grid [--bilagrid-shape X Y L]]
-        [--normal-consistency [--normal-lambda 0.05] [--normal-start 7000]] ...
+        [--normal-consistency [--normal-lambda 0.05] [--normal-start 7000]]
+        [--depth-distortion [--distortion-lambda 100] [--distortion-start 3000]] ...
 
 `harness.train.train` with `TrainConfig.dataset`: the files are uploaded as integers into a
 gs_fused.ImageCache and every step's target comes from one kernel.  Writes `OUTPUT_DIR/step-*.ckpt` (the toolkit's
@@ -49,6 +50,11 @@ def parse_args(argv=None):
                          "--fused-render or --use-graph")
     ap.add_argument("--normal-lambda", type=float, default=0.05)
     ap.add_argument("--normal-start", type=int, default=7000, help="the term joins the loss after this iteration")
+    ap.add_argument("--depth-distortion", action="store_true",
+                    help="depth distortion loss (one more walk over the tile lists, forward and backward); not with "
+                         "--fused-render or --use-graph")
+    ap.add_argument("--distortion-lambda", type=float, default=100.0)
+    ap.add_argument("--distortion-start", type=int, default=3000, help="the term joins the loss after this iteration")
     ap.add_argument("--depth-loss-start-iteration", type=int, default=6000)
     ap.add_argument("--save-every", type=int, default=2000)
     ap.add_argument("--seed", type=int, default=0)
@@ -85,6 +91,8 @@ def main(argv=None):
         fused_render=a.fused_render, use_graph=a.use_graph, camera_optimizer=a.camera_optimizer,
         bilateral_grid=a.bilateral_grid, bilagrid_shape=tuple(a.bilagrid_shape),
         normal_consistency=a.normal_consistency, normal_lambda=a.normal_lambda, normal_start_iteration=a.normal_start,
+        depth_distortion=a.depth_distortion, distortion_lambda=a.distortion_lambda,
+        distortion_start_iteration=a.distortion_start,
         depth_loss_start_iteration=a.depth_loss_start_iteration, checkpoint_dir=a.output_dir, save_every=save_every,
         seed=a.seed, means_lr_schedule=True, log_every=max(a.iters // 100, 1),
         dataset_eval_mode=a.eval_mode, dataset_train_split_fraction=a.train_split_fraction,
