@@ -20,3 +20,4 @@ from .target import DeferredTarget, ImageCache, plane_from_int, target_from_u8  
 from .bilagrid import BilateralGrids, bilagrid_slice, bilagrid_tv_loss  # noqa: F401
 from .normals import depth_to_normal, gaussian_normals, normal_consistency_loss  # noqa: F401
 from .distortion import depth_distortion, distortion_loss  # noqa: F401
+from .contribution import ContributionStats, prune_gaussians, prune_mask, view_contributions  # noqa: F401

@@ -212,3 +212,37 @@ def render_view(
         normals_kw["distortion"], normals_kw["median_depth"] = dist[..., None], median[..., None]
     return {"rgb": rgb, "alpha": alpha, "depth": depth_im, "depth_acc": depth_acc, "xys": xys, "radii": radii,
             "depths": depths, "conics": conics, "num_tiles_hit": num_tiles_hit, "rgbs": rgbs, **normals_kw}
+
+
+@torch.no_grad()
+def contribution_stats(model, cams, cfg):
+    """-> `gs_fused.ContributionStats` of `model` (a `harness.train.GaussianParams`) over the views `cams`
+    (`CameraTensors`, at the resolution they state): per Gaussian the largest blend weight, the weight sum, the number
+    of (pixel, Gaussian) pairs and the number of pixels it dominates.  Every view is projected
+    by the separate ops and walked once by gs_fused's contribution walk, which builds the view's tile lists; with
+    `cfg.rasterize_mode == "antialiased"` the opacities are the compensated ones the RGB pass composites with.  The
+    statistics depend on no colour, so no image is composited and no SH degree enters.  No crop box.  CUDA only."""
+    from gs_fused import ContributionStats
+
+    g = model.gauss
+    if cfg.rasterize_mode not in ("classic", "antialiased"):
+        raise ValueError("Unknown rasterize_mode: %s" % cfg.rasterize_mode)
+    if not cams:
+        return ContributionStats(g["means"].shape[0], g["means"].device)
+    if getattr(model, "fused_activations", False) and g["means"].is_cuda:
+        from gs_fused import activate_gaussians
+
+        scales, quats, opac, _ = activate_gaussians(g["means"], g["scales"], g["quats"], g["opacities"],
+                                                    cams[0].campos)
+    else:
+        scales = torch.exp(g["scales"])
+        quats = g["quats"] / g["quats"].norm(dim=-1, keepdim=True)
+        opac = torch.sigmoid(g["opacities"])
+    stats = ContributionStats(g["means"].shape[0], g["means"].device)
+    for cam in cams:
+        xys, depths, radii, conics, comp, num_tiles_hit, _ = project_gaussians(
+            g["means"], scales, 1, quats, cam.viewmat[:3, :], cam.projmat, cam.fx, cam.fy, cam.cx, cam.cy,
+            cam.height, cam.width, BLOCK_WIDTH)
+        view_opac = opac * comp[:, None] if cfg.rasterize_mode == "antialiased" else opac
+        stats.accumulate(xys, depths, radii, conics, num_tiles_hit, view_opac, cam.height, cam.width, BLOCK_WIDTH)
+    return stats

@@ -574,6 +574,19 @@ class TrainConfig:
     distortion_start_iteration: int = 3000
     distortion_near: Optional[float] = 0.2
     distortion_far: Optional[float] = 100.0
+    # contribution-based pruning (gs_fused.ContributionStats / prune_mask; RadSplat,
+    # LightGaussian, Mini-Splatting): after the optimiser step and any refinement of every step listed in `prune_at`,
+    # the blend-weight statistics of the model over ALL training views (full resolution) are formed, the Gaussians the
+    # rule scores lowest are removed -- `prune_keep`: the fraction that stays; `prune_threshold`: scores below it go;
+    # neither: the rule's default threshold -- and the parameters, their Adam moments and the densification statistics
+    # are swapped as after a refinement that changed N.  Rules: "max_weight" (default threshold 0.01), "weight_sum"
+    # (needs one of the two), "dominant" (default threshold 1).  Steps after `stop_split_at` keep what was pruned: an
+    # earlier one is densified again.  The separate ops, `fused_render` and `use_graph` on one GPU; a world size above
+    # 1, `strategy="mcmc"`, `sharded_adam` and CPU tensors are refused.  `()`: nothing changes.
+    prune_at: tuple = ()
+    prune_rule: str = "max_weight"
+    prune_threshold: Optional[float] = None
+    prune_keep: Optional[float] = None
     # (sigma of the log-gain, sigma of the bias): every synthetic training target is multiplied once by a per-view,
     # per-channel gain exp(N(0, sigma_gain)) and shifted by N(0, sigma_bias), drawn from `view_exposure_seed`, standing
     # in for auto-exposure and white balance (a random background: the RGBA ground truth's colour is disturbed, its
@@ -769,6 +782,33 @@ def _check_depth_distortion(cfg: TrainConfig, device, world: int) -> None:
     if mod is not None and mod.is_deterministic():
         raise ValueError("depth_distortion does not run in deterministic mode: the walk's backward sums with float "
                          "atomics")
+
+
+def _check_prune(cfg: TrainConfig, device, world: int) -> None:
+    """What `prune_at` refuses, once the device and the world size are known."""
+    if not tuple(cfg.prune_at):
+        return
+    if world > 1:
+        raise ValueError("prune_at runs on one GPU (world size 1): the ranks of a data-parallel run do not form the "
+                         "statistics over all views together")
+    if cfg.strategy == "mcmc":
+        raise ValueError("prune_at does not run with strategy='mcmc': that strategy holds the model at its cap and "
+                         "relocates what pruning would remove")
+    if cfg.sharded_adam:
+        raise ValueError("prune_at does not run with sharded_adam: pruning moves whole rows of both Adam moments")
+    if device.type != "cuda":
+        raise ValueError("prune_at needs CUDA tensors: the contribution walk is a HIP kernel")
+    if cfg.prune_keep is not None and cfg.prune_threshold is not None:
+        raise ValueError("prune_at: give prune_keep or prune_threshold, not both")
+    from gs_fused.contribution import RULES
+
+    if cfg.prune_rule not in RULES:
+        raise ValueError(f"prune_at: unknown prune_rule {cfg.prune_rule!r}; known: {sorted(RULES)}")
+    if cfg.prune_keep is None and cfg.prune_threshold is None and RULES[cfg.prune_rule] is None:
+        raise ValueError(f"prune_at: prune_rule {cfg.prune_rule!r} has no default threshold; give prune_keep or "
+                         f"prune_threshold")
+    if cfg.prune_keep is not None and not (0.0 < cfg.prune_keep <= 1.0):
+        raise ValueError(f"prune_at: prune_keep must be a fraction in (0, 1], got {cfg.prune_keep}")
 
 
 def _params(model: GaussianParams) -> Dict[str, torch.nn.Parameter]:
@@ -1662,6 +1702,39 @@ def refine_model_mcmc(cfg: TrainConfig, mcfg, step: int, model, optims, exchange
         exchange.rebind(_params(model))
 
 
+def prune_model(cfg: TrainConfig, step: int, model, optims, exchange, stats: DensifyState, cams, history: list,
+                log: list) -> None:
+    """A step of `prune_at`: the contribution statistics over the views `cams`, the keep mask of `prune_rule`, and the
+    surviving rows of the parameters and their Adam moments installed as `refine_model` installs a refinement that
+    changed N.  `log` gets {step, n_in, n_out, ms} (ms: host time around the whole, the device drained at both ends)."""
+    from gs_fused import prune_gaussians, prune_mask
+
+    from .pipeline import contribution_stats
+
+    torch.cuda.synchronize(model.gauss["means"].device)
+    t0 = time.perf_counter()
+    n_in = model.num_points
+    with torch.no_grad():
+        cs = contribution_stats(model, cams, cfg)
+        keep = prune_mask(cs, cfg.prune_rule, threshold=cfg.prune_threshold, keep=cfg.prune_keep,
+                          scales=torch.exp(model.gauss["scales"]) if cfg.prune_rule == "weight_sum" else None)
+    if not bool(keep.all()):
+        old = _params(model)
+        moments = {}
+        for o in optims.values():
+            moments.update(_adam_moments(o, old))
+        new, new_moments = prune_gaussians(old, moments, keep)
+        model.replace(new)
+        cur = _params(model)
+        for o in optims.values():
+            _swap_parameters(o, old, cur, new_moments)
+        stats.reset(model.num_points)
+        history.append((step, model.num_points))
+        exchange.rebind(_params(model))
+    torch.cuda.synchronize(model.gauss["means"].device)
+    log.append({"step": step, "n_in": n_in, "n_out": model.num_points, "ms": 1e3 * (time.perf_counter() - t0)})
+
+
 def phase_record(marks, cfg: TrainConfig, factors) -> Dict:
     """The four `phase_ms_*` entries of the result from the steps' events: medians over all sampled steps, per
     resolution under a coarse-to-fine schedule, before / after co-gs' depth loss joins, and every sample."""
@@ -1720,6 +1793,7 @@ def result_record(cfg: TrainConfig, device, world: int, model, run: Dict, eval0:
             "densify_grad_thresh": (run["rcfg"].densify_grad_thresh if cfg.densify else None),
             # (only where it was asked for, as above)
             **({"dataset": run["dataset"]} if run.get("dataset") is not None else {}),
+            **({"prune": run["prune"]} if run.get("prune") is not None else {}),
             **run.get("pose", {}), **run.get("appearance", {})}
 
 
@@ -1738,6 +1812,7 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
     _check_bilateral_grid(cfg, device, world)
     _check_normal_consistency(cfg, device, world)
     _check_depth_distortion(cfg, device, world)
+    _check_prune(cfg, device, world)
     cuda = device.type == "cuda"
     mcfg = None
     if cfg.strategy == "mcmc":
@@ -1793,6 +1868,7 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
     if cfg.means_lr_schedule and sharded is None:
         means_group = (optims["all"] if "all" in optims else optims["means"]).param_groups[0]
     losses, history, exchanged_bytes = [], [], []  # history: (step, N) after every refinement that changed the model
+    prune_steps, prune_log = frozenset(int(s) for s in cfg.prune_at), []
     cams_by_d = data.cams_by_d
     if cuda:
         torch.cuda.synchronize(device)
@@ -1859,6 +1935,9 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
                     refine_model_mcmc(cfg, mcfg, step, model, optims, exchange, stats, history)
                 lr = means_lr(step, LRS["means"]) if cfg.means_lr_schedule else LRS["means"]
                 _mcmc_noise(model, lr * mcfg.noise_lr, cfg.refine_seed ^ 0x5DEECE66D, step)
+            if prune_steps and step in prune_steps:
+                prune_model(cfg, step, model, optims, exchange, stats,
+                            cams_by_d[1] if camera is None else camera.eval_cameras(data), history, prune_log)
             if cfg.save_every and cfg.checkpoint_dir and step > 0 and step % cfg.save_every == 0 and \
                     (rank == 0 or sharded is not None):
                 from .checkpoint import save_checkpoint
@@ -1903,6 +1982,7 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
                           **({} if data.exposure is None else {"view_exposure": data.exposure}),
                           **(_normal_record(cfg, run_step) if cfg.normal_consistency else {}),
                           **(_distortion_record(cfg, run_step) if cfg.depth_distortion else {})},
+           "prune": prune_log if prune_steps else None,
            "update": "reduce-scatter + sharded Adam + all-gather" if sharded is not None else
            ("all-reduce (geometry) + all-gathered colour cotangents (SH) + Adam" if sh_views else "all-reduce + Adam")}
     return result_record(cfg, device, world, model, run, eval0, eval1, phase_record(run_step.marks, cfg, data.factors))

@@ -1451,3 +1451,29 @@ def distortion_backward(img_height, img_width, gaussian_ids_sorted, tile_bins, x
                   vsum, final_Ts, final_idx, v_distortion, flat[:2 * n], flat[2 * n:5 * n], flat[5 * n:6 * n],
                   flat[6 * n:], _stream(dev))
     return flat[:2 * n].view(n, 2), flat[2 * n:5 * n].view(n, 3), flat[5 * n:6 * n], flat[6 * n:]
+
+
+def contribution_accumulate(tile_bounds, img_size, gaussian_ids_sorted, tile_bins, xys, conics, opacities, max_w, sum_q,
+                            hits, dominant) -> None:
+    """The contribution walk on given single-segment lists of 16 x 16 tiles (``gsr_contribution_accumulate``): ADDS the
+    view's blend-weight statistics to the caller's ``max_w`` float32 [N], ``sum_q``, ``hits`` and ``dominant`` int64
+    [N], in place.  A view without list entries launches nothing and changes nothing."""
+    W, H = int(img_size[0]), int(img_size[1])
+    if W < 1 or H < 1:
+        raise RuntimeError("contribution_accumulate: empty image")
+    if tuple(int(v) for v in tile_bounds[:2]) != ((W + 15) // 16, (H + 15) // 16):
+        raise RuntimeError(f"contribution_accumulate: tile bounds {tuple(tile_bounds)} are not those of a {W} x {H} "
+                           f"image in 16 x 16 tiles")
+    n, dev = xys.size(0), xys.device
+    for t, nm, dt in ((max_w, "max_w", _f32), (sum_q, "sum_q", torch.int64), (hits, "hits", torch.int64),
+                      (dominant, "dominant", torch.int64)):
+        if tuple(_check(t, nm, dt).shape) != (n,) or t.device != dev:
+            raise RuntimeError(f"{nm} must have dimensions ({n},) on the device of xys")
+    if gaussian_ids_sorted is None or gaussian_ids_sorted.numel() == 0 or n == 0:
+        return
+    _distortion_inputs(gaussian_ids_sorted, tile_bins, xys, conics, opacities, opacities)
+    if tile_bins.numel() < 2 * tile_bounds[0] * tile_bounds[1]:
+        raise RuntimeError("tile_bins must hold one (start, end) pair per tile")
+    with _on(dev):
+        _call("gsr_contribution_accumulate", tile_bounds[0], tile_bounds[1], W, H, n, gaussian_ids_sorted, tile_bins, xys,
+              conics, opacities, max_w, sum_q, hits, dominant, _stream(dev))

@@ -1640,6 +1640,31 @@ int gsr_distortion_backward(unsigned img_height, unsigned img_width, int num_poi
                             float *v_conic, float *v_opacity, float *v_values,
                             gsr_stream_t stream);
 
+/* ---- contribution statistics (csrc/contribution.hip) -------------------
+ * Per-Gaussian statistics of the blend weight over a view, what contribution-based pruning
+ * (RadSplat, LightGaussian, Mini-Splatting) scores with: one forward walk of its own over
+ * single-segment tile lists (ids int32 [I], bins int32 [tiles,2]; block width 16).
+ *
+ * The walk is the forward compositing's, as stated for gsr_distortion_forward above: pixel
+ * centre = the integer pixel coordinate, sigma = (a dx^2 + c dy^2) / 2 + b dx dy,
+ * alpha = min(0.999, opac exp(-sigma)); an entry with sigma < 0 or alpha < 1/255 is skipped;
+ * the walk stops BEFORE the entry that would make T (1 - alpha) <= 1e-4.  T is float32, and for
+ * every contributing (pixel, entry) pair w = alpha T is one float32 product.  With g the entry's
+ * Gaussian, the call ADDS to four arrays [num_points] the caller owns (zeros before the first
+ * view; V calls accumulate V views):
+ *   max_w[g]    = max(max_w[g], w)     float32; an integer atomic max on the bits (w > 0)
+ *   sum_q[g]   += (uint32)(w * 2^24)   int64; fixed point, truncated: independent of the order
+ *   hits[g]    += 1                    int64
+ *   dominant[g] += 1 per PIXEL whose largest w is g's entry; strictly greater replaces, so of
+ *                  equal weights the front-most entry wins.  int64
+ * No float atomics: every array is bit-reproducible from run to run.  A list entry whose id is
+ * outside [0, num_points) is skipped.  Pixels outside the image contribute nothing. */
+int gsr_contribution_accumulate(int tiles_x, int tiles_y, unsigned img_width, unsigned img_height,
+                                int num_points, const int32_t *gaussian_ids_sorted,
+                                const int32_t *tile_bins, const float *xys, const float *conics,
+                                const float *opacities, float *max_w, int64_t *sum_q,
+                                int64_t *hits, int64_t *dominant, gsr_stream_t stream);
+
 /* ---- k nearest neighbours: points against a point cloud ----------------
  * What the toolkit's models ask scikit-learn for when they turn seed points into initial scales
  * (`k_nearest_sklearn`, vanilla_gs.py:136-140, 260-280), as a general query.  Reference points P

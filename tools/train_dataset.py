@@ -5,7 +5,8 @@
         [--eval-mode fraction|filename|interval|all] [--fused-render] [--use-graph] [--camera-optimizer SO3xR3]
         [--strategy default|mcmc [--cap-max 1000000]] [--bilateral-grid [--bilagrid-shape X Y L]]
         [--normal-consistency [--normal-lambda 0.05] [--normal-start 7000]]
-        [--depth-distortion [--distortion-lambda 100] [--distortion-start 3000]] ...
+        [--depth-distortion [--distortion-lambda 100] [--distortion-start 3000]]
+        [--prune-at 16000,24000 [--prune-rule max_weight|weight_sum|dominant] [--prune-keep 0.6 | --prune-threshold T]] ...
 
 `harness.train.train` with `TrainConfig.dataset`: the files are uploaded as integers into a
 gs_fused.ImageCache and every step's target comes from one kernel.  Writes `OUTPUT_DIR/step-*.ckpt` (the toolkit's
@@ -55,6 +56,12 @@ def parse_args(argv=None):
                          "--fused-render or --use-graph")
     ap.add_argument("--distortion-lambda", type=float, default=100.0)
     ap.add_argument("--distortion-start", type=int, default=3000, help="the term joins the loss after this iteration")
+    ap.add_argument("--prune-at", default="", help="comma-separated steps after which the model is pruned by its blend-"
+                                                   "weight statistics over all training views (DESIGN.md 4.21)")
+    ap.add_argument("--prune-rule", default="max_weight", choices=["max_weight", "weight_sum", "dominant"])
+    ap.add_argument("--prune-keep", type=float, default=None, help="the fraction of the Gaussians that stays")
+    ap.add_argument("--prune-threshold", type=float, default=None,
+                    help="scores below it are removed (default: the rule's: max_weight 0.01, dominant 1)")
     ap.add_argument("--depth-loss-start-iteration", type=int, default=6000)
     ap.add_argument("--save-every", type=int, default=2000)
     ap.add_argument("--seed", type=int, default=0)
@@ -93,6 +100,8 @@ def main(argv=None):
         normal_consistency=a.normal_consistency, normal_lambda=a.normal_lambda, normal_start_iteration=a.normal_start,
         depth_distortion=a.depth_distortion, distortion_lambda=a.distortion_lambda,
         distortion_start_iteration=a.distortion_start,
+        prune_at=tuple(int(s) for s in a.prune_at.split(",") if s.strip()), prune_rule=a.prune_rule,
+        prune_keep=a.prune_keep, prune_threshold=a.prune_threshold,
         depth_loss_start_iteration=a.depth_loss_start_iteration, checkpoint_dir=a.output_dir, save_every=save_every,
         seed=a.seed, means_lr_schedule=True, log_every=max(a.iters // 100, 1),
         dataset_eval_mode=a.eval_mode, dataset_train_split_fraction=a.train_split_fraction,
