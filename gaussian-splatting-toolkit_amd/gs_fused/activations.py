@@ -9,6 +9,8 @@ GaussianSplattingModel.get_outputs (gs_toolkit/models/vanilla_gs.py:765-826) run
 as ~9 small launches forward and ~12 backward per iteration.  `activate_gaussians`
 returns the same four tensors from one kernel (`gsr_activate_forward`) and
 back-propagates through the first three with one kernel (`gsr_activate_backward`).
+Given ``filter_3d`` (gs_fused.filter3d, Mip-Splatting's 3D smoothing filter) the same two launches are
+`gsr_activate_filtered_forward` / `_backward`, with the filter folded into the scales and the opacity.
 """
 from typing import Optional, Tuple
 
@@ -66,16 +68,25 @@ class _Activate(Function):
 
 
 def activate_gaussians(means: Optional[Tensor], log_scales: Tensor, raw_quats: Tensor, opacity_logits: Tensor,
-                       camera_position: Optional[Tensor] = None
+                       camera_position: Optional[Tensor] = None, filter_3d: Optional[Tensor] = None
                        ) -> Tuple[Tensor, Tensor, Tensor, Optional[Tensor]]:
     """-> (exp(log_scales) [N,3], raw_quats / |raw_quats| [N,4], sigmoid(opacity_logits) [N,1],
     normalised (means - camera_position) [N,3] or None).  Differentiable w.r.t. the three
-    parameter tensors; the view directions carry no gradient (as in the reference)."""
+    parameter tensors; the view directions carry no gradient (as in the reference).
+
+    ``filter_3d`` (float32 [N] on the device, `gs_fused.sampling_filter_3d`; None: the unfiltered calls, unchanged):
+    the scales become ``s' = sqrt(s^2 + f^2)`` and the opacity ``o prod_k s_k / s'_k`` (`gs_fused.apply_filter_3d` states the rule); no
+    gradient reaches the filter; a row with ``f == 0`` carries the unfiltered call's bits, gradients included.  CUDA
+    tensors only (ValueError otherwise)."""
     n = log_scales.shape[0]
     if log_scales.shape != (n, 3) or raw_quats.shape != (n, 4) or opacity_logits.numel() != n:
         raise ValueError("expected scales [N,3], quats [N,4], opacities [N,1]")
     if camera_position is not None and (means is None or means.shape != (n, 3) or camera_position.numel() != 3):
         raise ValueError("view directions need means [N,3] and a camera position [3]")
+    if filter_3d is not None:
+        from .filter3d import activate_gaussians_filtered
+
+        return activate_gaussians_filtered(means, log_scales, raw_quats, opacity_logits, camera_position, filter_3d)
     return _Activate.apply(means.detach().contiguous() if camera_position is not None else None,
                            log_scales.contiguous(), raw_quats.contiguous(), opacity_logits.contiguous(),
                            camera_position.contiguous() if camera_position is not None else None)

@@ -30,6 +30,8 @@ _CAMERA_GROUP = "camera_opt"
 # the per-view bilateral grids (gs_fused.BilateralGrids, [V,L,Gh,Gw,12]; `to_gsplat` gives gsplat's layout) and their Adam
 _BILAGRID_KEY = "_model.bilateral_grids.grids"
 _BILAGRID_GROUP = "bilateral_grid"
+# the 3D smoothing filter (gs_fused.filter3d): one float32 [N] buffer next to the parameters, not one of them
+_FILTER_KEY = "_model.filter_3d"
 
 
 def checkpoint_path(directory: str, step: int) -> str:
@@ -106,6 +108,8 @@ def save_checkpoint(directory: str, step: int, model, optims: Dict[str, torch.op
     if bilagrid is not None:  # (gs_fused.BilateralGrids, its optimizer): the grids in their own channel-last layout
         pipeline[_BILAGRID_KEY] = bilagrid[0].grids.detach()
         opt_state[_BILAGRID_GROUP] = bilagrid[1].state_dict()
+    if getattr(model, "filter_3d", None) is not None:
+        pipeline[_FILTER_KEY] = model.filter_3d.detach()
     if not write:
         return None
     os.makedirs(directory, exist_ok=True)
@@ -146,6 +150,14 @@ def load_model_state(model, state: Dict[str, torch.Tensor]) -> int:
         new = torch.zeros((newp,) + tuple(old.shape[1:]), device=old.device, dtype=old.dtype)
         new.copy_(src)
         model.gauss[name] = torch.nn.Parameter(new)
+    # the 3D filter: restored when the checkpoint holds one; a buffer of another size does not survive the resize
+    saved = state.get(_FILTER_KEY)
+    if saved is not None:
+        if tuple(saved.shape) != (newp,):
+            raise ValueError(f"filter_3d: checkpoint holds {tuple(saved.shape)}, the model {newp} Gaussians")
+        model.filter_3d = saved.to(device=model.gauss["means"].device, dtype=torch.float32).contiguous()
+    elif getattr(model, "filter_3d", None) is not None and model.filter_3d.shape[0] != newp:
+        model.filter_3d = None
     return newp
 
 

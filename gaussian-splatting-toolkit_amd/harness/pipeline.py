@@ -232,8 +232,12 @@ def contribution_stats(model, cams, cfg):
     if getattr(model, "fused_activations", False) and g["means"].is_cuda:
         from gs_fused import activate_gaussians
 
+        # (the walk sees the filtered model, as every render does)
         scales, quats, opac, _ = activate_gaussians(g["means"], g["scales"], g["quats"], g["opacities"],
-                                                    cams[0].campos)
+                                                    cams[0].campos, filter_3d=getattr(model, "filter_3d", None))
+    elif getattr(model, "filter_3d", None) is not None:
+        raise ValueError("filter_3d needs fused_activations on CUDA tensors: the filter is folded into the "
+                         "activation kernels (gs_fused.apply_filter_3d is the torch form)")
     else:
         scales = torch.exp(g["scales"])
         quats = g["quats"] / g["quats"].norm(dim=-1, keepdim=True)

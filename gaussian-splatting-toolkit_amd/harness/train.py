@@ -277,6 +277,7 @@ def means_lr(step: int, lr_init: float = 1.6e-4, lr_final: float = 1.6e-6, max_s
 class GaussianParams(torch.nn.Module):
     split_sh = True  # evaluate SH from (features_dc, features_rest) without torch.cat
     fused_activations = True  # exp / normalise / sigmoid / view directions in one launch (gs_fused)
+    filter_3d = None  # Mip-Splatting's 3D smoothing filter, float32 [N] (gs_fused.sampling_filter_3d); not a parameter
 
     def __init__(self, raw: Dict[str, np.ndarray], device):
         super().__init__()
@@ -309,7 +310,10 @@ class GaussianParams(torch.nn.Module):
             from gs_fused import activate_gaussians
 
             scales, quats, opac, dirs = activate_gaussians(g["means"], g["scales"], g["quats"], g["opacities"],
-                                                           cam.campos)
+                                                           cam.campos, filter_3d=self.filter_3d)
+        elif self.filter_3d is not None:
+            raise ValueError("filter_3d needs fused_activations on CUDA tensors: the filter is folded into the "
+                             "activation kernels (gs_fused.apply_filter_3d is the torch form)")
         else:
             scales = torch.exp(g["scales"])
             quats = g["quats"] / g["quats"].norm(dim=-1, keepdim=True)
@@ -587,6 +591,17 @@ class TrainConfig:
     prune_rule: str = "max_weight"
     prune_threshold: Optional[float] = None
     prune_keep: Optional[float] = None
+    # Mip-Splatting's 3D smoothing filter (gs_fused.filter3d): the model holds one float32 [N]
+    # buffer `filter_3d` -- sqrt(0.2) over the largest fx / z of any training camera that sees the Gaussian, at the
+    # resolution being fitted -- and every render folds it into the scales and the opacity (training, evaluation and
+    # the contribution walk alike).  Recomputed before the first step, every `filter_3d_every` steps, right after
+    # anything that changes the model's rows (a refinement, a `prune_at` step) and when the resolution schedule changes
+    # factor; cameras as given (not the camera optimizer's).  Refinement, opacity reset and pruning work on the raw
+    # parameters.  Saved in checkpoints; `export_ply` writes the baked model (gs_fused.bake_filter_3d).  The separate
+    # ops on one GPU; `fused_render`, `use_graph`, `strategy="mcmc"`, a world size above 1, `fused_activations=False`
+    # and CPU tensors are refused.  Off: nothing changes.
+    filter_3d: bool = False
+    filter_3d_every: int = 100
     # (sigma of the log-gain, sigma of the bias): every synthetic training target is multiplied once by a per-view,
     # per-channel gain exp(N(0, sigma_gain)) and shifted by N(0, sigma_bias), drawn from `view_exposure_seed`, standing
     # in for auto-exposure and white balance (a random background: the RGBA ground truth's colour is disturbed, its
@@ -809,6 +824,71 @@ def _check_prune(cfg: TrainConfig, device, world: int) -> None:
                          f"prune_threshold")
     if cfg.prune_keep is not None and not (0.0 < cfg.prune_keep <= 1.0):
         raise ValueError(f"prune_at: prune_keep must be a fraction in (0, 1], got {cfg.prune_keep}")
+
+
+def _check_filter_3d(cfg: TrainConfig, device, world: int) -> None:
+    """What `filter_3d` refuses, once the device and the world size are known."""
+    if not cfg.filter_3d:
+        return
+    if cfg.fused_render:
+        raise ValueError("filter_3d needs the separate-ops path: the one-node view (fused_render) runs the unfiltered "
+                         "activations inside its single call")
+    if cfg.use_graph:
+        raise ValueError("filter_3d does not run under use_graph: the captured view holds the unfiltered activations")
+    if cfg.strategy == "mcmc":
+        raise ValueError("filter_3d does not run with strategy='mcmc': relocation and the opacity regulariser read the "
+                         "raw opacities, not the filtered ones")
+    if world > 1:
+        raise ValueError("filter_3d runs on one GPU (world size 1): the ranks of a data-parallel run do not agree on "
+                         "when the buffer is recomputed")
+    if not cfg.fused_activations:
+        raise ValueError("filter_3d needs fused_activations: the filter is folded into the activation kernels")
+    if device.type != "cuda":
+        raise ValueError("filter_3d needs CUDA tensors: the sampling pass and the filtered activations are HIP kernels")
+    if int(cfg.filter_3d_every) < 1:
+        raise ValueError(f"filter_3d: filter_3d_every must be a positive number of steps, got {cfg.filter_3d_every}")
+
+
+class Filter3DState:
+    """`TrainConfig.filter_3d`: the camera tables of the sampling pass, one per factor of the resolution schedule (the
+    training cameras as given), and when the model's buffer was last recomputed."""
+
+    def __init__(self, cfg: TrainConfig, data, device):
+        from gs_fused import filter_cameras
+
+        self.tables = {d: filter_cameras(cams, device) for d, cams in data.cams_by_d.items()}
+        self.every = int(cfg.filter_3d_every)
+        self.d, self.at, self.updates = None, None, 0
+
+    def update(self, model, d: int, step: int) -> None:
+        from gs_fused import sampling_filter_3d
+
+        model.filter_3d = sampling_filter_3d(model.gauss["means"].detach(), self.tables[d])
+        self.d, self.at = d, step
+        self.updates += 1
+
+    def start(self, cfg: TrainConfig, model, start_step: int) -> None:
+        """Before the first step (and the evaluation in front of it): a buffer restored from a checkpoint stays -- it
+        is what the interrupted run held at this step -- anything else is computed at this step's factor."""
+        f = model.filter_3d
+        if f is not None and f.shape[0] == model.num_points and start_step > 0:
+            self.d = downscale_factor(start_step - 1, cfg.num_downscales, cfg.resolution_schedule)
+        else:
+            self.update(model, downscale_factor(start_step, cfg.num_downscales, cfg.resolution_schedule), start_step)
+
+    def due(self, step: int, d: int) -> bool:
+        return d != self.d or (step % self.every == 0 and step != self.at)
+
+
+def export_parameters(model: GaussianParams, bake_filter: bool = True) -> Dict[str, np.ndarray]:
+    """The six raw parameter arrays `gs_io.write_gaussian_ply` takes; with a 3D filter on the model (and `bake_filter`)
+    the log-scales and opacity logits are the baked ones: the file rendered without a filter is the filtered model."""
+    out = {k: model.gauss[k].detach() for k in PARAM_NAMES}
+    if bake_filter and model.filter_3d is not None:
+        from gs_fused import bake_filter_3d
+
+        out["scales"], out["opacities"] = bake_filter_3d(out["scales"], out["opacities"], model.filter_3d)
+    return {k: v.cpu().numpy() for k, v in out.items()}
 
 
 def _params(model: GaussianParams) -> Dict[str, torch.nn.Parameter]:
@@ -1794,6 +1874,7 @@ def result_record(cfg: TrainConfig, device, world: int, model, run: Dict, eval0:
             # (only where it was asked for, as above)
             **({"dataset": run["dataset"]} if run.get("dataset") is not None else {}),
             **({"prune": run["prune"]} if run.get("prune") is not None else {}),
+            **({"filter_3d": run["filter_3d"]} if run.get("filter_3d") is not None else {}),
             **run.get("pose", {}), **run.get("appearance", {})}
 
 
@@ -1813,6 +1894,7 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
     _check_normal_consistency(cfg, device, world)
     _check_depth_distortion(cfg, device, world)
     _check_prune(cfg, device, world)
+    _check_filter_3d(cfg, device, world)
     cuda = device.type == "cuda"
     mcfg = None
     if cfg.strategy == "mcmc":
@@ -1851,6 +1933,12 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
         start_step = load_checkpoint(cfg.resume_from, model, optims, sharded=sharded,  # resizes the model to the saved N
                                      camera=None if camera is None else (camera.opt, camera.adam),
                                      **({} if bilagrid is None else {"bilagrid": (bilagrid.grids, bilagrid.adam)}))
+    f3d = None
+    if cfg.filter_3d:
+        f3d = Filter3DState(cfg, data, device)
+        f3d.start(cfg, model, start_step)
+    else:
+        model.filter_3d = None  # (a checkpoint written with a filter resumes as the raw model)
     use_fused = (cfg.fused_render or cfg.use_graph) and cuda and cfg.split_sh and cfg.fused_loss \
         and cfg.sh_degree in (0, 1, 2, 3)
     kernel = None
@@ -1898,6 +1986,9 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
             # this step's resolution (vanilla_gs.py:646-657, 719-720), background, ground truth and mask
             d = downscale_factor(step, cfg.num_downscales, cfg.resolution_schedule)
             cam = cams_by_d[d][v]
+            if f3d is not None and f3d.due(step, d):
+                f3d.update(model, d, step)
+            rows_changed = len(history)
             max_dim = max(cam.width, cam.height)  # `max(self.last_size)` of after_train / refinement_after
             bg_step, target, m_step = inputs(v, d)
             if camera is not None:  # this step's camera, a function of the view's six numbers
@@ -1938,6 +2029,8 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
             if prune_steps and step in prune_steps:
                 prune_model(cfg, step, model, optims, exchange, stats,
                             cams_by_d[1] if camera is None else camera.eval_cameras(data), history, prune_log)
+            if f3d is not None and len(history) != rows_changed:
+                f3d.update(model, d, step)  # new rows: the buffer follows before anything renders them
             if cfg.save_every and cfg.checkpoint_dir and step > 0 and step % cfg.save_every == 0 and \
                     (rank == 0 or sharded is not None):
                 from .checkpoint import save_checkpoint
@@ -1960,7 +2053,7 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
     if cfg.export_ply and rank == 0:
         from gs_io.ply import write_gaussian_ply
 
-        write_gaussian_ply(cfg.export_ply, {k: model.gauss[k].detach().cpu().numpy() for k in PARAM_NAMES})
+        write_gaussian_ply(cfg.export_ply, export_parameters(model))
     heldout = None
     if data.cache is not None and cfg.dataset_eval_split and cuda:
         from gs_io.dataset import load_dataset
@@ -1983,6 +2076,7 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
                           **(_normal_record(cfg, run_step) if cfg.normal_consistency else {}),
                           **(_distortion_record(cfg, run_step) if cfg.depth_distortion else {})},
            "prune": prune_log if prune_steps else None,
+           "filter_3d": None if f3d is None else {"every": f3d.every, "updates": f3d.updates},
            "update": "reduce-scatter + sharded Adam + all-gather" if sharded is not None else
            ("all-reduce (geometry) + all-gathered colour cotangents (SH) + Adam" if sh_views else "all-reduce + Adam")}
     return result_record(cfg, device, world, model, run, eval0, eval1, phase_record(run_step.marks, cfg, data.factors))

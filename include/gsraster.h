@@ -963,6 +963,56 @@ int gsr_activate_backward(int num_points, const float *raw_quats,
                           float *v_log_scales, float *v_raw_quats,
                           float *v_logits, gsr_stream_t stream);
 
+/* ---- 3D smoothing filter (csrc/filter3d.hip) -------------------------
+ * Mip-Splatting's 3D filter (Yu et al., CVPR 2024, section 4.1): every Gaussian is convolved with
+ * an isotropic Gaussian of the size its best-sampling training camera resolves.
+ *
+ * gsr_filter3d_sampling: means float [N,3]; cameras float [V,20] ON THE DEVICE, 16-byte aligned,
+ * per row [0,12) the top 3x4 of the world->camera matrix (row-major), [12,18) fx, fy, cx, cy,
+ * width, height, [18,20) unread.  Per Gaussian (X, Y, Z) and camera, in float32, every operation
+ * rounded on its own in the order written (tests/filter3d_reference.py restates it in NumPy):
+ *   x = ((r00 X + r01 Y) + r02 Z) + t0     (y with row 1, z with row 2)
+ *   u = (x / z) fx + cx,   w = (y / z) fy + cy
+ *   seen = z > near && u >= -(margin W) && u <= W + margin W
+ *                   && w >= -(margin H) && w <= H + margin H      (a NaN compares false: unseen)
+ *   nu = the largest fx / z over the cameras that see it, visited in index order; 0 when none does
+ *   filter = k / nu for the seen, k / min{nu : nu > 0} for the unseen (the largest filter of any
+ *            seen Gaussian), 0 for all when no camera sees any Gaussian.
+ * k = sqrt(variance) as the caller rounded it.  Three launches on `stream`: `workspace`
+ * (GSR_FILTER3D_WORKSPACE_BYTES on the device, 4-byte aligned, any content) is cleared, the rates
+ * go to filter_out and their smallest positive one into the workspace by an integer atomic on the
+ * bit patterns (no float atomics: bit-reproducible), and a second pass over filter_out applies
+ * the fallback.  No read-back, no synchronisation, nothing allocated: capturable.  num_points = 0
+ * launches nothing; num_cameras <= 0, a null pointer and a misaligned `cameras` are GSR_EINVAL
+ * before any launch.
+ *
+ * gsr_activate_filtered_forward / _backward: gsr_activate_forward / _backward with the filter
+ * folded into the scales and the opacity, filter_3d float [N], no gradient to it.  With
+ * s_k = exp(l_k), o = sigmoid(a), f = filter_3d[i]:
+ *   s'_k = sqrt(s_k^2 + f^2),   c = prod_k s_k / s'_k,   o' = o c        (scales, opacities)
+ *   v_a = v_o' c o (1 - o),   v_l_k = v_s'_k s_k^2 / s'_k + v_o' o c f^2 / s'_k^2
+ * Quaternions and view directions as in gsr_activate_forward.  A row with f == 0 takes the
+ * unfiltered expressions and carries the bits gsr_activate_forward / _backward produce.
+ * The backward reads the RAW log_scales and opacity_logits (5 words per Gaussian with the filter)
+ * rather than the forward's outputs (4 words): s_k cannot be recovered from s'_k and f where
+ * f >> s_k (s'^2 - f^2 cancels), and the raw parameters are alive anyway, so nothing extra is
+ * kept for the backward.  One launch each; v_scales / v_quats / v_opacities may each be NULL. */
+#define GSR_FILTER3D_WORKSPACE_BYTES 16
+int gsr_filter3d_sampling(int num_points, const float *means, int num_cameras,
+                          const float *cameras, float k, float near, float margin,
+                          float *filter_out, void *workspace, gsr_stream_t stream);
+int gsr_activate_filtered_forward(int num_points, const float *means, const float *log_scales,
+                                  const float *raw_quats, const float *opacity_logits,
+                                  const float *camera_position, const float *filter_3d,
+                                  float *scales, float *quats, float *opacities, float *viewdirs,
+                                  gsr_stream_t stream);
+int gsr_activate_filtered_backward(int num_points, const float *raw_quats,
+                                   const float *log_scales, const float *quats,
+                                   const float *opacity_logits, const float *filter_3d,
+                                   const float *v_scales, const float *v_quats,
+                                   const float *v_opacities, float *v_log_scales,
+                                   float *v_raw_quats, float *v_logits, gsr_stream_t stream);
+
 /* ---- densification statistics -----------------------------
  * GaussianSplattingModel.after_train (gs_toolkit/models/vanilla_gs.py:344-372) in
  * one launch: for every Gaussian with radii > 0,

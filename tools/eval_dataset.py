@@ -4,7 +4,7 @@
     python tools/eval_dataset.py DATA CHECKPOINT --output output.json [--split val] [--model gaussian-splatting]
 
 CHECKPOINT is a `step-*.ckpt` file in the toolkit's layout or a directory of them (the latest step).  Every view of the
-split is rendered at full size and measured by `harness.train.evaluate_dataset` (PSNR, SSIM, rays per second and frames
+split is rendered at full size (with the 3D smoothing filter the checkpoint holds, if any) and measured by `harness.train.evaluate_dataset` (PSNR, SSIM, rays per second and frames
 per second, with their standard deviations; LPIPS is not computed: no network weights ship with this package).  The
 output file has the four top-level keys of gs_toolkit/scripts/eval.py:39-44: `experiment_name`, `method_name`,
 `checkpoint`, `results`.  The dataparser options must be the ones the model was trained with.
@@ -45,7 +45,7 @@ def main(argv=None):
     if not a.output.endswith(".json"):
         raise SystemExit("eval_dataset: --output must be a .json file")
     import harness.train as HT
-    from export_gaussians import checkpoint_parameters
+    from export_gaussians import checkpoint_filter_3d, checkpoint_parameters
     from harness.checkpoint import latest_checkpoint
 
     device = torch.device(a.device)
@@ -54,6 +54,9 @@ def main(argv=None):
     bands = params["features_rest"].shape[1] + 1
     sh_degree = {1: 0, 4: 1, 9: 2, 16: 3, 25: 4}[bands]
     model = HT.GaussianParams({k: v.numpy() for k, v in params.items()}, device)
+    filter_3d = checkpoint_filter_3d(path, a.trust_pickle)
+    if filter_3d is not None:  # trained with TrainConfig.filter_3d: evaluated as trained
+        model.filter_3d = filter_3d.to(device)
     cfg = HT.TrainConfig(dataset=a.data, model=a.model, sh_degree=sh_degree, rasterize_mode=a.rasterize_mode,
                          dataset_eval_mode=a.eval_mode, dataset_train_split_fraction=a.train_split_fraction,
                          dataset_eval_interval=a.eval_interval, dataset_orientation_method=a.orientation_method,

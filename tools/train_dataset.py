@@ -6,7 +6,8 @@
         [--strategy default|mcmc [--cap-max 1000000]] [--bilateral-grid [--bilagrid-shape X Y L]]
         [--normal-consistency [--normal-lambda 0.05] [--normal-start 7000]]
         [--depth-distortion [--distortion-lambda 100] [--distortion-start 3000]]
-        [--prune-at 16000,24000 [--prune-rule max_weight|weight_sum|dominant] [--prune-keep 0.6 | --prune-threshold T]] ...
+        [--prune-at 16000,24000 [--prune-rule max_weight|weight_sum|dominant] [--prune-keep 0.6 | --prune-threshold T]]
+        [--filter-3d [--filter-3d-every 100]] ...
 
 `harness.train.train` with `TrainConfig.dataset`: the files are uploaded as integers into a
 gs_fused.ImageCache and every step's target comes from one kernel.  Writes `OUTPUT_DIR/step-*.ckpt` (the toolkit's
@@ -62,6 +63,10 @@ def parse_args(argv=None):
     ap.add_argument("--prune-keep", type=float, default=None, help="the fraction of the Gaussians that stays")
     ap.add_argument("--prune-threshold", type=float, default=None,
                     help="scores below it are removed (default: the rule's: max_weight 0.01, dominant 1)")
+    ap.add_argument("--filter-3d", action="store_true",
+                    help="Mip-Splatting's 3D smoothing filter from the training cameras' sampling rate (DESIGN.md 4.22); "
+                         "not with --fused-render, --use-graph or --strategy mcmc")
+    ap.add_argument("--filter-3d-every", type=int, default=100, help="steps between recomputations of the filter")
     ap.add_argument("--depth-loss-start-iteration", type=int, default=6000)
     ap.add_argument("--save-every", type=int, default=2000)
     ap.add_argument("--seed", type=int, default=0)
@@ -102,6 +107,7 @@ def main(argv=None):
         distortion_start_iteration=a.distortion_start,
         prune_at=tuple(int(s) for s in a.prune_at.split(",") if s.strip()), prune_rule=a.prune_rule,
         prune_keep=a.prune_keep, prune_threshold=a.prune_threshold,
+        filter_3d=a.filter_3d, filter_3d_every=a.filter_3d_every,
         depth_loss_start_iteration=a.depth_loss_start_iteration, checkpoint_dir=a.output_dir, save_every=save_every,
         seed=a.seed, means_lr_schedule=True, log_every=max(a.iters // 100, 1),
         dataset_eval_mode=a.eval_mode, dataset_train_split_fraction=a.train_split_fraction,
