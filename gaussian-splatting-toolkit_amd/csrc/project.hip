@@ -15,6 +15,25 @@
 // including the integer radii / num_tiles_hit, which sit behind a ceil() -- are then
 // bit-identical to the oracle's (tests/test_gpu_kernels.py::test_project_forward).  The
 // kernels are HBM-bound, so the few un-fused multiply-adds cost nothing measurable.
+//
+// Equidistant fisheye (FISH; gsplat's camera_model="fisheye" with an ideal lens).  For the
+// view-space centre t = V p~ of a Gaussian:
+//   * near plane: culled when tz <= clip, as above -- which also keeps the polar angle below 90 degrees;
+//   * pixel centre: r = sqrt(tx^2 + ty^2), theta = atan2(r, tz), s = theta / r (-> 1 / tz as r -> 0),
+//     xy = (fx s tx + cx - 0.5, fy s ty + cy - 0.5): pixel i has its centre at i, as on the pinhole path.  `projmat`
+//     is not read;
+//   * Jacobian, with d^2 = r^2 + tz^2 and c = (tz / d^2 - s) / r^2 (= 2 ds/d(r^2)):
+//       J = [ fx (s + tx^2 c)   fx tx ty c        -fx tx / d^2 ]
+//           [ fy tx ty c        fy (s + ty^2 c)   -fy ty / d^2 ]
+//     Below q = r^2 / tz^2 < GSR_FISHEYE_SERIES_Q, s and c (and dc/d(r^2), which the backward needs) come from their
+//     power series in q -- the closed forms are 0/0 at r = 0 and cancel next to it -- so every entry is finite and
+//     accurate from r = 0 upward, also where r^2 underflows;
+//   * no clamp of the centre, forward or backward: |J| <= max(fx, fy) / clip for tz > clip, and both directions
+//     differentiate the same function;
+//   * everything after J (cov2d = J W S W^T J^T, the +0.3, gsr_cov2d_bounds, the radius, gsr_tile_bbox) is the
+//     pinhole text, but for the compensation's determinant, which is formed from the minors of T M where scales and
+//     rotation are given (at its place in the kernel); depths = tz (ordering by ray distance |t| is not built);
+//   * backward: v_t = J^T v_xy + (dJ/dt contracted with v_J) + W's third row v_depth; the rest is the pinhole chain.
 #include "gsr_common.h"
 
 namespace {
@@ -61,6 +80,38 @@ __device__ __forceinline__ M3 quat_to_rot(float qw, float qx, float qy, float qz
   return R;
 }
 
+// s = theta / r, c = 2 ds/d(r^2), cu = dc/d(r^2) (GRAD only), w = 1 / d^2 of the equidistant projection (header).
+// Series: s tz = sum_k (-q)^k / (2k + 1), c tz^3 = sum_{k>=1} (-1)^k 2k / (2k + 1) q^(k-1),
+// cu tz^5 = sum_{k>=2} (-1)^k 2k (k - 1) / (2k + 1) q^(k-2); six terms each, first dropped term below 3e-8 relative
+// at the switch.  Above it the closed form of c loses 1.5 ulp / q: below 3e-6 relative, times q in J.
+#define GSR_FISHEYE_SERIES_Q 0.03125f
+struct Fisheye {
+  float s, c, cu, w;
+};
+template <bool GRAD>
+__device__ __forceinline__ Fisheye fisheye_terms(const float tx, const float ty, const float tz) {
+  Fisheye f;
+  const float r2 = tx * tx + ty * ty;  // (may underflow to 0: the series takes it)
+  const float z2 = tz * tz;
+  const float q = r2 / z2;
+  f.w = 1.f / (r2 + z2);
+  f.cu = 0.f;
+  if (q < GSR_FISHEYE_SERIES_Q) {
+    const float rz = 1.f / tz, rz3 = rz * rz * rz;
+    f.s = rz * (1.f + q * (-1.f / 3.f + q * (1.f / 5.f + q * (-1.f / 7.f + q * (1.f / 9.f + q * (-1.f / 11.f))))));
+    f.c = rz3 * (-2.f / 3.f + q * (4.f / 5.f + q * (-6.f / 7.f + q * (8.f / 9.f + q * (-10.f / 11.f + q * (12.f / 13.f))))));
+    if constexpr (GRAD)
+      f.cu = rz3 * rz * rz *
+             (4.f / 5.f + q * (-12.f / 7.f + q * (24.f / 9.f + q * (-40.f / 11.f + q * (60.f / 13.f + q * (-84.f / 15.f))))));
+  } else {
+    const float r = sqrtf(r2);
+    f.s = atan2f(r, tz) / r;
+    f.c = (tz * f.w - f.s) / r2;
+    if constexpr (GRAD) f.cu = (-tz * f.w * f.w - 1.5f * f.c) / r2;
+  }
+  return f;
+}
+
 struct Cam {
   float v[12];  // view matrix, top 3x4, row-major
   float p[16];  // full projection (P*V), row-major
@@ -81,8 +132,9 @@ template <typename T, typename... R>
 __device__ __forceinline__ const T &fwd_first(const T &t, const R &...) {
   return t;
 }
+// FISH: the equidistant fisheye's Jacobian and pixel centre (header) in place of the pinhole's; no clamp, no projmat.
 // X: nothing, FwdAA, FwdCrop, or FwdAA then FwdCrop (an empty pack leaves the classic kernel's signature as it was)
-template <bool AA, bool CROP, typename... X>
+template <bool AA, bool CROP, bool FISH, typename... X>
 __global__ __launch_bounds__(256) void project_fwd_kernel(
     const int n, const float *__restrict__ means3d,
     const float *__restrict__ scales, const float glob_scale,
@@ -95,7 +147,7 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(
     float *__restrict__ conics, float *__restrict__ compensation,
     int *__restrict__ num_tiles_hit, const X... aa) {
   static_assert(sizeof...(X) == (AA ? 1 : 0) + (CROP ? 1 : 0),
-                "project_fwd_kernel<AA, CROP, [FwdAA,] [FwdCrop]>: one argument per flag, in that order");
+                "project_fwd_kernel<AA, CROP, FISH, [FwdAA,] [FwdCrop]>: one argument per flag, in that order");
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
 
@@ -117,6 +169,18 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(
   }
 
   if (keep && tz > clip) {  // near-plane cull is `z <= clip` (helpers.cuh:212-219)
+    const M3 W{V[0], V[1], V[2], V[4], V[5], V[6], V[8], V[9], V[10]};
+    // FISH: T = J W is formed first, so that the minors of T M (the compensation, below) can be taken while M exists
+    [[maybe_unused]] M3 Tf;
+    [[maybe_unused]] float fish_s = 0.f, fish_det = 0.f;
+    if constexpr (FISH) {
+      const Fisheye f = fisheye_terms<false>(tx, ty, tz);
+      const float xyc = tx * ty * f.c;
+      const M3 J{fx * (f.s + tx * tx * f.c), fx * xyc, -fx * tx * f.w, fy * xyc, fy * (f.s + ty * ty * f.c), -fy * ty * f.w,
+                 0.f, 0.f, 0.f};
+      Tf = mul(J, W);
+      fish_s = f.s;
+    }
     M3 S;
     if (scales) {
       float w, x, y, z;
@@ -127,6 +191,17 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(
       const M3 M{R.a00 * s0, R.a01 * s1, R.a02 * s2, R.a10 * s0, R.a11 * s1,
                  R.a12 * s2, R.a20 * s0, R.a21 * s1, R.a22 * s2};
       S = mul(M, transpose(M));
+      if constexpr (FISH) {
+        // det C for the compensation.  C00 C11 - C01^2 loses every digit on an elongated footprint (a needle of
+        // 1 : 1000 has a determinant of 1e-6 of its terms).  C = A A^T with A = T M (2 x 3), and by Cauchy-Binet det C
+        // is the sum of the squares of A's three 2 x 2 minors -- each a product of two scales times a minor of T R,
+        // no cancellation between them.  Covariances handed in have no factor M: they keep the pinhole expression
+        const M3 A = mul(Tf, M);
+        const float m01 = A.a00 * A.a11 - A.a01 * A.a10;
+        const float m02 = A.a00 * A.a12 - A.a02 * A.a10;
+        const float m12 = A.a01 * A.a12 - A.a02 * A.a11;
+        fish_det = m01 * m01 + m02 * m02 + m12 * m12;
+      }
     } else {  // precomputed covariances: cov3d is an INPUT (upper triangle xx xy xz yy yz zz)
       const float *c = cov3d + 6 * i;
       S = M3{c[0], c[1], c[2], c[1], c[3], c[4], c[2], c[4], c[5]};
@@ -138,34 +213,47 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(
     o_cov[4] = S.a12;
     o_cov[5] = S.a22;
 
-    // EWA: clamp the centre to 1.3x the frustum, J = d(pix)/d(t)
-    const float limx = 1.3f * (0.5f * (float)img_w / fx);
-    const float limy = 1.3f * (0.5f * (float)img_h / fy);
-    const float ex = tz * fminf(limx, fmaxf(-limx, tx / tz));
-    const float ey = tz * fminf(limy, fmaxf(-limy, ty / tz));
-    const float rz = 1.f / tz, rz2 = rz * rz;
-    const M3 J{fx * rz, 0.f, -fx * ex * rz2, 0.f, fy * rz, -fy * ey * rz2, 0.f, 0.f, 0.f};
-    const M3 W{V[0], V[1], V[2], V[4], V[5], V[6], V[8], V[9], V[10]};
-    const M3 T = mul(J, W);
+    M3 T;
+    if constexpr (FISH) {
+      T = Tf;
+    } else {
+      // EWA: clamp the centre to 1.3x the frustum, J = d(pix)/d(t)
+      const float limx = 1.3f * (0.5f * (float)img_w / fx);
+      const float limy = 1.3f * (0.5f * (float)img_h / fy);
+      const float ex = tz * fminf(limx, fmaxf(-limx, tx / tz));
+      const float ey = tz * fminf(limy, fmaxf(-limy, ty / tz));
+      const float rz = 1.f / tz, rz2 = rz * rz;
+      const M3 J{fx * rz, 0.f, -fx * ex * rz2, 0.f, fy * rz, -fy * ey * rz2, 0.f, 0.f, 0.f};
+      T = mul(J, W);
+    }
     const M3 Vs{S.a00, S.a01, S.a02, S.a01, S.a11, S.a12, S.a02, S.a12, S.a22};
     const M3 C = mul(mul(T, Vs), transpose(T));
     const float det_orig = C.a00 * C.a11 - C.a01 * C.a01;
     const float c0 = C.a00 + 0.3f, c1 = C.a01, c2 = C.a11 + 0.3f;
     const float det_blur = c0 * c2 - c1 * c1;
-    const float comp = sqrtf(fmaxf(0.f, det_orig / det_blur));
+    float comp = sqrtf(fmaxf(0.f, det_orig / det_blur));
+    if constexpr (FISH) {  // det (C + 0.3 I) = det C + 0.3 tr C + 0.09: positive terms only
+      if (scales) comp = sqrtf(fish_det / (fish_det + 0.3f * (C.a00 + C.a11) + 0.09f));
+    }
 
     float k0, k1, k2, radius;
     if (gsr_cov2d_bounds(c0, c1, c2, k0, k1, k2, radius)) {
       o_k0 = k0;
       o_k1 = k1;
       o_k2 = k2;
-      const float *P = projmat;
-      const float hx = P[0] * px + P[1] * py + P[2] * pz + P[3];
-      const float hy = P[4] * px + P[5] * py + P[6] * pz + P[7];
-      const float hw = P[12] * px + P[13] * py + P[14] * pz + P[15];
-      const float rw = 1.f / (hw + 1e-6f);
-      const float u = 0.5f * (float)img_w * (hx * rw) + cx - 0.5f;
-      const float v = 0.5f * (float)img_h * (hy * rw) + cy - 0.5f;
+      float u, v;
+      if constexpr (FISH) {
+        u = fx * fish_s * tx + cx - 0.5f;
+        v = fy * fish_s * ty + cy - 0.5f;
+      } else {
+        const float *P = projmat;
+        const float hx = P[0] * px + P[1] * py + P[2] * pz + P[3];
+        const float hy = P[4] * px + P[5] * py + P[6] * pz + P[7];
+        const float hw = P[12] * px + P[13] * py + P[14] * pz + P[15];
+        const float rw = 1.f / (hw + 1e-6f);
+        u = 0.5f * (float)img_w * (hx * rw) + cx - 0.5f;
+        v = 0.5f * (float)img_h * (hy * rw) + cy - 0.5f;
+      }
       int minx, miny, maxx, maxy;
       gsr_tile_bbox(u, v, radius, tiles_x, tiles_y, 0.f, bw, minx, miny, maxx, maxy);
       const int area = (maxx - minx) * (maxy - miny);
@@ -180,6 +268,13 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(
     }
   }
 
+  if constexpr (FISH) {  // every output of a culled Gaussian is zero (the pinhole entries keep the covariance and the
+    if (o_tiles == 0) {  // conic of one that passed the near plane and was culled later, as the reference's kernel does)
+#pragma unroll
+      for (int k = 0; k < 6; ++k) o_cov[k] = 0.f;
+      o_k0 = o_k1 = o_k2 = 0.f;
+    }
+  }
   if (scales) {
 #pragma unroll
     for (int k = 0; k < 6; ++k) gsr_store_stream(cov3d + 6 * i + k, o_cov[k]);  // (read again by the backward only)
@@ -214,7 +309,8 @@ struct BwdChain {
 
 // AA: `v_comp_aa` (= v_opacities_aa * opacities, the antialiased opacity's share) is added to the compensation's
 // cotangent in float32, in front of its scaling.
-template <bool AA = false>
+// FISH: the equidistant fisheye's centre and Jacobian (header); the camera-gradient fields (vt0, vt1, vt3) stay zero.
+template <bool AA = false, bool FISH = false>
 __device__ __forceinline__ void project_bwd_chain(
     const int i, const float *__restrict__ means3d, const float *__restrict__ viewmat,
     const float *__restrict__ projmat, const float fx, const float fy, const int img_w, const int img_h,
@@ -226,18 +322,24 @@ __device__ __forceinline__ void project_bwd_chain(
   const float *P = projmat;
   const float *V = viewmat;
 
-  // pixel = ndc2pix(P p / (w + eps))  ->  d/dp  (helpers.cuh:125-142)
-  const float hx = P[0] * px + P[1] * py + P[2] * pz + P[3];
-  const float hy = P[4] * px + P[5] * py + P[6] * pz + P[7];
-  const float hw = P[12] * px + P[13] * py + P[14] * pz + P[15];
-  const float rw = 1.f / (hw + 1e-6f);
-  const float vnx = v_xy ? 0.5f * (float)img_w * v_xy[2 * i] : 0.f;
-  const float vny = v_xy ? 0.5f * (float)img_h * v_xy[2 * i + 1] : 0.f;
-  const float vt0 = vnx * rw, vt1 = vny * rw;
-  const float vt3 = -(vnx * hx + vny * hy) * rw * rw;
-  gm[0] = P[0] * vt0 + P[4] * vt1 + P[12] * vt3;
-  gm[1] = P[1] * vt0 + P[5] * vt1 + P[13] * vt3;
-  gm[2] = P[2] * vt0 + P[6] * vt1 + P[14] * vt3;
+  float vt0 = 0.f, vt1 = 0.f, vt3 = 0.f;
+  if constexpr (FISH) {
+    gm[0] = gm[1] = gm[2] = 0.f;  // (the centre's share joins v_t below, through J)
+  } else {
+    // pixel = ndc2pix(P p / (w + eps))  ->  d/dp  (helpers.cuh:125-142)
+    const float hx = P[0] * px + P[1] * py + P[2] * pz + P[3];
+    const float hy = P[4] * px + P[5] * py + P[6] * pz + P[7];
+    const float hw = P[12] * px + P[13] * py + P[14] * pz + P[15];
+    const float rw = 1.f / (hw + 1e-6f);
+    const float vnx = v_xy ? 0.5f * (float)img_w * v_xy[2 * i] : 0.f;
+    const float vny = v_xy ? 0.5f * (float)img_h * v_xy[2 * i + 1] : 0.f;
+    vt0 = vnx * rw;
+    vt1 = vny * rw;
+    vt3 = -(vnx * hx + vny * hy) * rw * rw;
+    gm[0] = P[0] * vt0 + P[4] * vt1 + P[12] * vt3;
+    gm[1] = P[1] * vt0 + P[5] * vt1 + P[13] * vt3;
+    gm[2] = P[2] * vt0 + P[6] * vt1 + P[14] * vt3;
+  }
 
   // depth = V[2,:] . p
   const float vz = v_depth ? v_depth[i] : 0.f;
@@ -272,8 +374,17 @@ __device__ __forceinline__ void project_bwd_chain(
   const float tx = V[0] * px + V[1] * py + V[2] * pz + V[3];
   const float ty = V[4] * px + V[5] * py + V[6] * pz + V[7];
   const float tz = V[8] * px + V[9] * py + V[10] * pz + V[11];
-  const float rz = 1.f / tz, rz2 = rz * rz, rz3 = rz2 * rz;
-  const M3 J{fx * rz, 0.f, -fx * tx * rz2, 0.f, fy * rz, -fy * ty * rz2, 0.f, 0.f, 0.f};
+  [[maybe_unused]] const float rz = 1.f / tz, rz2 = rz * rz, rz3 = rz2 * rz;
+  M3 J;
+  [[maybe_unused]] Fisheye f;
+  if constexpr (FISH) {
+    f = fisheye_terms<true>(tx, ty, tz);
+    const float xyc = tx * ty * f.c;
+    J = M3{fx * (f.s + tx * tx * f.c), fx * xyc, -fx * tx * f.w, fy * xyc, fy * (f.s + ty * ty * f.c), -fy * ty * f.w,
+           0.f, 0.f, 0.f};
+  } else {
+    J = M3{fx * rz, 0.f, -fx * tx * rz2, 0.f, fy * rz, -fy * ty * rz2, 0.f, 0.f, 0.f};
+  }
   const float *c3 = cov3d + 6 * i;
   const M3 Vs{c3[0], c3[1], c3[2], c3[1], c3[3], c3[4], c3[2], c3[4], c3[5]};
   const M3 Gc{g2[0], 0.5f * g2[1], 0.f, 0.5f * g2[1], g2[2], 0.f, 0.f, 0.f, 0.f};
@@ -292,10 +403,31 @@ __device__ __forceinline__ void project_bwd_chain(
               P1.a10 + P2.a10, P1.a11 + P2.a11, P1.a12 + P2.a12,
               P1.a20 + P2.a20, P1.a21 + P2.a21, P1.a22 + P2.a22};
   const M3 vJ = mul(vT, transpose(W));
-  const float vtx = -fx * rz2 * vJ.a02;
-  const float vty = -fy * rz2 * vJ.a12;
-  const float vtz = -fx * rz2 * vJ.a00 + 2.f * fx * tx * rz3 * vJ.a02 -
-                    fy * rz2 * vJ.a11 + 2.f * fy * ty * rz3 * vJ.a12;
+  float vtx, vty, vtz;
+  if constexpr (FISH) {
+    // sum(v_J * J) = ae s + m c - ct w with ae, m, ct below; s, c, w are functions of (r^2, tz) with
+    // ds/dtx = tx c, dc/dtx = 2 tx cu, dw/dtx = -2 tx w^2 (ty alike), ds/dtz = -w, dc/dtz = 2 w^2, dw/dtz = -2 tz w^2
+    const float A = fx * vJ.a00, B = fx * vJ.a01 + fy * vJ.a10, E = fy * vJ.a11;
+    const float Cx = fx * vJ.a02, Cy = fy * vJ.a12;
+    const float ae = A + E;
+    const float m = A * tx * tx + B * tx * ty + E * ty * ty;
+    const float ct = Cx * tx + Cy * ty;
+    const float w2 = f.w * f.w;
+    const float k = ae * f.c + 2.f * m * f.cu + 2.f * ct * w2;  // the factor of tx (ty) the three radial terms share
+    vtx = tx * k + (2.f * A * tx + B * ty) * f.c - Cx * f.w;
+    vty = ty * k + (B * tx + 2.f * E * ty) * f.c - Cy * f.w;
+    vtz = -ae * f.w + 2.f * m * w2 + 2.f * ct * tz * w2;
+    // xy = (fx s tx, fy s ty) + const:  v_t += J^T v_xy
+    const float vx = v_xy ? v_xy[2 * i] : 0.f, vy = v_xy ? v_xy[2 * i + 1] : 0.f;
+    vtx += J.a00 * vx + J.a10 * vy;
+    vty += J.a01 * vx + J.a11 * vy;
+    vtz += J.a02 * vx + J.a12 * vy;
+  } else {
+    vtx = -fx * rz2 * vJ.a02;
+    vty = -fy * rz2 * vJ.a12;
+    vtz = -fx * rz2 * vJ.a00 + 2.f * fx * tx * rz3 * vJ.a02 -
+          fy * rz2 * vJ.a11 + 2.f * fy * ty * rz3 * vJ.a12;
+  }
   gm[0] += vtx * W.a00 + vty * W.a10 + vtz * W.a20;
   gm[1] += vtx * W.a01 + vty * W.a11 + vtz * W.a21;
   gm[2] += vtx * W.a02 + vty * W.a12 + vtz * W.a22;
@@ -312,7 +444,7 @@ struct BwdAA {  // (v_opacities may be v_opacities_aa itself: read before the wr
   const float *opacities, *v_opacities_aa;
   float *v_opacities, *v_compensation_out;
 };
-template <bool AA, typename... X>  // X: nothing, or BwdAA
+template <bool AA, bool FISH, typename... X>  // X: nothing, or BwdAA
 __global__ __launch_bounds__(256) void project_bwd_kernel(
     const int n, const float *__restrict__ means3d,
     const float *__restrict__ scales, const float glob_scale,
@@ -325,7 +457,7 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
     const float *__restrict__ v_compensation, float *__restrict__ v_cov2d,
     float *__restrict__ v_cov3d, float *__restrict__ v_mean3d,
     float *__restrict__ v_scale, float *__restrict__ v_quat, const X... aa) {
-  static_assert(AA == (sizeof...(X) == 1), "project_bwd_kernel<true, BwdAA> or project_bwd_kernel<false>");
+  static_assert(AA == (sizeof...(X) == 1), "project_bwd_kernel<true, FISH, BwdAA> or project_bwd_kernel<false, FISH>");
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
 
@@ -345,7 +477,7 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(
   float gq[4] = {0.f, 0.f, 0.f, 0.f};
 
   if (radii[i] > 0) {
-    project_bwd_chain<AA>(i, means3d, viewmat, projmat, fx, fy, img_w, img_h, cov3d, conics, compensation, v_xy,
+    project_bwd_chain<AA, FISH>(i, means3d, viewmat, projmat, fx, fy, img_w, img_h, cov3d, conics, compensation, v_xy,
                           v_depth, v_conic, v_compensation, c, v_comp_aa);
 
     // cov3d = M M^T, M = R S  (backward.cu:427-453)
@@ -555,7 +687,7 @@ GSR_EXPORT int gsr_project_forward(
               "project_forward: pass both scales and quats, or neither (cov3d is then an input)");
   const int tiles_x = (int)gsr_cdiv(img_width, block_width);
   const int tiles_y = (int)gsr_cdiv(img_height, block_width);
-  hipLaunchKernelGGL((project_fwd_kernel<false, false>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
+  hipLaunchKernelGGL((project_fwd_kernel<false, false, false>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
                      (hipStream_t)stream, num_points, means3d, scales, glob_scale, quats,
                      viewmat, projmat, fx, fy, cx, cy, (int)img_width, (int)img_height,
                      tiles_x, tiles_y, (int)block_width, clip_thresh, cov3d, xys, depths,
@@ -582,7 +714,7 @@ GSR_EXPORT int gsr_project_forward_aa(
               "project_forward_aa: pass both scales and quats, or neither (cov3d is then an input)");
   const int tiles_x = (int)gsr_cdiv(img_width, block_width);
   const int tiles_y = (int)gsr_cdiv(img_height, block_width);
-  hipLaunchKernelGGL((project_fwd_kernel<true, false, FwdAA>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
+  hipLaunchKernelGGL((project_fwd_kernel<true, false, false, FwdAA>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
                      (hipStream_t)stream, num_points, means3d, scales, glob_scale, quats,
                      viewmat, projmat, fx, fy, cx, cy, (int)img_width, (int)img_height,
                      tiles_x, tiles_y, (int)block_width, clip_thresh, cov3d, xys, depths,
@@ -612,13 +744,13 @@ GSR_EXPORT int gsr_project_forward_crop(
   const int tiles_x = (int)gsr_cdiv(img_width, block_width);
   const int tiles_y = (int)gsr_cdiv(img_height, block_width);
   if (opacities) {
-    hipLaunchKernelGGL((project_fwd_kernel<true, true, FwdAA, FwdCrop>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
+    hipLaunchKernelGGL((project_fwd_kernel<true, true, false, FwdAA, FwdCrop>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
                        (hipStream_t)stream, num_points, means3d, scales, glob_scale, quats,
                        viewmat, projmat, fx, fy, cx, cy, (int)img_width, (int)img_height,
                        tiles_x, tiles_y, (int)block_width, clip_thresh, cov3d, xys, depths,
                        radii, conics, compensation, num_tiles_hit, FwdAA{opacities, opacities_aa}, FwdCrop{crop});
   } else {
-    hipLaunchKernelGGL((project_fwd_kernel<false, true, FwdCrop>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
+    hipLaunchKernelGGL((project_fwd_kernel<false, true, false, FwdCrop>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
                        (hipStream_t)stream, num_points, means3d, scales, glob_scale, quats,
                        viewmat, projmat, fx, fy, cx, cy, (int)img_width, (int)img_height,
                        tiles_x, tiles_y, (int)block_width, clip_thresh, cov3d, xys, depths,
@@ -659,7 +791,7 @@ GSR_EXPORT int gsr_project_backward(
               "project_backward: null pointer");
   GSR_REQUIRE((scales == nullptr) == (quats == nullptr), "project_backward: pass both scales and quats, or neither");
   GSR_REQUIRE(scales == nullptr || (v_scale && v_quat), "project_backward: null pointer");
-  hipLaunchKernelGGL((project_bwd_kernel<false>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
+  hipLaunchKernelGGL((project_bwd_kernel<false, false>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
                      (hipStream_t)stream, num_points, means3d, scales, glob_scale, quats,
                      viewmat, projmat, fx, fy, (int)img_width, (int)img_height, cov3d, radii,
                      conics, compensation, v_xy, v_depth, v_conic, v_compensation, v_cov2d,
@@ -689,13 +821,92 @@ GSR_EXPORT int gsr_project_backward_aa(
   // (v_opacities may be v_opacities_aa itself; nothing else may overlap what the kernel still reads)
   GSR_REQUIRE(v_compensation_out == nullptr || v_compensation_out != v_compensation,
               "project_backward_aa: v_compensation_out must not alias v_compensation");
-  hipLaunchKernelGGL((project_bwd_kernel<true, BwdAA>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
+  hipLaunchKernelGGL((project_bwd_kernel<true, false, BwdAA>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
                      (hipStream_t)stream, num_points, means3d, scales, glob_scale, quats,
                      viewmat, projmat, fx, fy, (int)img_width, (int)img_height, cov3d, radii,
                      conics, compensation, v_xy, v_depth, v_conic, v_compensation, v_cov2d,
                      v_cov3d, v_mean3d, v_scale, v_quat,
                      BwdAA{opacities, v_opacities_aa, v_opacities, v_compensation_out});
   GSR_CHECK_LAUNCH("project_backward_aa");
+  return GSR_OK;
+}
+
+// The fisheye entries: one each way for both rasterize modes (opacities / opacities_aa, and the backward's
+// opacities / v_opacities_aa / v_opacities, all NULL: the classic mode).
+GSR_EXPORT int gsr_project_forward_fisheye(
+    int num_points, const float *means3d, const float *scales, float glob_scale,
+    const float *quats, const float *viewmat, const float *projmat, float fx,
+    float fy, float cx, float cy, unsigned img_height, unsigned img_width,
+    unsigned block_width, float clip_thresh, const float *opacities, float *cov3d, float *xys,
+    float *depths, int32_t *radii, float *conics, float *compensation,
+    int32_t *num_tiles_hit, float *opacities_aa, gsr_stream_t stream) {
+  GSR_REQUIRE(num_points >= 0, "project_forward_fisheye: num_points < 0");
+  GSR_REQUIRE(block_width >= 2 && block_width <= 16, "project_forward_fisheye: block_width must be in [2,16]");
+  GSR_REQUIRE(img_height > 0 && img_width > 0, "project_forward_fisheye: empty image");
+  if (num_points == 0) return GSR_OK;
+  GSR_REQUIRE(means3d && viewmat && cov3d && xys && depths && radii && conics && compensation && num_tiles_hit,
+              "project_forward_fisheye: null pointer");  // (projmat is not read)
+  GSR_REQUIRE((opacities == nullptr) == (opacities_aa == nullptr),
+              "project_forward_fisheye: pass both opacities and opacities_aa, or neither");
+  GSR_REQUIRE((scales == nullptr) == (quats == nullptr),
+              "project_forward_fisheye: pass both scales and quats, or neither (cov3d is then an input)");
+  const int tiles_x = (int)gsr_cdiv(img_width, block_width);
+  const int tiles_y = (int)gsr_cdiv(img_height, block_width);
+  if (opacities) {
+    hipLaunchKernelGGL((project_fwd_kernel<true, false, true, FwdAA>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
+                       (hipStream_t)stream, num_points, means3d, scales, glob_scale, quats,
+                       viewmat, projmat, fx, fy, cx, cy, (int)img_width, (int)img_height,
+                       tiles_x, tiles_y, (int)block_width, clip_thresh, cov3d, xys, depths,
+                       radii, conics, compensation, num_tiles_hit, FwdAA{opacities, opacities_aa});
+  } else {
+    hipLaunchKernelGGL((project_fwd_kernel<false, false, true>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
+                       (hipStream_t)stream, num_points, means3d, scales, glob_scale, quats,
+                       viewmat, projmat, fx, fy, cx, cy, (int)img_width, (int)img_height,
+                       tiles_x, tiles_y, (int)block_width, clip_thresh, cov3d, xys, depths,
+                       radii, conics, compensation, num_tiles_hit);
+  }
+  GSR_CHECK_LAUNCH("project_forward_fisheye");
+  return GSR_OK;
+}
+
+GSR_EXPORT int gsr_project_backward_fisheye(
+    int num_points, const float *means3d, const float *scales, float glob_scale,
+    const float *quats, const float *viewmat, const float *projmat, float fx,
+    float fy, float cx, float cy, unsigned img_height, unsigned img_width,
+    const float *cov3d, const int32_t *radii, const float *conics,
+    const float *compensation, const float *opacities, const float *v_xy, const float *v_depth,
+    const float *v_conic, const float *v_compensation, const float *v_opacities_aa, float *v_cov2d,
+    float *v_cov3d, float *v_mean3d, float *v_scale, float *v_quat, float *v_opacities,
+    float *v_compensation_out, gsr_stream_t stream) {
+  (void)cx;
+  (void)cy;
+  GSR_REQUIRE(num_points >= 0, "project_backward_fisheye: num_points < 0");
+  if (num_points == 0) return GSR_OK;
+  GSR_REQUIRE(means3d && viewmat && cov3d && radii && conics && compensation && v_cov2d && v_cov3d && v_mean3d,
+              "project_backward_fisheye: null pointer");
+  GSR_REQUIRE((opacities == nullptr) == (v_opacities_aa == nullptr) && (opacities == nullptr) == (v_opacities == nullptr),
+              "project_backward_fisheye: pass opacities, v_opacities_aa and v_opacities, or none of them");
+  GSR_REQUIRE(opacities != nullptr || v_compensation_out == nullptr,
+              "project_backward_fisheye: v_compensation_out goes with opacities");
+  GSR_REQUIRE((scales == nullptr) == (quats == nullptr), "project_backward_fisheye: pass both scales and quats, or neither");
+  GSR_REQUIRE(scales == nullptr || (v_scale && v_quat), "project_backward_fisheye: null pointer");
+  GSR_REQUIRE(v_compensation_out == nullptr || v_compensation_out != v_compensation,
+              "project_backward_fisheye: v_compensation_out must not alias v_compensation");
+  if (opacities) {
+    hipLaunchKernelGGL((project_bwd_kernel<true, true, BwdAA>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
+                       (hipStream_t)stream, num_points, means3d, scales, glob_scale, quats,
+                       viewmat, projmat, fx, fy, (int)img_width, (int)img_height, cov3d, radii,
+                       conics, compensation, v_xy, v_depth, v_conic, v_compensation, v_cov2d,
+                       v_cov3d, v_mean3d, v_scale, v_quat,
+                       BwdAA{opacities, v_opacities_aa, v_opacities, v_compensation_out});
+  } else {
+    hipLaunchKernelGGL((project_bwd_kernel<false, true>), dim3(gsr_cdiv(num_points, 256)), dim3(256), 0,
+                       (hipStream_t)stream, num_points, means3d, scales, glob_scale, quats,
+                       viewmat, projmat, fx, fy, (int)img_width, (int)img_height, cov3d, radii,
+                       conics, compensation, v_xy, v_depth, v_conic, v_compensation, v_cov2d,
+                       v_cov3d, v_mean3d, v_scale, v_quat);
+  }
+  GSR_CHECK_LAUNCH("project_backward_fisheye");
   return GSR_OK;
 }
 

@@ -15,6 +15,7 @@ from .mcmc import (MCMCConfig, MCMCInfo, mcmc_add, mcmc_branch, mcmc_inject_nois
 from .render import DensifyStats, ListCapacity, ViewSpec, render_gaussians  # noqa: F401
 from rasterizer.project_gaussians import project_gaussians_antialiased  # noqa: F401
 from .crop import CropBox, crop_gaussians, project_gaussians_cropped  # noqa: F401
+from .fisheye import project_gaussians_fisheye  # noqa: F401
 from .knn import KNN, initial_log_scales, k_nearest, knn, knn_mean_distance  # noqa: F401
 from .target import DeferredTarget, ImageCache, plane_from_int, target_from_u8  # noqa: F401
 from .bilagrid import BilateralGrids, bilagrid_slice, bilagrid_tv_loss  # noqa: F401

@@ -97,6 +97,10 @@ def fuse_views(volume: TSDFVolume, params: Dict[str, Tensor], cameras: Sequence[
     Everything stays on the device as float32: there is NO round trip through 8-bit colour PNG and 16-bit millimetre
     depth PNG files as in the toolkit's file-based route, hence none of their quantisation -- a deliberate difference;
     and the host is not synchronised between views."""
+    for i, cam in enumerate(cameras):
+        if getattr(cam, "model", "pinhole") != "pinhole":
+            raise ValueError(f"fuse_views: camera {i} is a {cam.model} camera; TSDF integration projects voxels with "
+                             "pinhole intrinsics (fisheye fusion is not built)")
     dev = volume.device
     if rasterize_mode not in ("classic", "antialiased"):
         raise ValueError("Unknown rasterize_mode: %s" % rasterize_mode)
@@ -133,13 +137,20 @@ def fuse_views(volume: TSDFVolume, params: Dict[str, Tensor], cameras: Sequence[
 
 def read_poses_json(path: str) -> List[Camera]:
     """The trajectory file `TSDFFusion.read_trajectory` reads: a list of {"pose": 4x4 camera-to-world,
-    "camera": {width, height, fx, fy, cx, cy}}.  `viewmat` is the fp64 inverse of `pose`, rounded to fp32."""
+    "camera": {width, height, fx, fy, cx, cy}}.  `viewmat` is the fp64 inverse of `pose`, rounded to fp32.  The format
+    has no field for the camera model and every entry is read as a pinhole camera; an optional "camera_model" key in
+    "camera" (absent from the toolkit's files) is honoured: anything but "pinhole" / "perspective" raises ValueError,
+    since TSDF integration projects voxels with pinhole intrinsics."""
     with open(path) as f:
         entries = json.load(f)
     cams = []
     for e in entries:
         pose = np.asarray(e["pose"], np.float64).reshape(4, 4)
         c = e["camera"]
+        model = str(c.get("camera_model", c.get("model", "pinhole")))
+        if model.lower() not in ("pinhole", "perspective"):
+            raise ValueError(f"{path}: a {model} camera (fisheye?) cannot be fused; TSDF integration projects voxels with "
+                             "pinhole intrinsics")
         W, H = int(c["width"]), int(c["height"])
         fx, fy = float(c["fx"]), float(c["fy"])
         V = np.linalg.inv(pose).astype(np.float32)

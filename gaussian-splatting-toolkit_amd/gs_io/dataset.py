@@ -18,6 +18,7 @@ import torch
 from .ply import read_point_cloud_ply
 
 PERSPECTIVE_MODELS = ("SIMPLE_PINHOLE", "PINHOLE", "SIMPLE_RADIAL", "RADIAL", "OPENCV")
+FISHEYE_MODELS = ("OPENCV_FISHEYE",)  # read with `allow_fisheye` and zero distortion: the ideal equidistant lens
 DISTORTION_KEYS = ("k1", "k2", "k3", "k4", "p1", "p2")
 IMAGE_DEPTH_SUFFIXES = (".png", ".jpg", ".jpeg")
 
@@ -94,9 +95,11 @@ def auto_orient_and_center_poses(poses, method: str = "up", center_method: str =
 
 
 # ---- cameras (vanilla_gs.py:722-742, 770-771) -------------------------------------------------------------------
-def camera_from_pose(c2w: np.ndarray, fx: float, fy: float, cx: float, cy: float, width: int, height: int):
+def camera_from_pose(c2w: np.ndarray, fx: float, fy: float, cx: float, cy: float, width: int, height: int,
+                     model: str = "pinhole"):
     """`harness.scene.Camera` of a camera-to-world [3,4]: the y/z flip into the rasterizer's convention, the analytic
-    inverse, the fields of view from width / fx, `projection_matrix(0.001, 1000, fovx, fovy) @ viewmat` -- float32."""
+    inverse, the fields of view from width / fx, `projection_matrix(0.001, 1000, fovx, fovy) @ viewmat` -- float32.
+    `model`: "pinhole" or "fisheye" (the projection matrix is formed alike; the fisheye projection does not read it)."""
     from harness import scene as S
 
     c2w = torch.as_tensor(np.asarray(c2w, np.float32))
@@ -110,7 +113,7 @@ def camera_from_pose(c2w: np.ndarray, fx: float, fy: float, cx: float, cy: float
     fovx, fovy = 2 * math.atan(width / (2 * fx)), 2 * math.atan(height / (2 * fy))
     V = viewmat.numpy().copy()
     P = S.projection_matrix(0.001, 1000.0, fovx, fovy) @ V
-    return S.Camera(int(width), int(height), fx, fy, cx, cy, V, P.astype(np.float32))
+    return S.Camera(int(width), int(height), fx, fy, cx, cy, V, P.astype(np.float32), model)
 
 
 # ---- files (data/datasets/base_dataset.py:52-128, data/utils/data_utils.py:13-30) --------------------------------
@@ -174,6 +177,7 @@ class Dataset:
     mono_depth_shifts: List[float] = field(default_factory=list)
     depth_unit_scale_factor: float = 1e-3
     cameras: list = field(default_factory=list)  # harness.scene.Camera per view
+    camera_model: str = "pinhole"            # or "fisheye": OPENCV_FISHEYE with every distortion coefficient zero
 
     def __len__(self) -> int:
         return len(self.image_filenames)
@@ -249,9 +253,11 @@ def _split_indices(meta: Dict, split: str, names: List[str], rel: List[str], dat
 def load_dataset(path: str, split: str = "train", *, scale_factor: float = 1.0, downscale_factor: Optional[int] = None,
                  orientation_method: str = "up", center_method: str = "poses", auto_scale_poses: bool = False,
                  eval_mode: str = "fraction", train_split_fraction: float = 0.9, eval_interval: int = 8,
-                 depth_unit_scale_factor: float = 1e-3) -> Dataset:
+                 depth_unit_scale_factor: float = 1e-3, allow_fisheye: bool = False) -> Dataset:
     """`path`: a directory holding `transforms.json`, or the json itself.  The keyword arguments are the fields of
-    `GSToolkitDataParserConfig` with its defaults."""
+    `GSToolkitDataParserConfig` with its defaults.  `allow_fisheye`: also read `camera_model: OPENCV_FISHEYE` where
+    every distortion coefficient is zero (the ideal equidistant lens, `Dataset.camera_model == "fisheye"`): the caller
+    renders such cameras through gs_fused.project_gaussians_fisheye, nothing is undistorted."""
     path = os.fspath(path)
     if not os.path.exists(path):
         raise FileNotFoundError(f"Data directory {path} does not exist.")
@@ -263,10 +269,14 @@ def load_dataset(path: str, split: str = "train", *, scale_factor: float = 1.0, 
         raise ValueError(f"downscale_factor {downscale_factor}: downscaled image folders (images_{downscale_factor}/) "
                          f"are not read; the trainer's resolution schedule resizes on the GPU")
     model = meta.get("camera_model", "PINHOLE")
-    if model not in PERSPECTIVE_MODELS:
-        raise ValueError(f"camera_model {model!r} is not a perspective camera")
+    fisheye = allow_fisheye and model in FISHEYE_MODELS
+    if model not in PERSPECTIVE_MODELS and not fisheye:
+        raise ValueError(f"camera_model {model!r} is not a perspective camera"
+                         + (" (allow_fisheye=True reads it where every distortion coefficient is zero)"
+                            if model in FISHEYE_MODELS else ""))
     if meta.get("fisheye_crop_radius") is not None:
-        raise ValueError("fisheye_crop_radius: fisheye images are not supported")
+        raise ValueError("fisheye_crop_radius: fisheye images are not supported"
+                         + (" with a crop radius (pass the image circle as mask_path)" if fisheye else ""))
     _distortion("transforms.json", meta)
     if "applied_scale" in meta:
         scale_factor = float(meta["applied_scale"])
@@ -350,6 +360,7 @@ def load_dataset(path: str, split: str = "train", *, scale_factor: float = 1.0, 
                  scale=float(scale), transform=transform.numpy().astype(np.float32), points3D_xyz=xyz,
                  points3D_rgb=rgb, mono_depth_scales=pick(scales) if scales else [],
                  mono_depth_shifts=pick(shifts) if shifts else [], depth_unit_scale_factor=depth_unit_scale_factor)
-    ds.cameras = [camera_from_pose(c2w[i], ds.fx[i], ds.fy[i], ds.cx[i], ds.cy[i], ds.width, ds.height)
+    ds.camera_model = "fisheye" if fisheye else "pinhole"
+    ds.cameras = [camera_from_pose(c2w[i], ds.fx[i], ds.fy[i], ds.cx[i], ds.cy[i], ds.width, ds.height, ds.camera_model)
                   for i in range(len(ds))]
     return ds

@@ -163,7 +163,7 @@ class PosedCameras:
         """View `v` at `like`'s resolution and intrinsics, its pose corrected by `opt`."""
         viewmat, projmat, campos = view_matrices(opt.apply_to_camera(self.c2w[v], v), self.proj(like))
         return CameraTensors(like.width, like.height, like.fx, like.fy, like.cx, like.cy, viewmat, projmat,
-                             campos.detach(), like.scalars)
+                             campos.detach(), like.scalars, like.model)
 
     @torch.no_grad()
     def pose_errors(self, opt: Optional[CameraOptimizer]):
@@ -202,5 +202,5 @@ def perturb_cameras(cams_np, sigma_trans: float, sigma_rot: float, seed: int):
         V = V.astype(np.float32)
         fovx, fovy = 2.0 * math.atan(c.width / (2.0 * c.fx)), 2.0 * math.atan(c.height / (2.0 * c.fy))
         P = _scene_projection(0.001, 1000.0, fovx, fovy) @ V
-        out.append(Camera(c.width, c.height, c.fx, c.fy, c.cx, c.cy, V, P.astype(np.float32)))
+        out.append(Camera(c.width, c.height, c.fx, c.fy, c.cx, c.cy, V, P.astype(np.float32), c.model))  # (the pose moves, the camera model stays)
     return out

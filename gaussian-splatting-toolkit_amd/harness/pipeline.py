@@ -35,6 +35,8 @@ class CameraTensors:
     # [fx, fy, cx, cy, width, height] on the device: the toolkit's `Cameras` keeps its intrinsics there and
     # `get_outputs` reads them back one `.item()` at a time (vanilla_gs.py:736-740,772-773) -- `caller_syncs="camera"`
     scalars: Optional[torch.Tensor] = None
+    # "pinhole", or "fisheye": the equidistant camera (gs_fused.project_gaussians_fisheye; `projmat` is then not read)
+    model: str = "pinhole"
 
     @staticmethod
     def from_numpy(cam, device) -> "CameraTensors":
@@ -42,7 +44,7 @@ class CameraTensors:
         return CameraTensors(cam.width, cam.height, cam.fx, cam.fy, cam.cx, cam.cy,
                              t(cam.viewmat), t(cam.projmat), t(cam.campos),
                              torch.tensor([cam.fx, cam.fy, cam.cx, cam.cy, cam.width, cam.height], dtype=torch.float32,
-                                          device=device))
+                                          device=device), getattr(cam, "model", "pinhole"))
 
 
 def render_view(
@@ -102,11 +104,29 @@ def render_view(
         _ = (sc[2].item(), sc[3].item(), float(sc[4] / (2 * sc[0])), float(sc[5] / (2 * sc[1])), sc[4].item(),
              sc[5].item(), sc[0].item(), sc[1].item())
     opac_aa = None
-    if crop is None:
+    if crop is None and cam.model == "pinhole":
         xys, depths, radii, conics, comp, num_tiles_hit, cov3d = project_gaussians(
             means3d, scales, 1, quats, cam.viewmat[:3, :], cam.projmat, cam.fx, cam.fy, cam.cx, cam.cy,
             H, W, BLOCK_WIDTH,
         )
+    elif cam.model != "pinhole":
+        from gs_fused.fisheye import check_camera_model, project_gaussians_fisheye
+
+        check_camera_model(cam.model)
+        if crop is not None:
+            raise ValueError("render_view: crop is not built for the fisheye camera (there is no cropped fisheye "
+                             "projection)")
+        if render_normals:
+            raise ValueError("render_view: render_normals is pinhole only (depth_to_normal and the normal loss "
+                             "unproject with pinhole intrinsics)")
+        if rasterize_mode not in ("classic", "antialiased"):
+            raise ValueError("Unknown rasterize_mode: %s" % rasterize_mode)
+        res = project_gaussians_fisheye(
+            means3d, scales, 1, quats, cam.viewmat[:3, :], cam.projmat, cam.fx, cam.fy, cam.cx, cam.cy,
+            H, W, BLOCK_WIDTH, opacities=opacities if rasterize_mode == "antialiased" else None,
+        )
+        xys, depths, radii, conics, comp, num_tiles_hit, cov3d = res[:7]
+        opac_aa = res[7] if len(res) == 8 else None
     else:
         from gs_fused import project_gaussians_cropped
 
@@ -159,7 +179,7 @@ def render_view(
         assert (num_tiles_hit > 0).any()  # vanilla_gs.py:811 (a second blocking read-back)
 
     if rasterize_mode == "antialiased":
-        opac = opacities * comp[:, None] if opac_aa is None else opac_aa  # (cropped: the product left the kernel)
+        opac = opacities * comp[:, None] if opac_aa is None else opac_aa  # (cropped, fisheye: the product left the kernel)
     elif rasterize_mode == "classic":
         opac = opacities
     else:
@@ -221,12 +241,16 @@ def contribution_stats(model, cams, cfg):
     of (pixel, Gaussian) pairs and the number of pixels it dominates.  Every view is projected
     by the separate ops and walked once by gs_fused's contribution walk, which builds the view's tile lists; with
     `cfg.rasterize_mode == "antialiased"` the opacities are the compensated ones the RGB pass composites with.  The
-    statistics depend on no colour, so no image is composited and no SH degree enters.  No crop box.  CUDA only."""
+    statistics depend on no colour, so no image is composited and no SH degree enters.  No crop box; pinhole cameras only (a fisheye camera raises ValueError).  CUDA only."""
     from gs_fused import ContributionStats
 
     g = model.gauss
     if cfg.rasterize_mode not in ("classic", "antialiased"):
         raise ValueError("Unknown rasterize_mode: %s" % cfg.rasterize_mode)
+    for cam in cams:
+        if cam.model != "pinhole":
+            raise ValueError(f"contribution_stats: a {cam.model} camera; the walk's views are projected by the pinhole "
+                             "op (the fisheye camera is not built here)")
     if not cams:
         return ContributionStats(g["means"].shape[0], g["means"].device)
     if getattr(model, "fused_activations", False) and g["means"].is_cuda:

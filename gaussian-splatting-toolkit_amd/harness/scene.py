@@ -1,6 +1,6 @@
 """Synthetic scenes and cameras with the reference's conventions.
 
-Camera: rasterizer convention (x right, y down, z forward), pinhole, the
+Camera: rasterizer convention (x right, y down, z forward), pinhole (or, `model="fisheye"`, equidistant), the
 projection matrix of ``gs_toolkit/utils/comms.py:103-123`` (OpenGL-style,
 ``w_clip = z_view``).  Scene statistics follow SURVEY.md section 8(d):
 ``z ~ U(2,10)``, ``x,y ~ U(-1,1) * 1.1 * tan(fov/2) * z`` (about 10 % of the
@@ -46,6 +46,7 @@ class Camera:
     cy: float
     viewmat: np.ndarray  # [4,4] world->camera, row-major
     projmat: np.ndarray  # [4,4] P @ V
+    model: str = "pinhole"  # or "fisheye": equidistant, pixel = f * theta (gs_fused.project_gaussians_fisheye)
 
     @property
     def campos(self) -> np.ndarray:
@@ -54,9 +55,15 @@ class Camera:
 
 
 def make_camera(width: int, height: int, fov_x_deg: float = 60.0, yaw: float = 0.0,
-                pitch: float = 0.0, roll: float = 0.0, trans=(0.0, 0.0, 0.0)) -> Camera:
+                pitch: float = 0.0, roll: float = 0.0, trans=(0.0, 0.0, 0.0), model: str = "pinhole") -> Camera:
     fovx = math.radians(fov_x_deg)
-    fx = width / (2.0 * math.tan(fovx / 2.0))
+    if model == "fisheye":  # pixel = f * theta: half the width at half the field of view (which may pass 180 degrees)
+        fx = width / fovx
+        fovx = 2.0 * math.atan(width / (2.0 * fx))  # (the projection matrix of these intrinsics: the fisheye never reads it)
+    elif model != "pinhole":
+        raise ValueError(f"unknown camera model {model!r}")
+    else:
+        fx = width / (2.0 * math.tan(fovx / 2.0))
     fy = fx
     fovy = 2.0 * math.atan(height / (2.0 * fy))
     cy_, sy_ = math.cos(yaw), math.sin(yaw)
@@ -69,7 +76,7 @@ def make_camera(width: int, height: int, fov_x_deg: float = 60.0, yaw: float = 0
     V[:3, :3] = (Rz @ Rx @ Ry).astype(np.float32)
     V[:3, 3] = np.asarray(trans, dtype=np.float32)
     P = projection_matrix(0.001, 1000.0, fovx, fovy) @ V
-    return Camera(width, height, fx, fy, width / 2.0, height / 2.0, V, P.astype(np.float32))
+    return Camera(width, height, fx, fy, width / 2.0, height / 2.0, V, P.astype(np.float32), model)
 
 
 def num_sh_bases(degree: int) -> int:

@@ -48,7 +48,11 @@ LRS = {"means": 1.6e-4, "features_dc": 0.0025, "features_rest": 0.0025 / 20, "op
 SH_C0 = 0.28209479177387814
 
 
-def orbit_cameras(n_views: int, width: int, height: int, radius: float = 6.0, fov_x_deg: float = 60.0):
+FISHEYE_FOV_X_DEG = 150.0  # the synthetic fisheye cameras' horizontal field of view
+
+
+def orbit_cameras(n_views: int, width: int, height: int, radius: float = 6.0, fov_x_deg: float = 60.0,
+                  model: str = "pinhole"):
     """Cameras on a circle around the origin, all looking at it (rasterizer
     convention: x right, y down, z forward)."""
     cams = []
@@ -60,14 +64,14 @@ def orbit_cameras(n_views: int, width: int, height: int, radius: float = 6.0, fo
         right /= np.linalg.norm(right)
         down = np.cross(fwd, right)
         R = np.stack([right, down, fwd])  # world -> camera rows
-        cam = S.make_camera(width, height, fov_x_deg)
+        cam = S.make_camera(width, height, fov_x_deg, model=model)
         V = np.eye(4, dtype=np.float32)
         V[:3, :3] = R.astype(np.float32)
         V[:3, 3] = (-R @ eye).astype(np.float32)
-        fovx = math.radians(fov_x_deg)
+        fovx = math.radians(fov_x_deg) if model == "pinhole" else 2.0 * math.atan(width / (2.0 * cam.fx))
         fovy = 2.0 * math.atan(height / (2.0 * cam.fy))
         P = S.projection_matrix(0.001, 1000.0, fovx, fovy) @ V
-        cams.append(S.Camera(width, height, cam.fx, cam.fy, cam.cx, cam.cy, V, P.astype(np.float32)))
+        cams.append(S.Camera(width, height, cam.fx, cam.fy, cam.cx, cam.cy, V, P.astype(np.float32), model))
     return cams
 
 
@@ -82,7 +86,7 @@ def rescale_camera(cam, d: int):
     W, H = int(cam.width * f), int(cam.height * f)
     fovx, fovy = 2.0 * math.atan(W / (2.0 * fx)), 2.0 * math.atan(H / (2.0 * fy))
     P = S.projection_matrix(0.001, 1000.0, fovx, fovy) @ cam.viewmat
-    return S.Camera(W, H, fx, fy, cx, cy, cam.viewmat, P.astype(np.float32))
+    return S.Camera(W, H, fx, fy, cx, cy, cam.viewmat, P.astype(np.float32), cam.model)
 
 
 def downscale_factor(step: int, num_downscales: int, resolution_schedule: int) -> int:
@@ -419,6 +423,13 @@ class TrainConfig:
     # `ViewSpec.rasterize_mode` (the product inside the projection kernels).  A model trained in one mode renders
     # wrongly in the other.
     rasterize_mode: str = "classic"
+    # the camera model of every view: "pinhole", or "fisheye" -- the equidistant camera, pixel = f * theta, inside the
+    # projection kernels (gs_fused.project_gaussians_fisheye).  The synthetic cameras then
+    # span FISHEYE_FOV_X_DEG and the targets are rendered through the same model; with a `dataset` the model is the
+    # dataset's.  Everything behind the projection is camera-blind.  The separate ops on one GPU: `fused_render`,
+    # `use_graph`, `camera_optimizer`, `normal_consistency`, `filter_3d`, `prune_at` and a world size above 1 are
+    # refused.
+    camera_model: str = "pinhole"
     # absgrad (AbsGS; `absgrad` of gsplat / splatfacto): densification thresholds the accumulated norm of the per-pixel
     # |dL/dxy| sums instead of the signed screen-space gradient's, which cancels under a large Gaussian over texture.
     # Both step bodies: `ViewSpec.absgrad` on the one-node view and its graph, `rasterize_gaussians(absgrad=True)`
@@ -631,6 +642,7 @@ class TrainConfig:
     dataset_num_random: int = 50000
     dataset_random_scale: float = 10.0
     dataset_eval_split: Optional[str] = "val"
+    dataset_allow_fisheye: bool = False  # gs_io.dataset.load_dataset(allow_fisheye=...): read OPENCV_FISHEYE datasets
 
 
 def quantise_depth_mm(depth: torch.Tensor) -> torch.Tensor:
@@ -702,6 +714,28 @@ def _check_config(cfg: TrainConfig) -> None:
         if cfg.use_graph:
             raise ValueError("camera_optimizer needs the separate-ops path: a replayed HIP graph (use_graph) holds the "
                              "camera's matrices as constants of the capture")
+
+
+def _check_camera_model(cfg: TrainConfig, world: int) -> None:
+    """What `camera_model="fisheye"` refuses: everything that projects on its own."""
+    if cfg.camera_model not in ("pinhole", "fisheye"):
+        raise ValueError(f"unknown camera_model {cfg.camera_model!r}")
+    if cfg.camera_model == "pinhole":
+        return
+    if cfg.fused_render:
+        raise ValueError("camera_model='fisheye' does not run with fused_render: gsr_view_forward holds the pinhole projection")
+    if cfg.use_graph:
+        raise ValueError("camera_model='fisheye' does not run with use_graph: the captured view holds the pinhole projection")
+    if cfg.camera_optimizer != "off":
+        raise ValueError("camera_model='fisheye' does not run with camera_optimizer: the pose gradients differentiate the pinhole chain")
+    if cfg.normal_consistency:
+        raise ValueError("camera_model='fisheye' does not run with normal_consistency: depth_to_normal unprojects with pinhole intrinsics")
+    if cfg.filter_3d:
+        raise ValueError("camera_model='fisheye' does not run with filter_3d: its sampling rate is the pinhole's fx / z")
+    if tuple(cfg.prune_at):
+        raise ValueError("camera_model='fisheye' does not run with prune_at: contribution_stats projects on its own, through the pinhole")
+    if world > 1:
+        raise ValueError("camera_model='fisheye' runs on one GPU (world size 1): the data-parallel step was not taught the camera model")
 
 
 def _check_absgrad(cfg: TrainConfig, device) -> None:
@@ -956,7 +990,8 @@ def dataset_config(cfg: TrainConfig) -> Dict:
                 orientation_method=cfg.dataset_orientation_method, center_method=cfg.dataset_center_method,
                 auto_scale_poses=cfg.dataset_auto_scale_poses, eval_mode=cfg.dataset_eval_mode,
                 train_split_fraction=cfg.dataset_train_split_fraction, eval_interval=cfg.dataset_eval_interval,
-                depth_unit_scale_factor=cfg.dataset_depth_unit_scale_factor)
+                depth_unit_scale_factor=cfg.dataset_depth_unit_scale_factor,
+                **({"allow_fisheye": True} if cfg.dataset_allow_fisheye else {}))
 
 
 def upload_dataset(ds, device):
@@ -999,7 +1034,9 @@ def make_dataset_data(cfg: TrainConfig, device) -> TrainData:
 
 
 def make_data(cfg: TrainConfig, device) -> TrainData:
-    true_np = cams_np = orbit_cameras(cfg.num_views, cfg.width, cfg.height, radius=cfg.cam_radius)
+    fov = {} if cfg.camera_model == "pinhole" else {"fov_x_deg": FISHEYE_FOV_X_DEG}
+    true_np = cams_np = orbit_cameras(cfg.num_views, cfg.width, cfg.height, radius=cfg.cam_radius,
+                                      model=cfg.camera_model, **fov)
     true_cams = cams = [CameraTensors.from_numpy(c, device) for c in cams_np]
     if tuple(cfg.pose_noise) != (0.0, 0.0):  # the trainer's cameras carry a pose error; the images do not
         from .camera_opt import perturb_cameras
@@ -1866,6 +1903,7 @@ def result_record(cfg: TrainConfig, device, world: int, model, run: Dict, eval0:
             **({"rasterize_mode": cfg.rasterize_mode} if cfg.rasterize_mode != "classic" else {}),
             **({"absgrad": True} if cfg.absgrad else {}),
             **({"strategy": cfg.strategy} if cfg.strategy != "default" else {}),
+            **({"camera_model": cfg.camera_model} if cfg.camera_model != "pinhole" else {}),
             "depth": ({"loss_from_step": cfg.depth_loss_start_iteration + 1 if cfg.use_depth_loss else None,
                        "one_compositing_pass": bool(cfg.fused_depth and device.type == "cuda"),
                        "mean_abs_error_start_end": [eval0["depth_err"], eval1["depth_err"]]} if cogs else None),
@@ -1887,6 +1925,7 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
     """Fit a perturbed copy of a hidden scene to its own renders.  Returns timing
     and quality numbers; every rank ends with identical parameters."""
     _check_config(cfg)
+    _check_camera_model(cfg, world)
     _check_camera_optimizer(cfg, device, world)
     _check_absgrad(cfg, device)
     _check_mcmc(cfg, device, world)
@@ -1912,6 +1951,9 @@ def train(cfg: TrainConfig, device, rank: int = 0, world: int = 1) -> Dict:
         data = make_dataset_data(cfg, device)
         ds = data.dataset
         cfg = replace(cfg, num_views=len(ds), width=ds.width, height=ds.height)  # (a copy: the caller's is left alone)
+        if ds.camera_model != cfg.camera_model:  # the dataset's cameras decide
+            cfg = replace(cfg, camera_model=ds.camera_model)
+            _check_camera_model(cfg, world)
         model = dataset_initial_model(cfg, ds, device)
     else:
         data = make_data(cfg, device)

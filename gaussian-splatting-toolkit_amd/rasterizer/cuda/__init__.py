@@ -296,6 +296,94 @@ def project_gaussians_backward_aa(
     return v_cov2d, v_cov3d, v_mean3d, v_scale, v_quat, v_opacities, v_comp_out
 
 
+def project_gaussians_forward_fisheye(
+    num_points: int, means3d: Tensor, scales: Optional[Tensor], glob_scale: float, quats: Optional[Tensor],
+    viewmat: Tensor, projmat: Tensor, fx: float, fy: float, cx: float, cy: float,
+    img_height: int, img_width: int, block_width: int, clip_thresh: float,
+    opacities: Optional[Tensor] = None, cov3d_precomp: Optional[Tensor] = None,
+):
+    """-> (cov3d, xys, depths, radii, conics, compensation, num_tiles_hit, opacities_aa or None): the outputs of
+    ``project_gaussians_forward`` (with ``opacities``: of ``project_gaussians_forward_aa``) through the equidistant
+    fisheye camera (``gsr_project_forward_fisheye``, include/gsraster.h).  ``projmat`` is checked like the
+    pinhole entry's and not read."""
+    precomp = cov3d_precomp is not None
+    if precomp != (scales is None) or precomp != (quats is None):
+        raise RuntimeError("pass either scales and quats, or cov3d_precomp")
+    for t, nm in ((means3d, "means3d"), (viewmat, "viewmat"), (projmat, "projmat")) + (
+            ((cov3d_precomp, "cov3d_precomp"),) if precomp else ((scales, "scales"), (quats, "quats"))) + (
+            () if opacities is None else ((opacities, "opacities"),)):
+        _check(t, nm, _f32)
+    n = int(num_points)
+    if viewmat.numel() < 12 or projmat.numel() != 16:
+        raise RuntimeError("viewmat must hold at least 3x4 and projmat 4x4 values")
+    if means3d.numel() != 3 * n or (not precomp and (scales.numel() != 3 * n or quats.numel() != 4 * n)) \
+            or (precomp and cov3d_precomp.numel() != 6 * n) or (opacities is not None and opacities.numel() != n):
+        raise RuntimeError("means3d/scales/quats/opacities do not match num_points")
+    dev = means3d.device
+    with _on(dev):
+        e = lambda shape, dt=_f32: torch.empty(shape, dtype=dt, device=dev)  # noqa: E731
+        xys, depths, conics, compensation = e((n, 2)), e((n,)), e((n, 3)), e((n,))
+        radii, num_tiles_hit = e((n,), _i32), e((n,), _i32)
+        cov3d = cov3d_precomp if precomp else e((n, 6))
+        opacities_aa = None if opacities is None else e(tuple(opacities.shape))
+        _call("gsr_project_forward_fisheye", n, means3d, scales, glob_scale, quats, viewmat, projmat, fx, fy, cx, cy,
+              img_height, img_width, block_width, clip_thresh, opacities, cov3d, xys, depths, radii, conics,
+              compensation, num_tiles_hit, opacities_aa, _stream(dev))
+    return cov3d, xys, depths, radii, conics, compensation, num_tiles_hit, opacities_aa
+
+
+def project_gaussians_backward_fisheye(
+    num_points: int, means3d: Tensor, scales: Optional[Tensor], glob_scale: float, quats: Optional[Tensor],
+    viewmat: Tensor, projmat: Tensor, fx: float, fy: float, cx: float, cy: float,
+    img_height: int, img_width: int, cov3d: Tensor, radii: Tensor, conics: Tensor,
+    compensation: Tensor, opacities: Optional[Tensor], v_xy: Optional[Tensor], v_depth: Optional[Tensor],
+    v_conic: Optional[Tensor], v_compensation: Optional[Tensor], v_opacities_aa: Optional[Tensor] = None,
+    trusted: bool = False,
+):
+    """-> (v_cov2d, v_cov3d, v_mean3d, v_scale, v_quat, v_opacities or None): ``project_gaussians_backward`` (with
+    ``opacities``: ``project_gaussians_backward_aa``) through the equidistant fisheye camera.  A cotangent that is
+    None is zero; ``scales`` = ``quats`` = None: the covariances were handed in and the chain ends at v_cov3d."""
+    n = int(num_points)
+    dev = means3d.device
+    precomp = scales is None and quats is None
+    if not trusted:
+        for t, nm in ((means3d, "means3d"), (viewmat, "viewmat"), (projmat, "projmat"), (cov3d, "cov3d"),
+                      (conics, "conics"), (compensation, "compensation")) + (
+                () if precomp else ((scales, "scales"), (quats, "quats"))) + (
+                () if opacities is None else ((opacities, "opacities"),)):
+            _check(t, nm, _f32)
+        _check(radii, "radii", _i32)
+        if compensation.numel() != n or (opacities is not None and opacities.numel() != n):
+            raise RuntimeError("opacities/compensation do not match num_points")
+    v_xy, v_depth, v_conic, v_compensation = (
+        None if t is None else _check(t.contiguous(), nm, _f32)
+        for t, nm in ((v_xy, "v_xy"), (v_depth, "v_depth"), (v_conic, "v_conic"),
+                      (v_compensation, "v_compensation"))
+    )
+    with _on(dev):
+        e = lambda shape: torch.empty(shape, dtype=_f32, device=dev)  # noqa: E731
+        v_opacities = None
+        if opacities is None:
+            if v_opacities_aa is not None:
+                raise RuntimeError("v_opacities_aa without opacities")
+        else:
+            if v_opacities_aa is None:
+                v_opacities_aa = torch.zeros(tuple(opacities.shape), dtype=_f32, device=dev)
+            else:
+                v_opacities_aa = _check(v_opacities_aa.contiguous(), "v_opacities_aa", _f32)
+            if v_opacities_aa.numel() != n:
+                raise RuntimeError("v_opacities_aa does not match num_points")
+            v_opacities = e(tuple(opacities.shape))
+        v_cov2d, v_cov3d, v_mean3d = e((n, 3)), e((n, 6)), e((n, 3))
+        v_scale = None if precomp else e((n, 3))
+        v_quat = None if precomp else e((n, 4))
+        _call("gsr_project_backward_fisheye", n, means3d, scales, glob_scale, quats, viewmat, projmat, fx, fy, cx, cy,
+              img_height, img_width, cov3d, radii, conics, compensation, opacities, v_xy, v_depth, v_conic,
+              v_compensation, v_opacities_aa, v_cov2d, v_cov3d, v_mean3d, v_scale, v_quat, v_opacities, None,
+              _stream(dev))
+    return v_cov2d, v_cov3d, v_mean3d, v_scale, v_quat, v_opacities
+
+
 def project_gaussians_backward_pose(
     num_points: int, means3d: Tensor, viewmat: Tensor, projmat: Tensor, fx: float, fy: float,
     img_height: int, img_width: int, cov3d: Tensor, radii: Tensor, conics: Tensor, compensation: Tensor,

@@ -147,6 +147,48 @@ int gsr_project_forward_crop(int num_points, const float *means3d,
 int gsr_crop_mask(int num_points, const float *means3d, const float *crop,
                   uint8_t *mask, int32_t *count, gsr_stream_t stream);
 
+/* The equidistant fisheye camera (gsplat's camera_model="fisheye" with an ideal lens: every distortion coefficient
+ * of OPENCV_FISHEYE zero) inside the projection: the same kernels behind one more template flag.  For the view-space
+ * centre t = V p~: culled when tz <= clip_thresh (which keeps the polar angle below 90 degrees);
+ *   r = sqrt(tx^2 + ty^2), theta = atan2(r, tz), s = theta / r (1 / tz at r = 0),
+ *   xy = (fx s tx + cx - 0.5, fy s ty + cy - 0.5)   -- `projmat` is not read (may be NULL),
+ *   J = d(xy)/dt, finite and accurate from r = 0 upward (a power series below r^2 / tz^2 = 1/32), no clamp of the
+ *   centre in either direction; cov2d, conics, radii and the tile box follow from J as in gsr_project_forward;
+ *   the compensation is the same quantity, its determinants formed without cancellation where scales and quats are
+ *   given (accurate on needles; the pinhole expression where cov3d is handed in); depths = tz.  Every output of a
+ *   culled Gaussian is zero, cov3d and conics included.
+ * One entry each way for both rasterize modes: opacities / opacities_aa (forward) and opacities / v_opacities_aa /
+ * v_opacities (backward) are all NULL -- then the arguments and outputs are those of gsr_project_forward /
+ * gsr_project_backward -- or all given: those of the _aa entries (v_compensation_out stays nullable).
+ * No crop box and no camera gradients (gsr_project_backward_pose differentiates the pinhole chain). */
+int gsr_project_forward_fisheye(int num_points, const float *means3d,
+                                const float *scales, float glob_scale,
+                                const float *quats, const float *viewmat,
+                                const float *projmat, float fx, float fy,
+                                float cx, float cy, unsigned img_height,
+                                unsigned img_width, unsigned block_width,
+                                float clip_thresh, const float *opacities,
+                                float *cov3d, float *xys, float *depths,
+                                int32_t *radii, float *conics,
+                                float *compensation, int32_t *num_tiles_hit,
+                                float *opacities_aa, gsr_stream_t stream);
+int gsr_project_backward_fisheye(int num_points, const float *means3d,
+                                 const float *scales, float glob_scale,
+                                 const float *quats, const float *viewmat,
+                                 const float *projmat, float fx, float fy,
+                                 float cx, float cy, unsigned img_height,
+                                 unsigned img_width, const float *cov3d,
+                                 const int32_t *radii, const float *conics,
+                                 const float *compensation,
+                                 const float *opacities, const float *v_xy,
+                                 const float *v_depth, const float *v_conic,
+                                 const float *v_compensation,
+                                 const float *v_opacities_aa, float *v_cov2d,
+                                 float *v_cov3d, float *v_mean3d,
+                                 float *v_scale, float *v_quat,
+                                 float *v_opacities, float *v_compensation_out,
+                                 gsr_stream_t stream);
+
 /* Camera gradients of the projection (the reference has none: project_gaussians.py:156-232 returns None for both
  * matrices): v_viewmat[12] (top 3x4) and v_projmat[16], the sums over the Gaussians with radii > 0 of the terms
  * gsr_project_backward forms per Gaussian, under its conventions (no fov clamp; the compensation's cotangent scaled by

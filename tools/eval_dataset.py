@@ -61,7 +61,7 @@ def main(argv=None):
                          dataset_eval_mode=a.eval_mode, dataset_train_split_fraction=a.train_split_fraction,
                          dataset_eval_interval=a.eval_interval, dataset_orientation_method=a.orientation_method,
                          dataset_center_method=a.center_method, dataset_auto_scale_poses=a.auto_scale_poses,
-                         dataset_scale_factor=a.scale_factor)
+                         dataset_scale_factor=a.scale_factor, dataset_allow_fisheye=True)
     results = HT.evaluate_dataset(model, a.data, cfg, a.split, device)
     info = {"experiment_name": os.path.basename(os.path.normpath(os.path.dirname(a.data) if a.data.endswith(".json")
                                                                   else a.data)),

@@ -148,7 +148,10 @@ def main(argv=None):
     a = parse_args(argv)
 
     raw = read_gaussian_ply(a.ply)
-    cams = read_poses_json(a.poses)
+    try:
+        cams = read_poses_json(a.poses)  # (refuses a fisheye camera by name: fusion is pinhole only)
+    except ValueError as e:
+        raise SystemExit(f"export_tsdf: {e}") from None
     masks = load_masks(a.masks, len(cams)) if a.masks else None
     if a.bounds:
         lo, hi = np.asarray(a.bounds[:3]), np.asarray(a.bounds[3:])

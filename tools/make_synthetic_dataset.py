@@ -3,7 +3,7 @@
 gs_io.dataset.load_dataset) reads: `images/frame_00000.png ...` (RGBA with --alpha, straight colour; RGB over
 scene.BACKGROUND otherwise), `depths/*.png` (16 bit, millimetres, 0 = no measurement), `masks/*.png` (the object's
 silhouette, 0 / 255), `sparse_pc.ply` (a seed cloud: surface points with 8-bit colours) and `transforms.json`
-(camera-to-world matrices in the dataset convention -- x right, y up, z backwards -- and pinhole intrinsics, global or
+(camera-to-world matrices in the dataset convention -- x right, y up, z backwards -- and pinhole (or, --camera-model OPENCV_FISHEYE, equidistant) intrinsics, global or
 with --per-frame per frame).  The images are the ones `harness.train.make_data` renders for the same settings.
 
     python tools/make_synthetic_dataset.py OUT [--views 12 --width 64 --height 48 --alpha] [--device cpu]
@@ -57,20 +57,25 @@ def make_synthetic_dataset(out: str, views: int = 12, width: int = 64, height: i
                            depth: bool = True, mask: bool = True, device="cpu", scene: str = "ball",
                            num_gaussians: int = 600, seed_points: int = 200, seed: int = 0, per_frame: bool = False,
                            scene_scale=(0.03, 0.15), extra_meta=None, view_exposure=(0.0, 0.0),
-                           view_exposure_seed: int = 20241020) -> dict:
+                           view_exposure_seed: int = 20241020, camera_model: str = "PINHOLE") -> dict:
     """Writes the directory and returns the transforms.json dict.  `device` "cpu" needs the stand-ins wired
     (`use_cpu_standins`), as every CPU run of the harness does.  `view_exposure` (sigma of the log-gain, sigma of the
     bias): every image's colour is disturbed per view and channel before it is quantised, as
     `TrainConfig.view_exposure` disturbs the trainer's targets (`harness.train.disturb_exposure`); the gains and biases
-    go into transforms.json under "view_exposure"."""
+    go into transforms.json under "view_exposure".  `camera_model` "OPENCV_FISHEYE": the cameras are the trainer's
+    equidistant ones (`TrainConfig.camera_model="fisheye"`), the images are rendered through them, and transforms.json
+    states the model with `k1..k4 = 0` (gs_io.dataset.load_dataset reads it with `allow_fisheye=True`)."""
     from PIL import Image
 
     import harness.train as HT
     from gs_io.ply import write_point_cloud_ply
     from harness import scene as S
 
+    if camera_model not in ("PINHOLE", "OPENCV_FISHEYE"):
+        raise ValueError(f"camera_model must be PINHOLE or OPENCV_FISHEYE, got {camera_model!r}")
     device = torch.device(device)
-    cfg = HT.TrainConfig(num_gaussians=num_gaussians, width=width, height=height, num_views=views, seed=seed,
+    cfg = HT.TrainConfig(**({"camera_model": "fisheye"} if camera_model == "OPENCV_FISHEYE" else {}),
+                         num_gaussians=num_gaussians, width=width, height=height, num_views=views, seed=seed,
                          scene=scene, scene_scale=tuple(scene_scale), sh_degree=1,
                          background_color="random" if alpha else "fixed", model="co-gs" if depth else "gaussian-splatting",
                          mask="alpha" if mask else "none")
@@ -82,7 +87,9 @@ def make_synthetic_dataset(out: str, views: int = 12, width: int = 64, height: i
     for sub in ("images", "depths", "masks"):
         os.makedirs(os.path.join(out, sub), exist_ok=True)
     cam0 = data.true_cams_np[0]
-    meta = {"camera_model": "PINHOLE"}
+    meta = {"camera_model": camera_model}
+    if camera_model == "OPENCV_FISHEYE":
+        meta.update(k1=0.0, k2=0.0, k3=0.0, k4=0.0)
     intr = {"fl_x": float(cam0.fx), "fl_y": float(cam0.fy), "cx": float(cam0.cx), "cy": float(cam0.cy),
             "w": int(width), "h": int(height)}
     if not per_frame:
@@ -137,13 +144,16 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--view-exposure", type=float, nargs=2, default=[0.0, 0.0], metavar=("G", "B"),
                     help="per-view, per-channel gain exp(N(0, G)) and bias N(0, B) on every image")
+    ap.add_argument("--camera-model", default="PINHOLE", choices=["PINHOLE", "OPENCV_FISHEYE"],
+                    help="OPENCV_FISHEYE: equidistant cameras (every distortion coefficient zero), rendered as such")
     ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu", choices=["cpu", "cuda"])
     args = ap.parse_args()
     if args.device == "cpu":
         use_cpu_standins()
     meta = make_synthetic_dataset(args.out, args.views, args.width, args.height, args.alpha, not args.no_depth,
                                   not args.no_mask, args.device, args.scene, args.gaussians, args.seed_points,
-                                  args.seed, args.per_frame, view_exposure=tuple(args.view_exposure))
+                                  args.seed, args.per_frame, view_exposure=tuple(args.view_exposure),
+                                  camera_model=args.camera_model)
     print(json.dumps({"out": args.out, "frames": len(meta["frames"]), "width": args.width, "height": args.height}))
 
 

@@ -114,7 +114,8 @@ def main(argv=None):
         dataset_eval_interval=a.eval_interval, dataset_orientation_method=a.orientation_method,
         dataset_center_method=a.center_method, dataset_auto_scale_poses=a.auto_scale_poses,
         dataset_scale_factor=a.scale_factor, dataset_random_init=a.random_init, dataset_num_random=a.num_random,
-        dataset_random_scale=a.random_scale)
+        dataset_random_scale=a.random_scale,
+        dataset_allow_fisheye=True)  # (an OPENCV_FISHEYE dataset with zero distortion trains as camera_model="fisheye")
     os.makedirs(a.output_dir, exist_ok=True)
     res = HT.train(cfg, device)
     with open(os.path.join(a.output_dir, "result.json"), "w", encoding="utf-8") as f:
