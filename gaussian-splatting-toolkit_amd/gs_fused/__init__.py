@@ -23,3 +23,4 @@ from .normals import depth_to_normal, gaussian_normals, normal_consistency_loss 
 from .distortion import depth_distortion, distortion_loss  # noqa: F401
 from .contribution import ContributionStats, prune_gaussians, prune_mask, view_contributions  # noqa: F401
 from .filter3d import apply_filter_3d, bake_filter_3d, filter_cameras, sampling_filter_3d  # noqa: F401
+from .kmeans import KMeansResult, kmeans, kmeans_assign, kmeans_inertia, kmeans_update  # noqa: F401

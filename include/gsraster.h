@@ -1055,6 +1055,56 @@ int gsr_activate_filtered_backward(int num_points, const float *raw_quats,
                                    const float *v_opacities, float *v_log_scales,
                                    float *v_raw_quats, float *v_logits, gsr_stream_t stream);
 
+/* ---- k-means (csrc/kmeans.hip) -----------------------------------------
+ * Lloyd's k-means over N rows of D floats with K centres, 1 <= D <= GSR_KMEANS_MAX_DIM,
+ * 1 <= K <= GSR_KMEANS_MAX_CLUSTERS: what builds the codebook of the spherical-harmonics rows of a
+ * compressed export (gs_io.compressed).  points float [N,D], centroids float [K,D], row-major.
+ *
+ * gsr_kmeans_assign: labels int32 [N], dist float [N].  The rule, in float32
+ * (tests/kmeans_reference.py restates it in NumPy; the kernel is held to it bit for bit):
+ *   d(i,k) = sum_{j = 0..D-1} (x_ij - c_kj)^2, accumulated in the order j = 0, 1, ... from 0.0f;
+ *            the subtraction, the product and the addition each rounded on its own (no contraction)
+ *   best = +inf, label = 0;  for k = 0..K-1 in order:  if (d(i,k) < best) { best = d; label = k; }
+ * Ties go to the lowest index.  A row whose distances are all NaN or +inf keeps label 0, and dist
+ * takes the `best` that was left (+inf).  A NaN centroid never wins.  One launch; centroids pass
+ * through LDS in tiles of GSR_KMEANS_TILE rows.
+ *
+ * gsr_kmeans_update: order int32 [N] is the STABLE sort of 0..N-1 by label and offsets int32 [K+1]
+ * the segment starts (cluster k owns order[offsets[k] .. offsets[k+1])); weights float [N], >= 0,
+ * or NULL (every weight 1).  Per cluster and component, S_j = sum w_i x_ij and W = sum w_i in
+ * float64 (each product is exact); new_kj = float32(S_j / W).  The order of the additions depends
+ * on the segment's length and the launch constants only -- thread t of 256 adds the members
+ * t, t + 256, ... in order, a butterfly adds a wave's lanes, the four waves are added in index
+ * order -- and there are no atomics: bit-reproducible.  A cluster without a member, or with W == 0,
+ * copies old_centroids' bits; counts int32 [K] takes the segments' lengths.  A member whose label is
+ * not the segment's cluster or whose index is outside [0, N) is skipped, and offsets are clamped
+ * to [0, N].  new_centroids must not alias old_centroids.  One launch, K workgroups.
+ *
+ * gsr_kmeans_inertia: out double [1] on the device = sum_i w_i sum_j (x_ij - c_{l_i j})^2 with
+ * every operation in float64, j in index order, summed lane -> wave -> workgroup -> grid in a
+ * fixed order, no atomics (workspace: GSR_KMEANS_INERTIA_WORKSPACE_DOUBLES(N) doubles on the
+ * device, 8-byte aligned, any content).  A label outside [0, K) adds nothing.  This, not the
+ * float32 dist, is the quantity Lloyd's iteration decreases.  Two launches; N = 0 writes 0.
+ *
+ * All three: nothing allocated, no read-back, no synchronisation (capturable); sizes out of range
+ * and null pointers are GSR_EINVAL before any launch; N = 0 is allowed (assign launches nothing,
+ * update copies the old centroids and writes zero counts). */
+#define GSR_KMEANS_MAX_DIM 48
+#define GSR_KMEANS_MAX_CLUSTERS 65536
+#define GSR_KMEANS_TILE 128
+#define GSR_KMEANS_INERTIA_SHARE 1024 /* points per workgroup */
+#define GSR_KMEANS_INERTIA_WORKSPACE_DOUBLES(n) \
+  (((n) + GSR_KMEANS_INERTIA_SHARE - 1) / GSR_KMEANS_INERTIA_SHARE)
+int gsr_kmeans_assign(int num_points, int dim, int num_clusters, const float *points,
+                      const float *centroids, int32_t *labels, float *dist, gsr_stream_t stream);
+int gsr_kmeans_update(int num_points, int dim, int num_clusters, const float *points,
+                      const int32_t *labels, const int32_t *order, const int32_t *offsets,
+                      const float *weights, const float *old_centroids, float *new_centroids,
+                      int32_t *counts, gsr_stream_t stream);
+int gsr_kmeans_inertia(int num_points, int dim, int num_clusters, const float *points,
+                       const float *centroids, const int32_t *labels, const float *weights,
+                       double *out, void *workspace, gsr_stream_t stream);
+
 /* ---- densification statistics -----------------------------
  * GaussianSplattingModel.after_train (gs_toolkit/models/vanilla_gs.py:344-372) in
  * one launch: for every Gaussian with radii > 0,
