@@ -163,6 +163,74 @@ __global__ __launch_bounds__(64 * WAVES) void sh16_fwd_kernel(
   colors[3 * g + 2] = b;
 }
 
+// The same forward for a caller whose tile lists are being built on a second stream at that moment (rasterizer/ahead.py;
+// profiles/sh_beside_lists_{before,after}.txt).  The lists are the longer chain and latency-bound; this kernel yields:
+//  * a quarter of the LDS, 3.3 KB per wave instead of 13 KB (sh16_fwd_kernel at its three waves per SIMD holds 159.7 KB
+//    of a CU's 160 KB; gsr_p2::emit_kernel wants 143 KB).  The wave's twelve requests still go out first, then its 64
+//    rows pass through LDS sixteen at a time: quarter t is exactly the three requests 3 t .. 3 t + 2 (16 rows x 12
+//    float4 = 3 x 64), and lanes 16 t .. 16 t + 15 read their rows back.
+//  * optionally a narrow grid (GSR_SH_NARROW), whose waves loop over the rows: 3.6 TB/s instead of 6.3 TB/s alone.
+// The arithmetic is sh16_fwd_kernel's, expression for expression: the same bits.  One wave per workgroup: a wave
+// talks to no other wave, and the barriers are free.
+constexpr int kShQuarter = 16;  // rows per pass
+__global__ __launch_bounds__(64) void sh16_fwd_light_kernel(
+    const unsigned n, const unsigned deg_use, const float *__restrict__ viewdirs,
+    const float4 *__restrict__ coeffs, float *__restrict__ colors) {
+  __shared__ float4 lds[kShQuarter * kShRow];
+  const unsigned lane = threadIdx.x;
+  // (where the grid is narrower than the work a wave takes every gridDim.x-th run of 64 Gaussians)
+  for (unsigned g0 = blockIdx.x * 64; g0 < n; g0 += gridDim.x * 64) {
+    const unsigned navail = (n - g0 < 64 ? n - g0 : 64) * 12;
+    const float4 *src = coeffs + (size_t)g0 * 12;
+    const unsigned gd = g0 + lane < n ? g0 + lane : n - 1;
+    const float dx = viewdirs[3 * gd], dy = viewdirs[3 * gd + 1], dz = viewdirs[3 * gd + 2];
+    float4 q[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) {
+      const unsigned j = i * 64 + lane;
+      q[i] = j < navail ? gsr_load_stream(src + j) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    float4 row[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) row[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      __syncthreads();  // the previous quarter has been read
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const unsigned j = i * 64 + lane;  // float4 index inside this quarter: < 16 * 12
+        lds[(j / 12) * kShRow + j % 12] = q[3 * t + i];
+      }
+      __syncthreads();
+      if ((lane >> 4) == (unsigned)t) {
+#pragma unroll
+        for (int i = 0; i < 12; ++i) row[i] = lds[(lane & 15) * kShRow + i];
+      }
+    }
+    const unsigned g = g0 + lane;
+    if (g >= n) continue;  // (no barrier lies behind this point of the trip)
+    float B[16];
+    sh_basis<16>(deg_use, dx, dy, dz, B);
+    const float f[48] = {
+        row[0].x, row[0].y, row[0].z, row[0].w, row[1].x, row[1].y, row[1].z, row[1].w,
+        row[2].x, row[2].y, row[2].z, row[2].w, row[3].x, row[3].y, row[3].z, row[3].w,
+        row[4].x, row[4].y, row[4].z, row[4].w, row[5].x, row[5].y, row[5].z, row[5].w,
+        row[6].x, row[6].y, row[6].z, row[6].w, row[7].x, row[7].y, row[7].z, row[7].w,
+        row[8].x, row[8].y, row[8].z, row[8].w, row[9].x, row[9].y, row[9].z, row[9].w,
+        row[10].x, row[10].y, row[10].z, row[10].w, row[11].x, row[11].y, row[11].z, row[11].w};
+    float r = 0.f, gr = 0.f, b = 0.f;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      r += B[k] * sh_used(deg_use, k, f[3 * k]);
+      gr += B[k] * sh_used(deg_use, k, f[3 * k + 1]);
+      b += B[k] * sh_used(deg_use, k, f[3 * k + 2]);
+    }
+    colors[3 * g] = r;
+    colors[3 * g + 1] = gr;
+    colors[3 * g + 2] = b;
+  }
+}
+
 template <int WAVES>
 __global__ __launch_bounds__(64 * WAVES) void sh16_bwd_kernel(
     const unsigned n, const unsigned deg_use, const float *__restrict__ viewdirs,
@@ -570,15 +638,35 @@ GSR_EXPORT int gsr_sh_backward_views(unsigned num_points, unsigned degree, unsig
 // waves per workgroup of the K = 16 kernels (1 / 2 / 4 measured in round 3: 4)
 static int sh16_waves() { return 4; }
 
+// workgroups of sh16_fwd_light_kernel under GSR_SH_NARROW: two waves on each of the part's 256 CUs (384 ... 768 measured
+// alike beside the list build of the 1080p step, 256 and 1024 slower: profiles/sh_beside_lists_after.txt)
+constexpr unsigned kShNarrowGrid = 512;
+
 GSR_EXPORT int gsr_sh_forward(unsigned num_points, unsigned degree, unsigned degrees_to_use,
                               const float *viewdirs, const float *coeffs, float *colors,
                               gsr_stream_t stream) {
+  return gsr_sh_forward_flags(num_points, degree, degrees_to_use, viewdirs, coeffs, colors, 0u, stream);
+}
+
+GSR_EXPORT int gsr_sh_forward_flags(unsigned num_points, unsigned degree, unsigned degrees_to_use,
+                                    const float *viewdirs, const float *coeffs, float *colors,
+                                    unsigned flags, gsr_stream_t stream) {
   GSR_REQUIRE(degree <= 4, "sh_forward: degree must be in [0,4]");
   GSR_REQUIRE(degrees_to_use <= degree, "sh_forward: degrees_to_use > degree");
+  GSR_REQUIRE((flags & ~(unsigned)(GSR_SH_SHARE_CU | GSR_SH_NARROW)) == 0, "sh_forward: unknown flags");
+  GSR_REQUIRE(!(flags & GSR_SH_NARROW) || (flags & GSR_SH_SHARE_CU), "sh_forward: GSR_SH_NARROW without GSR_SH_SHARE_CU");
   if (num_points == 0) return GSR_OK;
   GSR_REQUIRE(viewdirs && coeffs && colors, "sh_forward: null pointer");
   hipStream_t s = (hipStream_t)stream;
   const dim3 blk(256), grd(gsr_cdiv(num_points, 256));
+  if (degree == 3 && (flags & GSR_SH_SHARE_CU) && aligned16(coeffs)) {
+    unsigned blocks = gsr_cdiv(num_points, 64);
+    if ((flags & GSR_SH_NARROW) && blocks > kShNarrowGrid) blocks = kShNarrowGrid;
+    hipLaunchKernelGGL(sh16_fwd_light_kernel, dim3(blocks), dim3(64), 0, s, num_points, degrees_to_use, viewdirs,
+                       reinterpret_cast<const float4 *>(coeffs), colors);
+    GSR_CHECK_LAUNCH("sh_forward");
+    return GSR_OK;
+  }
   switch (degree) {
     case 0: hipLaunchKernelGGL(sh_fwd_kernel<1>, grd, blk, 0, s, num_points, degrees_to_use, viewdirs, coeffs, colors); break;
     case 1: hipLaunchKernelGGL(sh_fwd_kernel<4>, grd, blk, 0, s, num_points, degrees_to_use, viewdirs, coeffs, colors); break;

@@ -50,11 +50,19 @@ def _R():
 # cannot be predicted (another recipe, no previous view) only the depth order is built ahead.  One more recipe: the
 # antialiased mode's `unary(leaf) * comp[:, None]` with the compensation of the projection that queues the lists
 # (`_product_signature` below).
-# WHEN: only while the caller is seen to block.  A caller without read-backs keeps the GPU's queue full; there is no
-# idle time to fill, and lists on a second stream merely compete with the SH kernel (bench default: +-0; 200 k
-# Gaussians / dense scales, where nothing is left to overlap with: +3 %).  The signal is the caller's stream itself: if
-# it is IDLE when `rasterize_gaussians` is entered, the host was blocked (or is the bottleneck) and the GPU had
-# nothing to do -- an exponential average of that observation above 1/2 switches the side stream on.  (A caller whose
+# WHEN: while the caller is seen to block, or runs this package's SH forward beside the lists.  A caller without
+# read-backs keeps the GPU's queue full; there is no idle time to fill, and beside kernels that stream at HBM speed the
+# latency-bound list kernels take up to twice as long -- whatever LDS the neighbour holds: the torch kernels of the view
+# directions slow them as the SH kernel does -- while each hand-off between the two streams costs 11-15 us
+# (profiles/sh_beside_lists_before.txt: of the 72 us of colour work that could hide behind the lists, 5 were left; 200 k
+# Gaussians / dense scales, where nothing is left to overlap with: +3 %).  Two signals switch the side stream on:
+#   * the caller's stream itself: if it is IDLE when `rasterize_gaussians` is entered, the host was blocked (or is the
+#     bottleneck) and the GPU had nothing to do -- an exponential average of that observation above 1/2;
+#   * on the previous view `rasterizer.sh`'s forward ran between `project_gaussians` and `rasterize_gaussians`
+#     (`note_sh_forward`): that kernel is ours and yields to the lists -- a quarter of the LDS, and for a caller whose
+#     stream is busy a narrow grid, since the colours have 130 us of slack and the lists have none (bench default
+#     0.9654 -> 0.9528 ms, profiles/sh_beside_lists_after.txt).  A caller that never calls our SH sees the first rule alone.
+# (A caller whose
 # opacity is the product recipe has its own multiply in flight at that moment: there the observation is whether the
 # projection, and all that was queued before it, had finished -- a weaker sign of a blocked host than an idle stream,
 # measured at one size only: 1 M Gaussians at 1080p, 0 -> 196 lists built ahead in 200 views)
@@ -131,6 +139,25 @@ def announce_opacity(opacity) -> None:
             st["recipe"] = ("same", weakref.ref(opacity))
 
 
+def note_sh_forward(device) -> int:
+    """(called by `rasterizer.sh` when it queues an SH forward) remember that this package's SH evaluation runs on
+    `device` between this view's projection and its `rasterize_gaussians` -- "WHEN" above -- and return the flags of
+    `rasterizer.cuda.compute_sh_forward` for it: while this view's tile lists are being built on the side stream, the
+    kernel that shares the compute units with them (`SH_SHARE_CU`) -- and, for a caller that keeps its queue full and
+    so does not wait for the colours, on a narrow grid (`SH_NARROW`): the lists are the longer chain, and a colour
+    kernel at full width only slows them down.  A caller that blocks on a read-back behind the SH forward waits for
+    that kernel: it runs at full width."""
+    with _R()._state_lock:
+        st = _spec.get(device)
+        if st is None:
+            return 0
+        st["sh_now"] = True
+        entry, busy = st["entry"], st.get("idle", 1.0) <= 0.5
+    if entry is None or entry["done"].query():
+        return 0
+    return _C.SH_SHARE_CU | (_C.SH_NARROW if busy else 0)
+
+
 def speculate_lists(xys, depths, radii, conics, num_tiles_hit, img_height, img_width, block_width, compensation=None,
                     node=None) -> None:
     """(called by `project_gaussians` once the projection is queued) start this view's depth order -- and, where the
@@ -158,8 +185,11 @@ def speculate_lists(xys, depths, radii, conics, num_tiles_hit, img_height, img_w
                 st["projected_event"] = torch.cuda.Event()  # (one per device, recorded again every view)
             st["projected"] = st["projected_event"]
             st["projected"].record(torch.cuda.current_stream(dev))
+        st["sh_now"] = False  # (an SH forward queued from here on belongs to this view)
         if mode == "auto":
-            if st.get("idle", 1.0) <= 0.5:  # the caller keeps the queue full: nothing to hide work behind
+            # the caller keeps the queue full -- and did not run our SH forward beside the previous view's lists either:
+            # nothing to hide work behind
+            if st.get("idle", 1.0) <= 0.5 and not st.get("sh_beside", False):
                 stale, st["entry"], st["retired"] = st["entry"], None, None  # (an entry nobody took: let go of its tensors)
                 if stale is not None:
                     torch.cuda.current_stream(dev).wait_event(stale["done"])

@@ -432,9 +432,13 @@ def _num_sh_bases(degree: int) -> int:
     return {0: 1, 1: 4, 2: 9, 3: 16}.get(int(degree), 25)
 
 
+SH_SHARE_CU, SH_NARROW = 1, 2  # GSR_SH_SHARE_CU, GSR_SH_NARROW (include/gsraster.h)
+
+
 def compute_sh_forward(num_points: int, degree: int, degrees_to_use: int, viewdirs: Tensor,
-                       coeffs: Tensor) -> Tensor:
-    """-> colors [N,3]; replaces ``compute_sh_forward_tensor`` (bindings.cu:58-77)."""
+                       coeffs: Tensor, flags: int = 0) -> Tensor:
+    """-> colors [N,3]; replaces ``compute_sh_forward_tensor`` (bindings.cu:58-77).  ``flags``: ``SH_SHARE_CU`` [``|
+    SH_NARROW``], the kernel that runs beside kernels of another stream (include/gsraster.h): the same bits."""
     n = int(num_points)
     if coeffs.dim() != 3 or coeffs.size(0) != n or coeffs.size(1) != _num_sh_bases(degree) \
             or coeffs.size(2) != 3:
@@ -444,7 +448,10 @@ def compute_sh_forward(num_points: int, degree: int, degrees_to_use: int, viewdi
     dev = coeffs.device
     with _on(dev):
         colors = torch.empty((n, 3), dtype=_f32, device=dev)
-        _call("gsr_sh_forward", n, degree, degrees_to_use, viewdirs, coeffs, colors, _stream(dev))
+        if flags:
+            _call("gsr_sh_forward_flags", n, degree, degrees_to_use, viewdirs, coeffs, colors, int(flags), _stream(dev))
+        else:
+            _call("gsr_sh_forward", n, degree, degrees_to_use, viewdirs, coeffs, colors, _stream(dev))
     return colors
 
 

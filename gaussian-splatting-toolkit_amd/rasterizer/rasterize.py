@@ -619,6 +619,8 @@ def build_tile_lists(xys, depths, radii, conics, num_tiles_hit, opacity, img_hei
                         and st.get("projected") is not None and st["projected"].query():
                     idle = 1.0  # only this opacity's own product is in flight: the projection finished long ago
                 st["idle"] = 0.75 * st.get("idle", 1.0) + 0.25 * idle
+                # the second signal: did this package's SH forward run since this view's projection?  (ahead.py)
+                st["sh_beside"], st["sh_now"] = st.get("sh_now", False), False
         ahead = _take_speculation(xys.device, key)
         if ahead is not None:
             main = torch.cuda.current_stream(xys.device)

@@ -10,6 +10,8 @@ from torch.autograd import Function
 
 import rasterizer.cuda as _C
 
+from . import ahead as _ahead
+
 # band count per degree; the reference answers 25 for any degree above 3
 _BAND_COUNT = (1, 4, 9, 16)
 _DEGREE_OF = {count: degree for degree, count in enumerate(_BAND_COUNT + (25,))}
@@ -32,7 +34,8 @@ class _SphericalHarmonics(Function):
     def forward(ctx, active_degree: int, dirs: Tensor, sh: Tensor):
         ctx.sizes = (sh.shape[0], deg_from_sh(sh.shape[-2]), active_degree)
         ctx.save_for_backward(dirs)
-        return _C.compute_sh_forward(*ctx.sizes, dirs, sh)
+        # while this view's tile lists are being built on the side stream: the kernel that runs beside them
+        return _C.compute_sh_forward(*ctx.sizes, dirs, sh, flags=_ahead.note_sh_forward(sh.device) if sh.is_cuda else 0)
 
     @staticmethod
     def backward(ctx, grad_colors: Tensor):

@@ -222,6 +222,21 @@ int gsr_project_backward_pose(int num_points, const float *means3d,
 int gsr_sh_forward(unsigned num_points, unsigned degree,
                    unsigned degrees_to_use, const float *viewdirs,
                    const float *coeffs, float *colors, gsr_stream_t stream);
+/* gsr_sh_forward with a flags word (0: gsr_sh_forward itself), for a caller
+ * with other kernels of its own in flight on another stream (tile lists
+ * built ahead).  Degree 3 with 16-byte aligned coeffs only; no effect
+ * elsewhere.  The same colours, bit for bit.
+ * GSR_SH_SHARE_CU: a quarter of the LDS per wave, so that kernels that need
+ * LDS fit on a compute unit beside this one.
+ * GSR_SH_NARROW (with GSR_SH_SHARE_CU): two waves per compute unit -- the
+ * kernel takes 2.5 x as long and leaves the memory system to the others;
+ * for a caller whose critical path is the other stream. */
+#define GSR_SH_SHARE_CU 1u
+#define GSR_SH_NARROW 2u
+int gsr_sh_forward_flags(unsigned num_points, unsigned degree,
+                         unsigned degrees_to_use, const float *viewdirs,
+                         const float *coeffs, float *colors, unsigned flags,
+                         gsr_stream_t stream);
 int gsr_sh_backward(unsigned num_points, unsigned degree,
                     unsigned degrees_to_use, const float *viewdirs,
                     const float *v_colors, float *v_coeffs,
